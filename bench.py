@@ -14,6 +14,13 @@ similarity + EgoNCE, backward (DDP gradient all-reduce overlapped), AdamW.  Work
 synthetic EgoClip batch, 4 x 3 x 224 x 224 frames + 32-token text, ViT-B/16 + DistilBERT, B = 32 per GPU,
 random-init weights (no network for checkpoints), inputs resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up (model, batch, the precision guard the trainer also runs before its first step), warms up, times `--steps`
+steps and prints the line.  `--full` adds every secondary measurement and check after the timed steps: per-kernel roofline and
+its PMC traffic, gradient error, trajectory drift, the single-pass bf16 / uint8-input / data-parallel-policy legs, exchange
+diagnostics at N > 1 and the CPU oracle baseline.  `--dump-outputs DIR` writes what the timed step computes from the state the
+timed steps started from (loss, a fixed sample of the updated parameters, gradient norms) as DIR/<name>.npy, for
+output-for-output comparisons of runs and builds.
 """
 import argparse
 import json
@@ -214,6 +221,64 @@ def trajectory_drift(model, loss_fn, make_opt, steps=20, B=8, T=4, L=32, modes=(
     return out
 
 
+DUMP_SAMPLE_PER_TENSOR = 8192       # the default model (327 parameter tensors): 1.2 M values = 4.7 MB
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def save_train_state(model):
+    """Everything a step reads besides the batch and the optimizer (a fresh AdamW is the optimizer's initial state): weights,
+    the precision policy in force (the guard may have demoted it; --full's fast-mode leg resets it), the fp16 backward's
+    loss-scale block, the text tower's dropout call counter, torch's RNG states."""
+    ec = model.exec_ctx
+    return {"weights": {k: v.detach().clone() for k, v in model.state_dict().items()},
+            "precision": {k: ec._s.get(k) for k in ("fwd_passes", "bwd_passes", "f16_single")},
+            "scaler": ec.loss_scaler().state.clone() if ec.bwd_passes == 4 else None,
+            "drop_calls": model.text_model._drop_calls, "rng": (torch.get_rng_state(), torch.cuda.get_rng_state())}
+
+
+def restore_train_state(model, saved):
+    from egovlp_amd import weights
+    model.load_state_dict(saved["weights"])
+    weights.bump_epoch()                      # the cached MFMA operand planes of the weights are stale now
+    ec = model.exec_ctx
+    ec.unset(*saved["precision"])
+    ec.set(**{k: v for k, v in saved["precision"].items() if v is not None})
+    if saved["scaler"] is not None:
+        model.exec_ctx.loss_scaler().state.copy_(saved["scaler"])
+    model.text_model._drop_calls = saved["drop_calls"]
+    torch.set_rng_state(saved["rng"][0])
+    torch.cuda.set_rng_state(saved["rng"][1])
+
+
+def dump_outputs(out_dir, model, loss_val, seed=0):
+    """What a caller of the timed step holds after the call, as .npy files in `out_dir`: the loss it returned (float32), the
+    parameters it updated in place (float32) -- for each parameter tensor (named_parameters order) all of it when it has at most
+    DUMP_SAMPLE_PER_TENSOR elements, else that many flat indices drawn by a generator seeded with (seed, tensor index), so the
+    sample is the same in every run and every build -- and the L2 norm of each parameter's gradient, loss scale divided out
+    (float64; 0 without a gradient): the magnitudes that AdamW's first, sign-like update hides in the parameters."""
+    import numpy as np
+    ec = model.exec_ctx
+    scale = ec.loss_scaler().get_scale() if ec.bwd_passes == 4 else 1.0
+    gn = torch.stack([torch.zeros((), dtype=torch.float64, device=p.device) if p.grad is None else
+                      torch.linalg.vector_norm(p.grad.detach(), dtype=torch.float64) for p in model.parameters()]) / scale
+    ps = []
+    gen = torch.Generator()
+    for i, (_, p) in enumerate(model.named_parameters()):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+            gen.manual_seed(seed * 100003 + i)
+            flat = flat[torch.randint(0, flat.numel(), (DUMP_SAMPLE_PER_TENSOR,), generator=gen).to(flat.device)]
+        ps.append(flat.float())
+    arrays = {"loss": np.array([loss_val], dtype=np.float32), "params_sample": torch.cat(ps).cpu().numpy(),
+              "grad_norms": gn.cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def measure_gemm_traffic(args, timeout_s=240):
     """roofline.traffic, measured in THIS run: two child runs of this script (2 timed steps, every secondary leg off, same precision /
     size) under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` and `... --pmc WRITE_SIZE` -- separate passes, as the counters do not fit one
@@ -352,7 +417,17 @@ def main():
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="exercise ONLY the N-rank launch path (self re-exec under torch.distributed.run, rendezvous, one "
                          "all-reduce on the gloo backend, rank 0 prints a JSON line) -- no GPU, no model; tests/test_bench_launch.py")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements and checks (kernel roofline + PMC traffic, "
+                         "grad_rel_err, trajectory, fast mode, uint8 input leg, data-parallel policy leg, exchange diagnostics, CPU "
+                         "baseline; each can still be turned off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, replay the timed step once from the state the timed steps started from and write what "
+                         "it computed as DIR/<name>.npy (rank 0): the loss, a fixed sample of the updated parameters, the "
+                         "per-parameter gradient norms")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # ---- N ranks: one process per GPU (reference: run/train_egoclip.py:39-45,128-134 / README.md:78-84).  Invoked bare
     # (`python bench.py --gpus N`, no WORLD_SIZE in the environment) this process is only the LAUNCHER: it re-executes
@@ -473,25 +548,30 @@ def main():
         hp = torch.cuda.Stream(priority=-1)
         hp.wait_stream(torch.cuda.current_stream())
         torch.cuda.set_stream(hp)          # everything below (timed steps, instrumented passes) runs on the high-priority stream
+    # --dump-outputs: every step starts from the weights, AdamW moments and loss scale the one before left, and the backward sums
+    # with atomics in an order that differs from run to run, so the state the LAST timed step starts from differs between runs.
+    # The dump therefore replays the timed step from the state saved here -- the same inputs in every run.
+    saved_state = save_train_state(model) if args.dump_outputs else None
     dt, loss_val = measure(args.steps, args.warmup)
-    # what ONE step costs the host when nothing pushes back: enqueue a step onto idle streams (3 repetitions, minimum).  The
-    # steady-state figure above (time until the host has enqueued `steps` steps) also contains the waits for space in the
-    # hardware queues once the host is a full step ahead of the GPU -- back-pressure, not work.
-    idle = []
-    for _ in range(3):
+    if args.full:
+        # what ONE step costs the host when nothing pushes back: enqueue a step onto idle streams (3 repetitions, minimum).  The
+        # steady-state figure above (time until the host has enqueued `steps` steps) also contains the waits for space in the
+        # hardware queues once the host is a full step ahead of the GPU -- back-pressure, not work.
+        idle = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0_ = time.perf_counter()
+            one_step()
+            idle.append((time.perf_counter() - t0_) * 1e3)
         torch.cuda.synchronize()
-        t0_ = time.perf_counter()
-        one_step()
-        idle.append((time.perf_counter() - t0_) * 1e3)
-    torch.cuda.synchronize()
-    HOST["enqueue_idle_ms"] = min(idle)
+        HOST["enqueue_idle_ms"] = min(idle)
     ms = dt / args.steps * 1e3
     pairs = world * B * args.steps / dt
 
     # ---- dominant-kernel roofline: the bf16-MFMA GEMM.  HIP events bracket every egv_gemm_nt launch on the stream
     # the kernels run on, in a separate instrumented pass of the same step (so the timed value above is untouched).
     roof = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         timer = ops.KernelTimer()
         # per-launch durations: one kernel at a time (no side streams) while the timer is attached
         ec.set(kernel_timer=timer, wgrad_side_stream=False, text_side_stream=False)
@@ -597,7 +677,7 @@ def main():
         "hbm_reserved_gb": round(torch.cuda.memory_reserved() / 2 ** 30, 1),
         "alloc_retries": int(torch.cuda.memory_stats().get("num_alloc_retries", 0)),
         "host_enqueue_ms_per_step": round(HOST.get("enqueue_ms_per_step", 0.0), 3),
-        "host_enqueue_ms_from_idle_streams": round(HOST.get("enqueue_idle_ms", 0.0), 3),
+        "host_enqueue_ms_from_idle_streams": round(HOST["enqueue_idle_ms"], 3) if "enqueue_idle_ms" in HOST else None,
         "host_flow_control_wait_ms_per_step": round(HOST.get("flow_wait_ms_per_step", 0.0), 3),
         "host_enqueue_ms_per_step_unthrottled": round(HOST.get("enqueue_ms_unthrottled", 0.0), 3),
         "host_lead_ms_at_last_enqueue": round(HOST.get("lead_ms", 0.0), 1),
@@ -611,10 +691,10 @@ def main():
         out["precision_guard"] = {"what": "video embedding of this batch in the policy in force vs the all-bf16x3 forward, measured on the device before the "
                                           "timed steps (egovlp_amd/guard.py); over budget -> the policy is demoted, logged, and the line reports it",
                                   **guard_report}
-    if args.precision != "bf16x3" and not args.no_grad_err:
+    if args.full and args.precision != "bf16x3" and not args.no_grad_err:
         out["grad_rel_err"] = grad_rel_err(model, loss_fn, data, world, rank, set_precision, args.precision)
     # ---- exchange diagnostics (N > 1): what the step spends in the collectives that backward does not hide
-    if use_dist:
+    if args.full and use_dist:
         import egovlp_amd.dist as egd
         egd.COMM_EVENTS = []
         nrep = 3
@@ -645,10 +725,10 @@ def main():
                        "note": "HIP events on the compute stream; grad_sync_exposed = wait for the bucket all-reduces that "
                                "backward did not hide + unpack; ms_per_step_rank_* are each rank's own untimed-barrier clock"}
     # ---- and over a TRAJECTORY: 20 optimisation steps at B = 8 in this mode vs the fp32-grade backward, same init, same batches
-    if args.precision in ("mixed", "f16x2", "f16mix") and not args.no_trajectory and world == 1 and (T, args.arch) == (4, "base_patch16_224"):
+    if args.full and args.precision in ("mixed", "f16x2", "f16mix") and not args.no_trajectory and world == 1 and (T, args.arch) == (4, "base_patch16_224"):
         out["trajectory"] = trajectory_drift(model, loss_fn, lambda ps: AdamW(ps, lr=3e-5), modes=("bf16x3", args.precision))
         opt = AdamW(model.parameters(), lr=3e-5)        # fresh optimizer state for the legs below (weights were restored)
-    if args.precision != "bf16" and not args.no_fast_mode:
+    if args.full and args.precision != "bf16" and not args.no_fast_mode:
         # secondary line: the same step with single-pass bf16 operands everywhere (embeddings ~6e-3 from fp32:
         # outside the parity bar, reported for reference only -- `value` above is the parity-mode number)
         set_precision("bf16")
@@ -658,7 +738,7 @@ def main():
                                  "step_mfma_frac": None if key not in FWD_GFLOP_PER_PAIR else round(
                                      B * args.steps / dt2 * FWD_GFLOP_PER_PAIR[key] * 3e9 / (PEAK_BF16_TFLOPS * 1e12), 4)}
         set_precision(args.precision)
-    if world == 1 and not args.no_h2d_leg:
+    if args.full and world == 1 and not args.no_h2d_leg:
         # secondary, clearly labelled figure: the step WITH the input hand-over the reference's step has (trainer/trainer_egoclip.py:
         # 114-121 moves every batch to the device before the step).  Decoded uint8 frames in pinned host memory (the loader's
         # output format; x / 255 and Normalize run inside the patch gather on the device), copied on a private copy stream one
@@ -691,7 +771,7 @@ def main():
                                                             + 4 * (batch["noun_vec"].numel() + batch["verb_vec"].numel())),
                                  "input": "decoded uint8 frames + token ids / masks / noun-verb vectors in pinned host memory, copied one "
                                           "batch ahead on a copy stream; normalisation fused into the patch gather", "loss": round(float(lossh), 5)}
-    if world == 1 and not use_dist and not args.no_dp_leg:
+    if args.full and world == 1 and not use_dist and not args.no_dp_leg:
         # secondary, clearly labelled: the step exactly as `world > 1` configures it -- RCCL process group, fused embedding
         # all-gather, hook-free bf16 gradient exchange (`--grad-exchange`) launched from the backward polls, ONE wgrad side stream, the
         # GEMM grid capped at 248 workgroups -- on the one GPU there is: what the data-parallel machinery costs before any byte crosses
@@ -764,8 +844,18 @@ def main():
                 out["roofline"]["traffic_over_algorithmic"] = round(tr["hbm_bytes_per_launch"] / alg, 2)
         else:
             out["roofline"]["traffic_missing_because"] = why
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
+    if saved_state is not None:
+        restore_train_state(model, saved_state)
+        opt = AdamW(model.parameters(), lr=3e-5)         # the optimizer's state when the timed steps started
+        scaler = ec.loss_scaler() if ec.bwd_passes == 4 else None
+        replay_loss = float(one_step())                   # every rank: the step's collectives
+        barrier()
+        if scaler is not None and scaler.skipped_steps() != int(saved_state["scaler"][3]):
+            raise SystemExit("bench.py: --dump-outputs: the replayed step overflowed the fp16 loss scale and was skipped")
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, replay_loss)
     _libc.fflush(None)        # anything native code buffered on stdout (RCCL's banner at N > 1) goes out BEFORE the line
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -1,12 +1,13 @@
-"""Runs INSIDE a subprocess of tests/test_boundary_cpu.py, only where /root/reference exists (the build container): imports
-the REAL reference (oracle/ref_import.py stub recipe) and
+"""Generates the fixtures of tests/test_boundary_cpu.py by running the REAL reference (oracle/ref_import.py stub recipe; needs a
+reference checkout, EGOVLP_REFERENCE): python tests/ref_boundary_probe.py <out_dir>, then copy ref_boundary.json,
+egoclip_config.json and ref_inflate.npz from <out_dir> into tests/golden/.  It
   1. builds the reference's own `parse_config.ConfigParser` on `configs/pt/egoclip.json` UNCHANGED, exactly as
-     run/train_egoclip.py:142-165 does, and lets it instantiate the drop-in classes by reflection (:63,69,73);
-  2. writes a checkpoint in the reference's format -- `module.`-prefixed state_dict + the live ConfigParser object
-     (base/base_trainer.py:407-414) -- for the parent test to load WITHOUT a parse_config module;
+     run/train_egoclip.py:142-165 does, lets it instantiate the drop-in classes by reflection (:63,69,73) and records what came
+     out (ref_boundary.json) and the configuration it parsed (egoclip_config.json);
+  2. records the attributes, with their types, of the live ConfigParser object that the reference pickles into every
+     checkpoint (base/base_trainer.py:407-414), so that the test can write a checkpoint of that format itself;
   3. runs the reference's own `_inflate_positional_embeds` (model/model.py:145-187) on temporal embeddings of 16 -> 4 and
-     4 -> 16 frames and saves the results.
-Prints one JSON line.  usage: python tests/ref_boundary_probe.py <out_dir>"""
+     4 -> 16 frames and saves the results (ref_inflate.npz)."""
 import argparse
 import collections
 import json
@@ -59,12 +60,11 @@ res = {"model": type(model).__name__, "keys": len(sd), "params_M": sum(v.numel()
        "time_init_zero": bool((model.video_model.blocks[0].timeattn.qkv.weight == 0).all()
                               and (model.video_model.blocks[0].timeattn.proj.weight == 1).all())}
 
-# 2. a reference-format checkpoint: DDP 'module.' prefix + the live ConfigParser (what _save_checkpoint pickles)
-from egovlp_amd.synth import synth_state_dict  # noqa: E402
-vals = synth_state_dict({k: v.shape for k, v in sd.items()}, seed=21)
-state = {'arch': 'FrozenInTime', 'epoch': 3, 'state_dict': collections.OrderedDict(('module.' + k, v) for k, v in vals.items()),
-         'optimizer': {'state': {}, 'param_groups': []}, 'monitor_best': 0.5, 'config': config}
-torch.save(state, os.path.join(out_dir, "ref_format_checkpoint.pth"))
+# 2. what _save_checkpoint pickles next to the `module.`-prefixed state_dict: the live ConfigParser, attribute by attribute
+res["config_class"] = type(config).__module__ + "." + type(config).__qualname__
+res["config_attrs"] = {k: type(v).__module__ + "." + type(v).__qualname__ for k, v in sorted(vars(config).items())}
+with open(os.path.join(out_dir, "egoclip_config.json"), "w") as f:
+    json.dump(config.config, f, indent=1)
 
 # 3. the reference's own temporal-embedding inflation
 out = {}
@@ -80,4 +80,5 @@ for load_frames, curr_frames, fix in [(16, 4, 'zeros'), (4, 16, 'zeros'), (4, 16
     out[f"in_{load_frames}_{curr_frames}_{fix}"] = te_.numpy()
     out[f"out_{load_frames}_{curr_frames}_{fix}"] = new['video_model.temporal_embed'].numpy()
 np.savez(os.path.join(out_dir, "ref_inflate.npz"), **out)
-print("PROBE " + json.dumps(res))
+with open(os.path.join(out_dir, "ref_boundary.json"), "w") as f:
+    json.dump(res, f, indent=1, sort_keys=True)

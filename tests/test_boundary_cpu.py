@@ -1,15 +1,17 @@
 """The drop-in boundary on the CPU (no GPU needed: modules are parameter containers until `forward`).
 
-* the reference's own ConfigParser, fed `configs/pt/egoclip.json` UNCHANGED, instantiates FrozenInTime / EgoNCE / AdamW
-  from the drop-in modules by reflection, exactly as run/train_egoclip.py:63,69,73 do (327 keys, 180.93 M parameters);
+* `configs/pt/egoclip.json` UNCHANGED, passed through a restatement of the reference's ConfigParser.initialize
+  (run/train_egoclip.py:63,69,73), instantiates FrozenInTime / EgoNCE / AdamW from the drop-in modules by reflection, and what
+  comes out equals what the reference's own ConfigParser built from the same file, recorded (327 keys, 180.93 M parameters);
 * a checkpoint in the reference's format (`module.` prefix, pickled ConfigParser) loads through
   `FrozenInTime(load_checkpoint=...)` with strict=True in a process that has no `parse_config` module;
 * `_inflate_positional_embeds` equals the reference's own method for 16 -> 4 and 4 -> 16 frames.
-The reference-dependent halves run in a subprocess (tests/ref_boundary_probe.py) and are skipped where /root/reference is
-absent (the GPU box); the rest runs everywhere."""
+What the reference itself does here is recorded under tests/golden/ (egoclip_config.json, ref_boundary.json, ref_inflate.npz,
+written by tests/ref_boundary_probe.py on a reference checkout), so every test runs without one."""
+import collections
+import inspect
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,27 +19,49 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("EGOVLP_REFERENCE", "/root/reference")
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "model")), reason="reference checkout not present")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 VIDEO_PARAMS = {"model": "SpaceTimeTransformer", "arch_config": "base_patch16_224", "num_frames": 16, "pretrained": True,
                 "time_init": "zeros"}
 TEXT_PARAMS = {"model": "distilbert-base-uncased", "pretrained": True, "input": "text"}
 
 
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("probe")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ref_boundary_probe.py"), str(out)],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    line = [l for l in r.stdout.splitlines() if l.startswith("PROBE ")][-1]
-    return json.loads(line[6:]), out
+def _golden_json(name):
+    with open(os.path.join(GOLDEN, name)) as f:
+        return json.load(f, object_pairs_hook=collections.OrderedDict)
 
 
-@needs_ref
-def test_reference_configparser_builds_the_dropin_classes_from_egoclip_json(probe):
-    res, _ = probe
+def _initialize(config, name, module, *args):
+    """What the reference's ConfigParser.initialize does for a section without an index: the class that the section's 'type'
+    names, called with the section's 'args' as keyword arguments plus every other constructor parameter that is a top-level
+    key of the configuration."""
+    cls = getattr(module, config[name]["type"])
+    kwargs = dict(config[name]["args"])
+    for p in inspect.signature(cls.__init__).parameters:
+        if p not in kwargs and p in config:
+            kwargs[p] = config[p]
+    return cls(*args, **kwargs)
+
+
+def test_initialize_restatement_builds_the_dropin_classes_as_the_reference_configparser_did():
+    import egovlp_amd.model.loss as module_loss
+    import egovlp_amd.model.model as module_arch
+    import egovlp_amd.optim as module_optim
+    config = _golden_json("egoclip_config.json")
+    model = _initialize(config, "arch", module_arch)                                      # run/train_egoclip.py:63
+    loss = _initialize(config, "loss", module_loss)                                       # :69
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    optimizer = _initialize(config, "optimizer", module_optim, trainable)                 # :73
+    sd = model.state_dict()
+    res = {"model": type(model).__name__, "keys": len(sd), "params_M": sum(v.numel() for v in sd.values()) / 1e6,
+           "loss": type(loss).__name__, "loss_temperature": loss.temperature, "optimizer": type(optimizer).__name__,
+           "lr": optimizer.param_groups[0]["lr"], "eps": optimizer.param_groups[0]["eps"],
+           "betas": list(optimizer.param_groups[0]["betas"]), "weight_decay": optimizer.param_groups[0]["weight_decay"],
+           "n_trainable": len(trainable), "model_frames": model.video_params["num_frames"],
+           "time_init_zero": bool((model.video_model.blocks[0].timeattn.qkv.weight == 0).all()
+                                  and (model.video_model.blocks[0].timeattn.proj.weight == 1).all())}
+    ref = _golden_json("ref_boundary.json")          # what the reference's own ConfigParser built from the same file
+    assert res == {k: ref[k] for k in res}
     assert res["model"] == "FrozenInTime" and res["keys"] == 327 and abs(res["params_M"] - 180.93) < 0.01
     assert res["n_trainable"] == 327 and res["model_frames"] == 16 and res["time_init_zero"]
     assert res["loss"] == "EgoNCE" and res["loss_temperature"] == 0.05
@@ -46,27 +70,53 @@ def test_reference_configparser_builds_the_dropin_classes_from_egoclip_json(prob
     assert res["betas"] == [0.9, 0.999] and res["weight_decay"] == 0.0
 
 
-@needs_ref
-def test_reference_format_checkpoint_loads_strict_without_parse_config(probe):
+def test_reference_format_checkpoint_loads_strict_without_parse_config(tmp_path):
+    """The reference's checkpoint (base/base_trainer.py:407-414): `module.`-prefixed state_dict and, under 'config', the pickled
+    parse_config.ConfigParser with the attributes -- of the types -- that the reference's live object has (ref_boundary.json)."""
+    import argparse
+    import logging
+    import pathlib
+    import types
     from egovlp_amd.model.model import FrozenInTime
     from egovlp_amd.synth import synth_state_dict
-    _, out = probe
-    assert "parse_config" not in sys.modules
-    path = os.path.join(str(out), "ref_format_checkpoint.pth")
+    ref = _golden_json("ref_boundary.json")
+    config = _golden_json("egoclip_config.json")
+    mod_name, cls_name = ref["config_class"].rsplit(".", 1)
+    assert mod_name not in sys.modules
+    by_type = {"collections.OrderedDict": config, "pathlib.PosixPath": pathlib.PosixPath("results/EgoClip_4f/models"),
+               "argparse.Namespace": argparse.Namespace(config="configs/pt/egoclip.json", resume=None, device=None, local_rank=0,
+                                                        world_size=1, rank=0, learning_rate1=2e-4, schedule=[60, 80], lr=None,
+                                                        bs=None),
+               "builtins.dict": {0: logging.WARNING, 1: logging.INFO, 2: logging.DEBUG}, "builtins.NoneType": None}
+    cls = type(cls_name, (), {"__module__": mod_name, "__qualname__": cls_name})   # pickled by reference (module + qualname)
+    cfg = cls()
+    for k, t in ref["config_attrs"].items():
+        setattr(cfg, k, by_type[t])
+    shapes = {k: v.shape for k, v in FrozenInTime(video_params=dict(VIDEO_PARAMS), text_params=dict(TEXT_PARAMS),
+                                                  projection="minimal", load_checkpoint="").state_dict().items()}
+    vals = synth_state_dict(shapes, seed=21)
+    state = {"arch": "FrozenInTime", "epoch": 3, "state_dict": collections.OrderedDict(("module." + k, v) for k, v in vals.items()),
+             "optimizer": {"state": {}, "param_groups": []}, "monitor_best": 0.5, "config": cfg}
+    path = str(tmp_path / "ref_format_checkpoint.pth")
+    mod = types.ModuleType(mod_name)
+    setattr(mod, cls_name, cls)
+    sys.modules[mod_name] = mod
+    try:
+        torch.save(state, path)
+    finally:
+        del sys.modules[mod_name]
     with pytest.raises(Exception):                  # what a plain torch.load does with this file (ADVICE r1)
         torch.load(path, map_location="cpu")
     m = FrozenInTime(video_params=dict(VIDEO_PARAMS), text_params=dict(TEXT_PARAMS), projection="minimal",
                      load_checkpoint=path)
-    want = synth_state_dict({k: v.shape for k, v in m.state_dict().items()}, seed=21)
+    assert mod_name not in sys.modules
     for k, v in m.state_dict().items():
-        assert torch.equal(v, want[k]), k
+        assert torch.equal(v, vals[k]), k
 
 
-@needs_ref
-def test_inflate_positional_embeds_matches_the_reference(probe):
+def test_inflate_positional_embeds_matches_the_reference():
     from egovlp_amd.model.model import FrozenInTime
-    _, out = probe
-    g = np.load(os.path.join(str(out), "ref_inflate.npz"))
+    g = np.load(os.path.join(GOLDEN, "ref_inflate.npz"))
     for load_frames, curr_frames, fix in [(16, 4, "zeros"), (4, 16, "zeros"), (4, 16, "bilinear")]:
         m = FrozenInTime(video_params={**VIDEO_PARAMS, "num_frames": curr_frames}, text_params=dict(TEXT_PARAMS),
                          projection="minimal", load_checkpoint="", load_temporal_fix=fix)

@@ -34,7 +34,7 @@ def _run(cmd, env):
 @pytest.mark.parametrize("exchange", ["bf16sync", "bf16sync-allreduce"])
 def test_bench_under_rccl_world1_matches_single_process(exchange):
     common = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--no-fast-mode",
-              "--no-kernel-timing", "--precision", "bf16x3"]
+              "--no-kernel-timing", "--precision", "bf16x3", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     plain = _run([sys.executable] + common, env)
     dist = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
