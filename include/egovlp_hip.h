@@ -404,6 +404,32 @@ int egv_cross_entropy_fwd_bwd(const float* logits, int64_t ld, const int64_t* ta
  *   y = softmax(x / temp, dim 1) * x;  out = softmax(y, dim 0).  work: n*m floats.  temp = 500 in the reference.        */
 int egv_dual_softmax(const float* x, int32_t n, int32_t m, float temp, float* work, float* out, void* stream);
 
+/* ---- retrieval scoring (model/metric.py mir_metrics / map, utils/nDCG.py, utils/mAP.py) ---------------------
+ * Per query row i of a similarity matrix S (fp32) and a relevancy matrix R, both stored [n1, n2] row-major with leading
+ * dimensions lds / ldr (elements), the two scores of the row's ranking pi_i (S descending):
+ *   DCG_i = sum_p R[i, pi_i(p)] * [p < K_i] / log2(p + 2),            K_i = #{j : R[i, j] > 0}          (calculate_DCG + calculate_k_counts)
+ *   AP_i  = (1 / n_i) sum_{p : R[i, pi_i(p)] == 1} c_i(p) / (p + 1),   c_i(p) = sum_{q <= p} R[i, pi_i(q)], n_i = #{j : R[i, j] == 1}
+ * c_i(p) is the running sum of the relevancies, as calculate_mAP's cumsum takes it: the number of positives up to p when R is
+ * binary (model/metric.py map).  n_i == 0 gives NaN (0 / 0), as the reference.
+ *   transposed == 0: the queries are the n1 rows; dcg_out / ap_out hold n1 doubles (either may be NULL, not both).
+ *   transposed == 1: the queries are the n2 columns (S^T scored against R^T); the outputs hold n2 doubles, and `work`
+ *     (egv_rank_scores_work_bytes(n1, n2) bytes, 8-byte aligned; unused and may be NULL otherwise) receives the transposed copies.
+ *     Nothing goes to the host in either direction.
+ *   S == NULL: the ideal ranking, S := R (calculate_IDCG) -- the row is ordered by its relevancies in R's own precision.
+ *   affine_half != 0: the ranking is that of (s + 1) / 2 evaluated in fp32 (mir_metrics), ties it creates included.
+ * TIE RULE: equal similarities (-0 == +0) are ranked by ascending column index (of the query's row, i.e. ascending row index of
+ *   S when transposed).  NaN similarities are not supported.
+ * LIMIT: the query row length (n2, or n1 when transposed) is at most EGV_RANK_MAX_ROW; the number of queries is unlimited.
+ *   A longer row returns 1 and launches nothing, as every invalid argument does.
+ * RELEVANCY PRECISION: r_is_f64 != 0: R is double, else float.  The tests `> 0` and `== 1` and the sums run on the value
+ *   converted to double, so a caller that hands over fp32 must make sure that the conversion from its fp64 original was exact
+ *   (0, 1, dyadic fractions) -- otherwise pass the fp64 matrix.
+ * All sums, the discount and the divisions are fp64; fixed summation order, no atomics (bitwise reproducible).            */
+#define EGV_RANK_MAX_ROW 16384
+int egv_rank_scores(const float* S, int64_t lds, int32_t transposed, const void* R, int32_t r_is_f64, int64_t ldr,
+                    int32_t n1, int32_t n2, int32_t affine_half, double* dcg_out, double* ap_out, void* work, void* stream);
+int64_t egv_rank_scores_work_bytes(int32_t n1, int32_t n2);
+
 /* ---- gradient exchange (data parallel) ------------------------------------------------------------------
  * Replaces the fp32 bucket copies of DistributedDataParallel (base/base_trainer.py:258): `count` fp32 gradient tensors
  * (HOST arrays of device pointers / sizes) are scaled by `scale` (= 1 / world size), rounded to bf16 (RNE) and written to
