@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the contrastive-head kernels (include/egovlp_hip.h: egv_sim_matrix_*,
-egv_egonce_from_sim, egv_egonce_fwd_bwd)."""
+egv_egonce_from_sim, egv_egonce_fwd_bwd, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd)."""
 import torch
 
 from . import _lib, ops
@@ -65,6 +65,40 @@ def maxmargin(x, weight, margin, fix_norm, want_grad=True):
     check(_lib.lib().egv_maxmargin_fwd_bwd(_p(x), _p(w), n, float(margin), int(bool(fix_norm)), _p(loss), _p(dx), ops._stream()),
           "egv_maxmargin_fwd_bwd")
     return loss, dx
+
+
+MAXMARGIN_HEAD_MAX_N, MAXMARGIN_HEAD_MAX_D = 1024, 256
+
+
+def maxmargin_head_ok(n, D):
+    """The limits of egv_maxmargin_head_fwd_bwd (the EgoNCE head's): n <= 1024 rows of D <= 256 features, D % 4 == 0."""
+    return 0 < n <= MAXMARGIN_HEAD_MAX_N and 0 < D <= MAXMARGIN_HEAD_MAX_D and D % 4 == 0
+
+
+def maxmargin_head(text, video, weight, margin, fix_norm, eps=1e-8, want_sim=False):
+    """sim_matrix + MaxMarginRankingLoss (weight None) / AdaptiveMaxMarginRankingLoss + backward in one call, on the global batch
+    text, video [n, D] -> (loss[1], sim [n, n] or None, d_text, d_video).  Deterministic; nothing n x n is written unless
+    want_sim."""
+    ops._need_cuda(text, video, weight)
+    if text.dim() != 2 or video.dim() != 2 or text.shape != video.shape:
+        raise ValueError("maxmargin_head: text and video must both be [n, D]")
+    text = text.contiguous().float()
+    video = video.contiguous().float()
+    n, D = text.shape
+    w = None if weight is None else weight.contiguous().float()
+    if w is not None and w.numel() != n:
+        raise ValueError("weight must have one entry per row")
+    dev = text.device
+    wf = max(int(_lib.lib().egv_maxmargin_head_work_floats(n, D)), 1)
+    work = torch.empty(wf, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    sim = torch.empty((n, n), dtype=torch.float32, device=dev) if want_sim else None
+    dt = torch.empty_like(text)
+    dv = torch.empty_like(video)
+    check(_lib.lib().egv_maxmargin_head_fwd_bwd(_p(text), _p(video), _p(w), n, D, float(margin), int(bool(fix_norm)), float(eps),
+                                                _p(loss), _p(sim), _p(dt), _p(dv), _p(work), ops._stream(text)),
+          "egv_maxmargin_head_fwd_bwd")
+    return loss, sim, dt, dv
 
 
 def dual_softmax(x, temp=500.0):

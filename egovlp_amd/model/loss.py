@@ -6,7 +6,8 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip):
   * the fused hot path  `loss.fused(text, video, noun, verb)`: ONE call computes the three similarity
     matrices, the mask, the loss and the gradients w.r.t. both embeddings (egv_egonce_fwd_bwd).
 MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EPIC-MIR / Charades fine-tuning heads over the
-same similarity matrix, run on egv_maxmargin_fwd_bwd.  CrossEntropy (:135-141), the loss of the OSCC / PNR
+same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
+of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR
 classification fine-tunes on the [B, classes] scores of FrozenInTime(video_only=True) (trainer/trainer_oscc.py:335-338), runs on
 egv_cross_entropy_fwd_bwd.
 """
@@ -87,6 +88,19 @@ class _MaxMarginFn(torch.autograd.Function):
         return dx * g, None, None, None
 
 
+class _FusedMaxMarginFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, text, video, weight, margin, fix_norm):
+        loss, _, dt, dv = loss_ops.maxmargin_head(text, video, weight, margin, fix_norm)
+        ctx.save_for_backward(dt, dv)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dt, dv = ctx.saved_tensors
+        return dt * g, dv * g, None, None, None
+
+
 class MaxMarginRankingLoss(nn.Module):
     """model/loss.py:55-90 (same constructor; `weight` is accepted and ignored, as in the reference)."""
 
@@ -97,6 +111,10 @@ class MaxMarginRankingLoss(nn.Module):
 
     def forward(self, x, weight=None):
         return _MaxMarginFn.apply(x, None, self.margin, self.fix_norm)
+
+    def fused(self, text_embeds, video_embeds, weight=None):
+        "loss(sim_matrix(text_embeds, video_embeds)) in one call (`weight` ignored, as in forward)"
+        return _FusedMaxMarginFn.apply(text_embeds, video_embeds, None, self.margin, self.fix_norm)
 
 
 class AdaptiveMaxMarginRankingLoss(nn.Module):
@@ -111,6 +129,12 @@ class AdaptiveMaxMarginRankingLoss(nn.Module):
         if weight is None:
             raise TypeError("AdaptiveMaxMarginRankingLoss needs the per-row weight (model/loss.py:109)")
         return _MaxMarginFn.apply(x, weight, self.margin, self.fix_norm)
+
+    def fused(self, text_embeds, video_embeds, weight=None):
+        "loss(sim_matrix(text_embeds, video_embeds), weight) in one call"
+        if weight is None:
+            raise TypeError("AdaptiveMaxMarginRankingLoss needs the per-row weight (model/loss.py:109)")
+        return _FusedMaxMarginFn.apply(text_embeds, video_embeds, weight, self.margin, self.fix_norm)
 
 
 class _CrossEntropyFn(torch.autograd.Function):

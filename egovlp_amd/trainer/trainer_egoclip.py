@@ -78,6 +78,29 @@ class AllGatherFused(torch.autograd.Function):
         return gv[lo:hi], gt[lo:hi], None, None, None, None
 
 
+class AllGatherRows(torch.autograd.Function):
+    """`AllGatherRows.apply(world_size, rank, *tensors)`: row-aligned [B, ...] tensors -> their global-batch versions with ONE
+    collective (packed as columns of one fp32 row block, like AllGatherFused).  Backward hands every input the LOCAL rows of
+    its gradient (inputs that do not require one, e.g. per-row loss weights, are ignored by autograd)."""
+
+    @staticmethod
+    def forward(ctx, world_size, rank, *tensors):
+        ctx.rank, ctx.B = rank, tensors[0].shape[0]
+        if world_size == 1 and os.environ.get("EGV_FORCE_GATHER") != "1":
+            return tensors if len(tensors) > 1 else tensors[0]
+        dtype = tensors[0].dtype
+        flat = [t.reshape(ctx.B, -1).to(dtype) for t in tensors]
+        allp = _gather_rows(torch.cat(flat, dim=1), world_size)
+        parts = torch.split(allp, [f.shape[1] for f in flat], dim=1)
+        out = tuple(p.contiguous().reshape((allp.shape[0],) + tuple(t.shape[1:])).to(t.dtype) for p, t in zip(parts, tensors))
+        return out if len(out) > 1 else out[0]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        lo, hi = ctx.B * ctx.rank, ctx.B * (ctx.rank + 1)
+        return (None, None) + tuple(None if g is None else g[lo:hi] for g in grads)
+
+
 def egoclip_step(model, loss_fn, optimizer, data, world_size=1, rank=0, fused_head=True, grad_sync=None, scaler=None):
     """One optimisation step = trainer/trainer_egoclip.py:123-141 (zero_grad, forward, gathers,
     similarity + loss, backward, optimizer.step).  Returns the (device) loss tensor; no host sync.

@@ -391,6 +391,20 @@ int egv_egonce_from_sim(const float* x, const float* sim_v, const float* sim_n, 
 int egv_maxmargin_fwd_bwd(const float* x, const float* weight, int32_t n, float margin, int32_t fix_norm,
                           float* loss, float* dx, void* stream);
 
+/* The ranking-loss head in one call: sim_matrix (model/model.py:189-197) + MaxMarginRankingLoss / AdaptiveMaxMarginRankingLoss
+ * (model/loss.py:55-133) + the backward of both, for the all-gathered global batch text, video [n, D] fp32:
+ *   x_ij = <t_i / max(|t_i|, eps), v_j / max(|v_j|, eps)>,  loss as egv_maxmargin_fwd_bwd on x (weight [n] or NULL, fix_norm),
+ *   d_text, d_video [n, D] (optional) = d loss / d text, d video through the normalisation, eps clamp included;
+ *   sim [n, n] (optional) receives x -- no n x n array is written otherwise.
+ * Deterministic: no floating-point atomics, fixed summation orders; two calls on the same input give identical bits.
+ * n <= 1024, D <= 256, D % 4 == 0 (and n >= 2 with fix_norm), else EGV_ERR_ARG before any launch.  work:
+ * egv_maxmargin_head_work_floats(n, D) floats; work, d_text and d_video 16-byte aligned.                                  */
+int egv_maxmargin_head_fwd_bwd(const float* text, const float* video, const float* weight /* [n] or NULL */,
+                               int32_t n, int32_t D, float margin, int32_t fix_norm, float eps,
+                               float* loss, float* sim /* optional [n,n] */, float* d_text, float* d_video /* optional */,
+                               float* work, void* stream);
+int64_t egv_maxmargin_head_work_floats(int32_t n, int32_t D);
+
 /* Softmax cross-entropy of the classification fine-tunes (OSCC / PNR heads): model/loss.py:135-141 (nn.CrossEntropyLoss with its
  * defaults) on the [rows, cols] scores of FrozenInTime(video_only=True) (trainer/trainer_oscc.py:335-338).
  *   loss = mean over rows with target != ignore_index of (logsumexp(x_r) - x_r[target_r]);  NaN when no row is valid (as torch);
