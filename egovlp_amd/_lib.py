@@ -117,6 +117,9 @@ PROTOTYPES = {
     "egv_maxmargin_fwd_bwd": (i32, [c_p, c_p, i32, f32, i32, c_p, c_p, c_p]),
     "egv_maxmargin_head_fwd_bwd": (i32, [c_p, c_p, c_p, i32, i32, f32, i32, f32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_maxmargin_head_work_floats": (i64, [i32, i32]),
+    "egv_cls_head_fwd": (i32, [c_p, i64, c_p, c_p, i32, i32, i32, c_p, i64, c_p]),
+    "egv_cls_head_loss_bwd": (i32, [c_p, i64, i32, i32, i32, i32, i32, i32, c_p, i64, c_p, i32, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p]),
+    "egv_cls_eval_update": (i32, [c_p, i64, i32, i32, i32, i32, i32, i32, i32, i32, c_p, c_p]),
     "egv_dual_softmax": (i32, [c_p, i32, i32, f32, c_p, c_p, c_p]),
     "egv_rank_scores": (i32, [c_p, i64, i32, c_p, i32, i64, i32, i32, i32, c_p, c_p, c_p, c_p]),
     "egv_rank_scores_work_bytes": (i64, [i32, i32]),

@@ -1,5 +1,6 @@
 """Tensor-level wrappers of the contrastive-head kernels (include/egovlp_hip.h: egv_sim_matrix_*,
-egv_egonce_from_sim, egv_egonce_fwd_bwd, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd)."""
+egv_egonce_from_sim, egv_egonce_fwd_bwd, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
+the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
 import torch
 
 from . import _lib, ops
@@ -128,3 +129,123 @@ def cross_entropy(logits, target, ignore_index=-100, want_grad=True):
     check(_lib.lib().egv_cross_entropy_fwd_bwd(_p(x), x.stride(0), _p(t), x.shape[0], x.shape[1], int(ignore_index), _p(loss),
                                                _p(dx), x.shape[1], ops._stream(x)), "egv_cross_entropy_fwd_bwd")
     return loss, dx
+
+
+CLS_MAX_N, CLS_MAX_B, CLS_MAX_K, CLS_MAX_C = 4096, 256, 1024, 64
+
+
+def cls_head_ok(n, B, K, C):
+    """The limits of egv_cls_head_fwd / egv_cls_head_loss_bwd: n <= 4096 gathered rows, B <= 256 local rows, K <= 1024 features with
+    K % 4 == 0, C <= 64 classes."""
+    return 0 < B <= CLS_MAX_B and B <= n <= CLS_MAX_N and 0 < K <= CLS_MAX_K and K % 4 == 0 and 0 < C <= CLS_MAX_C
+
+
+class ClsLayout:
+    """Columns of the fp32 row block that crosses the ranks in the classification fine-tunes: [0, C) the scores, then the class
+    index, then (PNR) the state, then (PNR validation) fps as two floats (hi + lo of the fp64 value), parent_start_frame,
+    parent_end_frame, parent_pnr_frame.  Integer columns are exact below 2^24."""
+
+    def __init__(self, C, task='oscc', evaluate=False):
+        if task not in ('oscc', 'pnr'):
+            raise ValueError("task is 'oscc' or 'pnr'")
+        self.C, self.task = C, task
+        self.target = C
+        self.state = C + 1 if task == 'pnr' else -1
+        self.fps = self.start = self.end = self.pnr = -1
+        self.ld = C + (2 if task == 'pnr' else 1)
+        if task == 'pnr' and evaluate:
+            self.fps, self.start, self.end, self.pnr = C + 2, C + 4, C + 5, C + 6
+            self.ld = C + 7
+
+    def fill(self, packed, target, state=None, fps=None, start=None, end=None, pnr=None):
+        """Write everything but the scores into packed [B, ld]."""
+        packed[:, self.target] = target
+        if self.state >= 0:
+            packed[:, self.state] = state
+        if self.fps >= 0:
+            f64 = fps.to(torch.float64)
+            hi = f64.to(torch.float32)
+            packed[:, self.fps] = hi
+            packed[:, self.fps + 1] = f64 - hi.to(torch.float64)
+            packed[:, self.start] = start
+            packed[:, self.end] = end
+            packed[:, self.pnr] = pnr
+        return packed
+
+
+def _rows_f32(x):
+    """[rows, K] fp32 with unit column stride, 16-byte aligned rows (a strided view such as the CLS rows is read in place)."""
+    x = x.float()
+    if x.dim() != 2:
+        raise ValueError("expected a [rows, K] matrix")
+    if x.stride(1) != 1 or x.stride(0) % 4 != 0 or x.stride(0) < x.shape[1] or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    return x
+
+
+def cls_head_fwd(feats, weight, bias, out=None):
+    """scores = feats W^T + b for feats [B, K], weight [C, K], bias [C] or None (egv_cls_head_fwd).  `out` [B, ld >= C] fp32:
+    the scores go to its first C columns (the block the collective sends) and `out` is returned; else a new [B, C]."""
+    ops._need_cuda(feats, weight)
+    x = _rows_f32(feats.detach())
+    w = weight.detach().float().contiguous()
+    b = None if bias is None else bias.detach().float().contiguous()
+    B, K = x.shape
+    C = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError("cls_head_fwd: feats [B, K] and weight [C, K]")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < C or out.stride(1) != 1:
+        raise ValueError("cls_head_fwd: out must be fp32 [B, >= C] with unit column stride")
+    check(_lib.lib().egv_cls_head_fwd(_p(x), x.stride(0), _p(w), _p(b), B, K, C, _p(out), out.stride(0), ops._stream(x)),
+          "egv_cls_head_fwd")
+    return out
+
+
+def cls_head_loss_bwd(packed, C, col_target, col_state=-1, row0=0, B=None, feats=None, weight=None, want_grad=True, want_pred=False):
+    """Loss (and backward) of the classification head on the gathered block packed [n, ld] (egv_cls_head_loss_bwd)
+    -> (loss[1], dW [C, K], db [C], dfeats [B, K], pred int32 [n]); entries not asked for are None.  feats [B, K]: the LOCAL rows
+    row0 .. row0 + B of the batch."""
+    ops._need_cuda(packed)
+    if packed.dim() != 2 or packed.dtype != torch.float32 or packed.stride(1) != 1:
+        raise ValueError("cls_head_loss_bwd: packed must be fp32 [n, ld] with unit column stride")
+    n = packed.shape[0]
+    dev = packed.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    work = torch.empty(n + 1, dtype=torch.float64, device=dev)
+    pred = torch.empty(n, dtype=torch.int32, device=dev) if want_pred else None
+    x = w = dW = db = dx = None
+    B = n if B is None else B
+    K = 4
+    if not want_grad:
+        row0, B = 0, 1                       # no local rows are read
+    else:
+        x = _rows_f32(feats.detach())
+        w = weight.detach().float().contiguous()
+        if x.shape[0] != B or w.shape != (C, x.shape[1]):
+            raise ValueError("cls_head_loss_bwd: feats [B, K] and weight [C, K]")
+        K = x.shape[1]
+        dW = torch.empty((C, K), dtype=torch.float32, device=dev)
+        db = torch.empty(C, dtype=torch.float32, device=dev)
+        dx = torch.empty((B, K), dtype=torch.float32, device=dev)
+    check(_lib.lib().egv_cls_head_loss_bwd(_p(packed), packed.stride(0), n, C, int(col_target), int(col_state), int(row0), B,
+                                           _p(x), 0 if x is None else x.stride(0), _p(w), K, _p(loss), _p(dW), _p(db), _p(dx), K,
+                                           _p(pred), _p(work), ops._stream(packed)), "egv_cls_head_loss_bwd")
+    return loss, dW, db, dx, pred
+
+
+def cls_eval_update(packed, layout, accum):
+    """Add the rows of a gathered validation block packed [n, layout.ld] to accum (float64 [4] on the device: hits, rows, sum of
+    err_sec, positives) -- egv_cls_eval_update.  Blocks of more than 4096 rows are fed in pieces."""
+    ops._need_cuda(packed, accum)
+    if packed.dim() != 2 or packed.dtype != torch.float32 or packed.stride(1) != 1 or packed.shape[1] < layout.ld:
+        raise ValueError("cls_eval_update: packed must be fp32 [n, >= layout.ld] with unit column stride")
+    if accum.dtype != torch.float64 or accum.numel() != 4 or not accum.is_contiguous():
+        raise ValueError("cls_eval_update: accum is a contiguous float64 [4]")
+    for lo in range(0, packed.shape[0], CLS_MAX_N):
+        part = packed[lo:lo + CLS_MAX_N]
+        check(_lib.lib().egv_cls_eval_update(_p(part), part.stride(0), part.shape[0], layout.C, layout.target, layout.state,
+                                             layout.fps, layout.start, layout.end, layout.pnr, _p(accum), ops._stream(packed)),
+              "egv_cls_eval_update")
+    return accum

@@ -9,7 +9,8 @@ MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EP
 same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
 of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR
 classification fine-tunes on the [B, classes] scores of FrozenInTime(video_only=True) (trainer/trainer_oscc.py:335-338), runs on
-egv_cross_entropy_fwd_bwd.
+egv_cross_entropy_fwd_bwd; its `fused(feats, weight, bias, target[, state])` is the whole head of those steps on ONE autograd
+node: the narrow projection (egv_cls_head_fwd), one packed collective, loss and backward (egv_cls_head_loss_bwd).
 """
 import torch
 from torch import nn
@@ -159,3 +160,37 @@ class CrossEntropy(nn.Module):
 
     def forward(self, output, target):
         return _CrossEntropyFn.apply(output, target)
+
+    def fused(self, feats, weight, bias, target, state=None, world_size=1, rank=0, ec=None):
+        """The classification head of the OSCC / PNR step in one node, from the video tower's features [B, K]:
+        scores = feats weight^T + bias, gathered over the ranks with target (and state) in one collective, then
+          state None:  CrossEntropy(scores, target)                       trainer/trainer_oscc.py:335-338
+          state [B]:   mean(state.T * CrossEntropy(scores, target))       trainer/trainer_pnr.py:345-350
+        and the local gradients w.r.t. feats, weight and bias (what AllGather_multi.backward leaves to this rank).
+        `ec`: the model's execution context (its backward poll runs first in backward, as in the projection node this replaces)."""
+        return _ClsHeadFn.apply(feats, weight, bias, target, state, world_size, rank, ec)[0]
+
+
+class _ClsHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, weight, bias, target, state, world, rank, ec=None):
+        from ..trainer import trainer_egoclip as T
+        B, C = feats.shape[0], weight.shape[0]
+        lay = loss_ops.ClsLayout(C, 'oscc' if state is None else 'pnr')
+        packed = torch.empty((B, lay.ld), dtype=torch.float32, device=feats.device)
+        loss_ops.cls_head_fwd(feats, weight, bias, out=packed)
+        lay.fill(packed, target, state)
+        allp = T._gather_rows(packed, world)                  # the ONE collective of the step; nothing is sent at world size 1
+        loss, dW, db, dx, _ = loss_ops.cls_head_loss_bwd(allp, C, lay.target, lay.state, row0=rank * B, B=B, feats=feats,
+                                                         weight=weight)
+        ctx.ec, ctx.has_bias = ec, bias is not None
+        ctx.save_for_backward(dx, dW, db)
+        ctx.mark_non_differentiable(allp)
+        return loss.reshape(()), allp
+
+    @staticmethod
+    def backward(ctx, g, _g_block):
+        dx, dW, db = ctx.saved_tensors
+        if ctx.ec is not None and not ctx.ec.on_text_stream():
+            ctx.ec.poll_backward()      # the first node of the video tower's backward on the main stream (as _ProjFn.backward)
+        return dx * g, dW * g, (db * g if ctx.has_bias else None), None, None, None, None, None

@@ -187,3 +187,36 @@ def oscc_metrics(preds, labels):
     preds, labels = torch.as_tensor(preds), torch.as_tensor(labels).reshape(-1)
     hit = preds.reshape(labels.shape[0], -1).argmax(dim=1) == labels.to(preds.device)
     return {"accuracy": float(hit.double().mean()) * 100}
+
+
+def pnr_metrics(preds, labels, sc_labels, fps, parent_start_frames, parent_end_frames, parent_pnr_frames):
+    """model/metric.py:355-397: mean distance in seconds between the predicted and the annotated point-of-no-return frame over the
+    clips with a state change (sc_label == 1).  The predicted frame is `(end - start) / 16 * argmax(pred)` in the tensors' own
+    arithmetic (fp32 for integer frame numbers; the 16 is the reference's literal), the error is taken in fp64 and divided by the
+    clip's fps.  NaN when no clip has a state change: the reference's `if len(distance_list) == 0` branch is overwritten by the
+    line after it (:393-394), so `np.mean([])` is what it returns.  `labels` is not read (as in the reference)."""
+    preds = torch.as_tensor(preds).detach().cpu()
+    n = preds.shape[0]
+    am = preds.reshape(n, -1).argmax(dim=1)
+
+    def col(t):
+        return torch.as_tensor(t).detach().cpu().reshape(-1)
+    sc, start, end, pnr, fps = col(sc_labels), col(parent_start_frames), col(parent_end_frames), col(parent_pnr_frames), col(fps)
+    mapped = ((end - start) / 16 * am).double()                                  # :381-382
+    err_sec = (mapped - (pnr - start).double()).abs() / fps.double()             # :383-385
+    sel = sc == 1
+    if not bool(sel.any()):
+        return {"keyframe_distance": float("nan")}
+    return {"keyframe_distance": float(np.mean(err_sec[sel].numpy()))}
+
+
+def oscc_metrics_from_counts(accum):
+    """oscc_metrics from the device accumulator of egv_cls_eval_update (hits, rows, -, -)."""
+    hits, rows = float(accum[0]), float(accum[1])
+    return {"accuracy": hits / rows * 100 if rows > 0 else float("nan")}      # no row seen: the reference divides by zero
+
+
+def pnr_metrics_from_counts(accum):
+    """pnr_metrics from the device accumulator of egv_cls_eval_update (-, rows, sum of err_sec, positives); NaN without positives."""
+    err, pos = float(accum[2]), float(accum[3])
+    return {"keyframe_distance": err / pos if pos > 0 else float("nan")}

@@ -112,6 +112,11 @@ class RetrievalTrainerBase(Multi_BaseTrainer_dist):
 
     _guard = None
 
+    def _step(self, data):
+        """The optimisation step of one device batch -> its (device) loss; the classification trainers put their own here."""
+        return retrieval_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank,
+                              fused_head=self.fused_head, grad_sync=self.grad_sync)
+
     def _train_epoch(self, epoch):
         self.model.train()
         total_loss = [torch.zeros((), device=self.device) for _ in self.data_loader]
@@ -127,8 +132,7 @@ class RetrievalTrainerBase(Multi_BaseTrainer_dist):
                 from ..guard import PrecisionGuard
                 self._guard = PrecisionGuard(self.model, interval=int(getattr(self.args, 'precision_guard_interval', 1000)))
             self._guard.maybe_check(data)
-            loss = retrieval_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank,
-                                  fused_head=self.fused_head, grad_sync=self.grad_sync)
+            loss = self._step(data)
             total_loss[dl_idx] += loss          # stays on the device: no per-step .item() sync (reference :141,143)
             if self.writer is not None and self.args.rank == 0 and batch_idx % self.log_step == 0:
                 total = int(self.data_loader[dl_idx].n_samples / self.n_gpu) if hasattr(self.data_loader[dl_idx], 'n_samples') else 0

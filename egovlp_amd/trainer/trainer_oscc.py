@@ -1,0 +1,168 @@
+"""Ego4D object-state-change classification (OSCC) fine-tuning -- drop-in for the reference's trainer/trainer_oscc.py -- and what
+it shares with the point-of-no-return trainer (trainer_pnr.py).
+
+`classification_step` is the optimisation step of both (trainer/trainer_oscc.py:330-341, trainer/trainer_pnr.py:331-354):
+zero_grad, video tower, the narrow head (vid_proj = Linear(768, 2 | 16 | 17)), gather over the ranks, CrossEntropy (PNR: times
+the mean of `state`, target = argmax of the one-hot `labels`, 0 for the all-zero rows of clips without a state change), backward,
+optimizer.step.  What differs from the reference: the head is ONE autograd node (`CrossEntropy.fused`: egv_cls_head_fwd, one packed
+collective instead of two or three, egv_cls_head_loss_bwd) where the padded-GEMM projection node + gathers + loss node took about
+fifteen launches for a [4, 768] x [768, 2] product.  `fused_head=False` (or a shape outside `cls_head_ok`) is that earlier route.
+
+`Multi_Trainer_dist_OSCC` keeps the reference's constructor and `train()` flow; constructor, batch feed, LR rule, precision guard
+and epoch loop are RetrievalTrainerBase's.  Validation (:382-467) runs on the device: one forward, one gathered block and one
+egv_cls_eval_update per batch, the rank-local validation loss (:428) summed there too (`monitor: "min val_loss_0"`).
+"""
+from __future__ import annotations
+
+import torch
+
+from .. import loss_ops
+from ..loss_ops import ClsLayout, cls_head_ok
+from .classification_eval import ClassificationEvaluator
+from .trainer_egoclip import AllGatherRows, _gather_rows, _world
+from .trainer_epic import RetrievalTrainerBase, format_nested_metrics_for_writer  # noqa: F401  (re-exported, as the reference file has it)
+
+
+def _targets(data, task, device):
+    """-> (target [B] int64, state [B] or None): OSCC classifies `state`; PNR localises argmax(labels) and weighs by `state`.
+    The argmax is taken locally: it commutes with the gather (trainer/trainer_pnr.py:346,350)."""
+    state = data['state'].to(device).reshape(-1)
+    if task == 'oscc':
+        return state.long(), None
+    if task != 'pnr':
+        raise ValueError("task is 'oscc' or 'pnr'")
+    return torch.argmax(data['labels'].to(device).long(), dim=1), state
+
+
+def _head(core):
+    lin = core.vid_proj[0] if isinstance(core.vid_proj, torch.nn.Sequential) else None
+    return lin if isinstance(lin, torch.nn.Linear) else None
+
+
+def classification_step(model, loss_fn, optimizer, data, world_size=1, rank=0, task='oscc', fused_head=True, grad_sync=None,
+                        scaler=None):
+    """One fine-tuning step on a batch {'video', 'state'[, 'labels']} already on the device.  Returns the (device) loss tensor; no
+    host sync.  `grad_sync` / `scaler`: as egoclip_step."""
+    core = getattr(model, 'module', model)
+    ec = getattr(core, 'exec_ctx', None)
+    if scaler is None and ec is not None and ec.bwd_passes == 4:
+        scaler = ec.loss_scaler(device=next(core.parameters()).device)
+    optimizer.zero_grad(set_to_none=True)                                       # trainer_oscc.py:333
+    video = data['video']
+    target, state = _targets(data, task, video.device)
+    lin, B = _head(core), video.shape[0]
+    if fused_head and hasattr(loss_fn, 'fused') and lin is not None and cls_head_ok(world_size * B, B, lin.in_features, lin.out_features):
+        ec.begin_step()
+        feats = core.video_model(video)                                         # model/model.py:114, without the projection
+        loss = loss_fn.fused(feats, lin.weight, lin.bias, target, state, world_size, rank, ec)   # :335-338 / pnr :341-350
+    else:
+        scores = model(data, video_only=True)                                   # :335
+        if state is None:
+            scores, target = AllGatherRows.apply(world_size, rank, scores, target)             # :336-337
+            loss = loss_fn(scores, target)                                      # :338
+        else:
+            scores, target, state = AllGatherRows.apply(world_size, rank, scores, target, state)   # pnr :345-347
+            loss = torch.mean(state * loss_fn(scores, target))                  # pnr :350
+    (loss if scaler is None else scaler.scale(loss)).backward()                 # :339
+    if ec is not None:
+        ec.join_side_stream()
+    if grad_sync is not None:
+        grad_sync.finish()
+    if scaler is None:
+        optimizer.step()                                                        # :341
+    else:
+        optimizer.step(scaler=scaler)
+    return loss.detach()
+
+
+class ClassificationTrainerBase(RetrievalTrainerBase):
+    """What the OSCC and PNR trainers share: the step, the host batch order without a tokenizer call (the reference's loops make
+    none: trainer_oscc.py:328-331) and the validation loop."""
+
+    task = 'oscc'
+    keep_val_blocks = False         # checks only: keep every gathered validation block in `last_val_blocks`
+
+    def _host_batches(self):
+        for batch_idx, data_li in enumerate(zip(*self.data_loader)):
+            if (batch_idx + 1) * self.total_batch_sum > self.max_samples_per_epoch:             # :326-327
+                break
+            for dl_idx, data in enumerate(data_li):
+                yield batch_idx, dl_idx, data
+            if batch_idx == self.len_epoch:                                                      # :361-362
+                break
+
+    def _step(self, data):
+        return classification_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank, task=self.task,
+                                   fused_head=self.fused_head, grad_sync=self.grad_sync)
+
+    def _val_columns(self, data):
+        """Everything of a validation batch that rides in the row block besides the scores (ClsLayout.fill's arguments)."""
+        target, state = _targets(data, self.task, self.device)
+        return {'target': target, 'state': state}
+
+    def _valid_epoch(self, epoch):
+        self.model.eval()
+        n_loaders = len(self.valid_data_loader)
+        evaluator = ClassificationEvaluator(self.metrics, n_loaders=n_loaders, keep_blocks=self.keep_val_blocks)
+        core = getattr(self.model, 'module', self.model)
+        lin, world = _head(core), _world()
+        with torch.no_grad():
+            for dl_idx, dl in enumerate(self.valid_data_loader):
+                for data in dl:
+                    video = data['video'].to(self.device)                                        # :403
+                    cols = self._val_columns(data)
+                    B = video.shape[0]
+                    C = lin.out_features if lin is not None else 0
+                    if lin is not None and cls_head_ok(world * B, B, lin.in_features, C):
+                        lay = ClsLayout(C, self.task, evaluate=True)
+                        block = torch.empty((B, lay.ld), dtype=torch.float32, device=self.device)
+                        core.exec_ctx.begin_step()
+                        loss_ops.cls_head_fwd(core.video_model(video), lin.weight, lin.bias, out=block)      # :406
+                        lay.fill(block, **cols)
+                        # the rank-local loss on the un-gathered batch (:428, pnr :473)
+                        loss = loss_ops.cls_head_loss_bwd(block, C, lay.target, lay.state, want_grad=False)[0]
+                    else:
+                        scores = self.model({'video': video}, video_only=True)
+                        C = scores.shape[1]
+                        lay = ClsLayout(C, self.task, evaluate=True)
+                        block = torch.empty((B, lay.ld), dtype=torch.float32, device=self.device)
+                        block[:, :C] = scores
+                        lay.fill(block, **cols)
+                        loss = self.loss(scores, cols['target'])
+                        if cols['state'] is not None:
+                            loss = torch.mean(cols['state'] * loss)
+                    evaluator.add_loss(loss, dl_idx)
+                    evaluator.update(_gather_rows(block, world), lay, dl_idx)                    # :415-426, one collective
+        self.last_val_blocks = evaluator.blocks
+        nested_metrics, losses = evaluator.compute()
+        val_loss = [losses[dl_idx] / len(self.valid_data_loader[dl_idx]) for dl_idx in range(n_loaders)]
+        if self.args.rank == 0:
+            for dl_idx in range(n_loaders):
+                name = getattr(self.valid_data_loader[dl_idx], 'dataset_name', 'TEST')
+                if self.writer is not None:
+                    self.writer.add_scalar(f'Loss_val/loss_total_{dl_idx}', val_loss[dl_idx], epoch - 1)     # :431-434
+                for metric_name, res in nested_metrics[dl_idx].items():
+                    self.logger.info(self._verbose(epoch=epoch, metrics=res, name=name))         # :449-450
+                    if self.writer is not None:
+                        for key, val in format_nested_metrics_for_writer(res, mode=metric_name, name=name).items():
+                            key = key.replace('[', '_').replace(']', '_')
+                            self.writer.add_scalar(f'Val_metrics_{dl_idx}/{key}', val, epoch - 1)            # :453-459
+        res_dict = {}
+        if self.args.rank == 0:                                                                  # :461-465
+            res_dict = {f'val_loss_{dl_idx}': val_loss[dl_idx] for dl_idx in range(n_loaders)}
+            res_dict['nested_val_metrics'] = nested_metrics
+        return res_dict
+
+
+def verbose(epoch, metrics, name="TEST"):
+    """The validation log line of trainer/trainer_oscc.py:479-483."""
+    msg = f"{name:s} epoch {epoch}, Acc: {metrics['accuracy']:.1f}"
+    print(msg)
+    return msg
+
+
+class Multi_Trainer_dist_OSCC(ClassificationTrainerBase):
+    """Drop-in for trainer/trainer_oscc.py:237-477 (configs/ft/oscc.json: projection_dim 2, CrossEntropy, oscc_metrics)."""
+
+    task = 'oscc'
+    _verbose = staticmethod(verbose)

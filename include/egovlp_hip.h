@@ -414,6 +414,39 @@ int64_t egv_maxmargin_head_work_floats(int32_t n, int32_t D);
 int egv_cross_entropy_fwd_bwd(const float* logits, int64_t ld, const int64_t* target, int32_t rows, int32_t cols,
                               int64_t ignore_index, float* loss, float* dlogits, int64_t ldd, void* stream);
 
+/* ---- classification head of the OSCC / PNR fine-tunes (csrc/cls_head.hip) -------------------------------------------------
+ * The narrow Linear behind the video tower (model/model.py:76, projection_dim = 2 | 16 | 17), its loss and backward over the
+ * all-gathered batch (trainer/trainer_oscc.py:335-338, trainer/trainer_pnr.py:341-350) and the validation scores
+ * (model/metric.py:342-397).  fp32 in memory, sums carried in fp64; deterministic (no atomics, fixed summation orders: two calls
+ * on the same input give identical bits).  Limits: C <= 64, K <= 1024 with K % 4 == 0, local rows B <= 256, gathered rows
+ * n <= 4096; anything else is EGV_ERR_ARG before any launch.
+ *
+ * scores[r, c] = bias[c] + sum_k feats[r, k] W[c, k]  for feats [B, K] (leading dimension ldf, ldf % 4 == 0, 16-byte aligned),
+ * W [C, K] (16-byte aligned), bias [C] or NULL; written to scores[r * ld + c], ld >= C: the first C columns of the row block
+ * the collective sends.                                                                                                     */
+int egv_cls_head_fwd(const float* feats, int64_t ldf, const float* W, const float* bias /* or NULL */, int32_t B, int32_t K,
+                     int32_t C, float* scores, int64_t ld, void* stream);
+/* Loss and backward on the gathered block packed [n, ld]: columns [0, C) the scores x, column col_target the class index t,
+ * column col_state (or -1) the PNR state; both integer-valued floats.  With s = mean of the state column (1 when col_state < 0):
+ *   loss = s (1/n) sum_r (logsumexp(x_r) - x_r[t_r])                     = CE (OSCC)  |  mean(state.T * CE) (PNR)
+ *   g_r  = s (softmax(x_r) - onehot(t_r)) / n  for the LOCAL rows r in [row0, row0 + B)   (AllGather_multi.backward's slice)
+ *   db [C] = sum_r g_r,  dW [C, K] = g^T feats,  dfeats [B, ldd] = g W        (each optional: NULL = skip; feats [B, ldf] local)
+ *   pred [n] (optional) = argmax of every score row, lowest index on ties.
+ * A target outside [0, C) makes the loss and every gradient NaN (as egv_cross_entropy_fwd_bwd).  work: n + 1 doubles.       */
+int egv_cls_head_loss_bwd(const float* packed, int64_t ld, int32_t n, int32_t C, int32_t col_target, int32_t col_state,
+                          int32_t row0, int32_t B, const float* feats, int64_t ldf, const float* W, int32_t K,
+                          float* loss, float* dW, float* db, float* dfeats, int64_t ldd, int32_t* pred, double* work,
+                          void* stream);
+/* Validation accumulator: accum = double[4] on the device {sum of hits, rows seen, sum of err_sec, positives seen}, updated in
+ * place with the rows of a gathered block in ascending order.
+ *   col_state < 0 (OSCC, model/metric.py:342-353): hit = argmax(x_r) == t_r; accum[0] += hits, accum[1] += n.
+ *   col_state >= 0 (PNR, :355-397), rows with state 1 only: mapped = float32((end - start) / 16) * float32(argmax(x_r)) in fp32
+ *   (the 16 is the reference's literal), err_sec = |mapped - (pnr - start)| / fps in fp64 with fps = (double)packed[r, col_fps] +
+ *   (double)packed[r, col_fps + 1] (an fp64 frame rate such as 29.97 split in two floats); accum[2] += err_sec, accum[3] += 1,
+ *   accum[1] += n.  col_target is not read for PNR.                                                                           */
+int egv_cls_eval_update(const float* packed, int64_t ld, int32_t n, int32_t C, int32_t col_target, int32_t col_state,
+                        int32_t col_fps, int32_t col_start, int32_t col_end, int32_t col_pnr, double* accum, void* stream);
+
 /* Dual-softmax re-scaling of a retrieval similarity matrix x [n texts, m videos] (run/test_epic.py:137-143, --dual_softmax):
  *   y = softmax(x / temp, dim 1) * x;  out = softmax(y, dim 0).  work: n*m floats.  temp = 500 in the reference.        */
 int egv_dual_softmax(const float* x, int32_t n, int32_t m, float temp, float* work, float* out, void* stream);
