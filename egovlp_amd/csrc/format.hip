@@ -576,6 +576,44 @@ extern "C" int egv_zero(void* p, int64_t bytes, void* stream) {
 // copy carries them).
 namespace {
 struct AugBox { int top, left, h, w, flip; };
+// Four consecutive pixels (x .. x + 3 of row y, channel c) of output frame bt -> the im2col planes of an R x R frame cut into P x P
+// patches: one 8-byte store per plane where the group lies inside one patch (P % 4 == 0: always), element-wise where it straddles
+// two (P = 14).
+__device__ __forceinline__ void store_patch4(const float (&v)[4], int bt, int c, int y, int x, int R, int P,
+                                             bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda) {
+  const int gw = R / P;
+  const int py = y / P, iy = y % P;
+  const int px = x / P, ix = x % P;
+  const long row = ((long)bt * gw + py) * gw + px;
+  const int col = (c * P + iy) * P + ix;
+  if (ix + 3 < P) {
+    uint32_t h0, h1, l0, l1;
+    split_bf16x2(v[0], v[1], h0, l0);
+    split_bf16x2(v[2], v[3], h1, l1);
+    if (((row * lda + col) & 3) == 0) {
+      *(u32x2_t*)(ahi + row * lda + col) = (u32x2_t){h0, h1};
+      if (alo) *(u32x2_t*)(alo + row * lda + col) = (u32x2_t){l0, l1};
+    } else {
+      *(uint32_t*)(ahi + row * lda + col) = h0;
+      *(uint32_t*)(ahi + row * lda + col + 2) = h1;
+      if (alo) {
+        *(uint32_t*)(alo + row * lda + col) = l0;
+        *(uint32_t*)(alo + row * lda + col + 2) = l1;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int xe = x + e;
+      const long rw = ((long)bt * gw + py) * gw + xe / P;
+      const int cl = (c * P + iy) * P + xe % P;
+      bf16_t h, l;
+      split_bf16(v[e], h, l);
+      ahi[rw * lda + cl] = h;
+      if (alo) alo[rw * lda + cl] = l;
+    }
+  }
+}
 __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned char* __restrict__ video, int BT, int T, int C,
                                                                int Hs, int Ws, int R, int P, const int* __restrict__ boxes,
                                                                bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda,
@@ -621,40 +659,7 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned ch
     const float val = (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
     v[e] = (val - mu) / sd;
   }
-  const int gw = R / P;
-  const int py = y / P, iy = y % P;
-  const int x = xg * 4;
-  const int px = x / P, ix = x % P;             // P % 4 == 0 is checked by the launcher... (P = 16); P = 14 takes the 2-pixel path below
-  const long row = ((long)bt * gw + py) * gw + px;
-  const int col = (c * P + iy) * P + ix;
-  if (ix + 3 < P) {
-    uint32_t h0, h1, l0, l1;
-    split_bf16x2(v[0], v[1], h0, l0);
-    split_bf16x2(v[2], v[3], h1, l1);
-    if (((row * lda + col) & 3) == 0) {
-      *(u32x2_t*)(ahi + row * lda + col) = (u32x2_t){h0, h1};
-      if (alo) *(u32x2_t*)(alo + row * lda + col) = (u32x2_t){l0, l1};
-    } else {
-      *(uint32_t*)(ahi + row * lda + col) = h0;
-      *(uint32_t*)(ahi + row * lda + col + 2) = h1;
-      if (alo) {
-        *(uint32_t*)(alo + row * lda + col) = l0;
-        *(uint32_t*)(alo + row * lda + col + 2) = l1;
-      }
-    }
-  } else {
-    // the 4-pixel group straddles two patches (P = 14): element-wise
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int xe = x + e;
-      const long rw = ((long)bt * gw + py) * gw + xe / P;
-      const int cl = (c * P + iy) * P + xe % P;
-      bf16_t h, l;
-      split_bf16(v[e], h, l);
-      ahi[rw * lda + cl] = h;
-      if (alo) alo[rw * lda + cl] = l;
-    }
-  }
+  store_patch4(v, bt, c, y, xg * 4, R, P, ahi, alo, lda);
 }
 }  // namespace
 
@@ -671,6 +676,138 @@ extern "C" int egv_patch_gather_u8_aug(const uint8_t* video, int32_t BT, int32_t
   const long total = (long)BT * C * R * (R / 4);
   EGV_LAUNCH(patch_gather_aug_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, video, BT, T, C, Hs,
              Ws, R, P, boxes, a_hi, a_lo, (long)lda, nrm);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+// ---- val / test transform fused into the patch gather (data_loader/transforms.py:49-60: Resize(S) -> CenterCrop(S) -> Resize(R) ->
+// Normalize, on x / 255; bilinear, align_corners = False, no antialias -- the tensor path of torchvision 0.13) ----------------------
+// The decoded uint8 frame bank [F, C, Hs, Ws] stays as it is; output frame bt reads bank frame index[bt] (clamped into the bank), so
+// a window of T frames is T entries of a table: overlapping, sub-sampled and ragged batches of windows cost no copy.  Every output
+// pixel is a bilinear sample (stage 2, S x S -> R x R) of four pixels of the centre crop of the stage-1 image, and each of those is
+// itself a bilinear sample (stage 1, Hs x Ws -> H1 x W1) of four source bytes: 16 byte loads per output pixel, 4 where stage 1 is
+// the identity (short side == S, the ego4d_256 frames).  Neither the H1 x W1 nor the R x R fp32 frame ever exists in memory.
+// Per 256 x 341 -> 224 frame 197 KB of the 262 KB source are touched once from HBM and 602 KB of planes (two bf16 planes of
+// 196 x 768) are written.  Bound: not HBM (1.2 TB/s of that traffic measured) but instruction issue -- the dependent
+// byte loads with their address arithmetic and the IEEE divisions that keep x / 255 and / std bit-compatible with the uint8 gather.
+namespace {
+struct LinTap { int i0, i1; float l; };
+// source taps of output index o of a bilinear resize n_in -> n_out (scale = (float)n_in / n_out), align_corners = False
+__device__ __forceinline__ LinTap lin_tap(int o, float scale, int n_in) {
+  float f = ((float)o + 0.5f) * scale - 0.5f;
+  f = f < 0.f ? 0.f : f;
+  const int i0 = min((int)f, n_in - 1);            // f < n_in by construction; the clamp makes it independent of rounding
+  LinTap t;
+  t.i0 = i0;
+  t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+  t.l = f - (float)i0;
+  return t;
+}
+__device__ __forceinline__ float bilerp(float ly, float lx, float p00, float p01, float p10, float p11) {
+  return (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
+}
+struct EvalGeom { int F, BT, C, Hs, Ws, H1, W1, top, left, S, R, P; };
+
+template <bool IDENT>   // IDENT: stage 1 is the identity (H1 == Hs, W1 == Ws)
+__global__ __launch_bounds__(256) void patch_gather_eval_kernel(const unsigned char* __restrict__ frames,
+                                                                const int* __restrict__ index, const EvalGeom g,
+                                                                bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda,
+                                                                const PatchNorm nrm) {
+  // thread -> (output frame bt, channel c, output row y, 4-pixel group xg)
+  const int R = g.R, WG = R / 4;
+  const long total = (long)g.BT * g.C * R * WG;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int xg = (int)(i % WG);
+  long t = i / WG;
+  const int y = (int)(t % R);
+  t /= R;
+  const int c = (int)(t % g.C);
+  const int bt = (int)(t / g.C);
+  // a table entry outside the bank is CLAMPED into it (the host validates tables it can see, ops.patch_gather_eval; a
+  // device-resident table cannot be checked without a sync): no read below can leave the bank
+  const int f = min(max(index ? index[bt] : bt, 0), g.F - 1);
+  const int Hs = g.Hs, Ws = g.Ws;
+  const unsigned char* src = frames + ((long)f * g.C + c) * Hs * Ws;
+  const float s2 = (float)g.S / (float)R;
+  const float s1y = (float)Hs / (float)g.H1, s1x = (float)Ws / (float)g.W1;
+  const LinTap ty = lin_tap(y, s2, g.S);                       // rows of the S x S crop
+  const int Y0 = g.top + ty.i0, Y1 = g.top + ty.i1;            // rows of the H1 x W1 stage-1 image (top + S <= H1)
+  LinTap ya, yb;                                               // source rows behind Y0 / Y1
+  if (IDENT) {
+    ya.i0 = ya.i1 = min(Y0, Hs - 1);
+    yb.i0 = yb.i1 = min(Y1, Hs - 1);
+    ya.l = yb.l = 0.f;
+  } else {
+    ya = lin_tap(Y0, s1y, Hs);
+    yb = lin_tap(Y1, s1y, Hs);
+  }
+  const unsigned char* ra0 = src + (long)ya.i0 * Ws;
+  const unsigned char* ra1 = src + (long)ya.i1 * Ws;
+  const unsigned char* rb0 = src + (long)yb.i0 * Ws;
+  const unsigned char* rb1 = src + (long)yb.i1 * Ws;
+  const float mu = nrm.mean[c], sd = nrm.std[c];
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const LinTap tx = lin_tap(xg * 4 + e, s2, g.S);
+    const int X0 = g.left + tx.i0, X1 = g.left + tx.i1;
+    float q00, q01, q10, q11;                                  // the four stage-1 pixels (Y0 | Y1, X0 | X1)
+    if (IDENT) {
+      const int x0 = min(X0, Ws - 1), x1 = min(X1, Ws - 1);
+      q00 = (float)ra0[x0] / 255.0f; q01 = (float)ra0[x1] / 255.0f;
+      q10 = (float)rb0[x0] / 255.0f; q11 = (float)rb0[x1] / 255.0f;
+    } else {
+      const LinTap xa = lin_tap(X0, s1x, Ws), xb = lin_tap(X1, s1x, Ws);
+      q00 = bilerp(ya.l, xa.l, (float)ra0[xa.i0] / 255.0f, (float)ra0[xa.i1] / 255.0f, (float)ra1[xa.i0] / 255.0f, (float)ra1[xa.i1] / 255.0f);
+      q01 = bilerp(ya.l, xb.l, (float)ra0[xb.i0] / 255.0f, (float)ra0[xb.i1] / 255.0f, (float)ra1[xb.i0] / 255.0f, (float)ra1[xb.i1] / 255.0f);
+      q10 = bilerp(yb.l, xa.l, (float)rb0[xa.i0] / 255.0f, (float)rb0[xa.i1] / 255.0f, (float)rb1[xa.i0] / 255.0f, (float)rb1[xa.i1] / 255.0f);
+      q11 = bilerp(yb.l, xb.l, (float)rb0[xb.i0] / 255.0f, (float)rb0[xb.i1] / 255.0f, (float)rb1[xb.i0] / 255.0f, (float)rb1[xb.i1] / 255.0f);
+    }
+    v[e] = (bilerp(ty.l, tx.l, q00, q01, q10, q11) - mu) / sd;
+  }
+  store_patch4(v, bt, c, y, xg * 4, R, g.P, ahi, alo, lda);
+}
+}  // namespace
+
+extern "C" int egv_patch_gather_u8_eval(const uint8_t* frames, int32_t F, const int32_t* index, int32_t BT, int32_t C, int32_t Hs,
+                                        int32_t Ws, int32_t S, int32_t R, int32_t P, const float* mean, const float* std,
+                                        egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  if (!frames || !a_hi || !mean || !std || F <= 0 || BT <= 0 || C <= 0 || C > 4) return EGV_ERR_ARG;
+  if (!index && BT > F) return EGV_ERR_ARG;                     // index == NULL: output frame bt IS bank frame bt
+  if (Hs <= 0 || Ws <= 0 || S <= 0 || R <= 0 || P <= 0 || R % P != 0 || R % 4 != 0 || P % 2 != 0 || lda % 2 != 0) return EGV_ERR_ARG;
+  if (lda < (int64_t)C * P * P) return EGV_ERR_ARG;
+  // Resize(S): the short side becomes S, the long side int(S * long / short) (torchvision's rule); sizes are kept below 2^20 so that
+  // every pixel coordinate is an exact fp32 integer and the products below cannot overflow
+  const int shrt = Hs < Ws ? Hs : Ws, lng = Hs < Ws ? Ws : Hs;
+  if (S >= (1 << 20) || R >= (1 << 20) || lng >= (1 << 20)) return EGV_ERR_ARG;
+  const double lng1 = (double)((int64_t)S * lng) / (double)shrt;
+  if (!(lng1 < (double)(1 << 20))) return EGV_ERR_ARG;
+  const int l1 = (int)lng1;                                     // >= S
+  EvalGeom g;
+  g.F = F; g.BT = BT; g.C = C; g.Hs = Hs; g.Ws = Ws; g.S = S; g.R = R; g.P = P;
+  g.H1 = Hs <= Ws ? S : l1;
+  g.W1 = Hs <= Ws ? l1 : S;
+  // CenterCrop(S): int(round((H1 - S) / 2.0)) with Python's round (halves go to the even neighbour)
+  auto centre = [](int d) { const int k = d / 2; return (d % 2 == 0 || k % 2 == 0) ? k : k + 1; };
+  g.top = centre(g.H1 - S);
+  g.left = centre(g.W1 - S);
+  PatchNorm nrm{};
+  for (int c = 0; c < C; ++c) {
+    if (!(std[c] > 0.f)) return EGV_ERR_ARG;
+    nrm.mean[c] = mean[c];
+    nrm.std[c] = std[c];
+  }
+  const long total = (long)BT * C * R * (R / 4);
+  const long blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffL) return EGV_ERR_ARG;
+  if (g.H1 == Hs && g.W1 == Ws) {
+    EGV_LAUNCH(patch_gather_eval_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, index, g, a_hi, a_lo,
+               (long)lda, nrm);
+  } else {
+    EGV_LAUNCH(patch_gather_eval_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, index, g, a_hi, a_lo,
+               (long)lda, nrm);
+  }
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }

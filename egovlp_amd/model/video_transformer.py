@@ -450,8 +450,13 @@ class _PatchTokensFn(torch.autograd.Function):
         wc = ec.wc
         mean, std = geom[6] if len(geom) > 6 else (ops.IMAGENET_MEAN, ops.IMAGENET_STD)
         aug = geom[7] if len(geom) > 7 else None
-        # uint8 frames: /255 + Normalize (and, with `aug`, the train transform's crop / resize / flip) inside the gather
-        a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug)
+        ev = geom[8] if len(geom) > 8 else None
+        if ev is not None:
+            # the val / test transform inside the gather: `video` is the uint8 frame bank, ev = (center_crop, out_res, frame table)
+            a = ops.patch_gather_eval(video.contiguous(), ev[2], T, P_, Pp, ev[0], ev[1], mean, std)
+        else:
+            # uint8 frames: /255 + Normalize (and, with `aug`, the train transform's crop / resize / flip) inside the gather
+            a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug)
         K = proj_w[0].numel()
         if a.cols == K:
             w_pl = wc.get(proj_w, need_t=False)[0]
@@ -654,18 +659,56 @@ class SpaceTimeTransformer(nn.Module):
         egovlp_amd.data_loader.transforms.train_transform_params) select, per clip, the region of the decoded uint8 frames
         that is resized to `out_res` (default: the model's img_size), flipped and normalised inside the patch gather.
         One-shot: consumed by the next forward_features call."""
+        if getattr(self, "_input_eval", None) is not None:
+            raise ValueError("set_input_augmentation: an eval transform is pending for the next forward (set_input_eval_transform)")
         host = boxes.detach().to(dtype=torch.int64).cpu() if not boxes.is_cuda else None     # checked against the frame size in forward
         if host is not None and (host.dim() != 2 or host.shape[1] != 5 or bool((host[:, :2] < 0).any()) or bool((host[:, 2:4] < 1).any())):
             raise ValueError("set_input_augmentation: boxes are int [B, 5] rows (top >= 0, left >= 0, h >= 1, w >= 1, flip)")
         self._input_aug = (boxes.to(device=self.cls_token.device, dtype=torch.int32).contiguous(),
                            int(out_res or self.patch_embed.img_size[0]), host)
 
+    def set_input_eval_transform(self, center_crop=256, out_res=None, frame_index=None):
+        """Fuse the loader's val / test transform (Resize(center_crop) -> CenterCrop(center_crop) -> Resize(out_res) -> Normalize,
+        data_loader/transforms.py:49-60) into the NEXT forward: it takes decoded uint8 frames [b, T, C, Hs, Ws] and resizes, crops
+        and normalises them inside the patch gather (`out_res` defaults to the model's img_size).  With `frame_index` (int [b, T])
+        the next forward takes a uint8 frame BANK [F, C, Hs, Ws] instead and row i of the table names the T bank frames of clip
+        i -- the windows of a long clip without a copy of its frames (egovlp_amd.extract).  A host table is validated against the
+        bank in forward; a device table is clamped into it by the kernel.  One-shot, and not combinable with
+        set_input_augmentation."""
+        if getattr(self, "_input_aug", None) is not None:
+            raise ValueError("set_input_eval_transform: a train augmentation is pending for the next forward (set_input_augmentation)")
+        S, R = int(center_crop), int(out_res or self.patch_embed.img_size[0])
+        if S < 1 or R < 1:
+            raise ValueError("set_input_eval_transform: center_crop and out_res are positive sizes")
+        if frame_index is not None:
+            if not torch.is_tensor(frame_index) or frame_index.dim() != 2 or frame_index.numel() == 0 \
+                    or frame_index.dtype not in (torch.int32, torch.int64):
+                raise ValueError("set_input_eval_transform: frame_index is an int32 / int64 [b, T] table of bank frame numbers")
+        self._input_eval = (S, R, frame_index)
+
     def forward_features(self, x):
-        b, curr_frames, channels, Hh, Ww = x.shape
-        assert curr_frames <= self.num_frames                                  # :74
-        P_ = self.patch_embed.patch_size[0]
+        ev = getattr(self, "_input_eval", None)
+        self._input_eval = None
         aug = getattr(self, "_input_aug", None)
         self._input_aug = None
+        if ev is not None:
+            if aug is not None:
+                raise ValueError("set_input_eval_transform and set_input_augmentation are mutually exclusive")
+            if x.dtype != torch.uint8:
+                raise ValueError("set_input_eval_transform expects decoded uint8 frames")
+            if ev[2] is not None:
+                if x.dim() != 4:
+                    raise ValueError("set_input_eval_transform(frame_index=...): the input is a uint8 frame bank [F, C, Hs, Ws]")
+                b, curr_frames = ev[2].shape
+                channels = x.shape[1]
+            else:
+                b, curr_frames, channels = x.shape[:3]
+                x = x.reshape(b * curr_frames, channels, *x.shape[3:])        # the batch is its own bank
+            Hh = Ww = ev[1]                                                    # the resized crop is what gets patched
+        else:
+            b, curr_frames, channels, Hh, Ww = x.shape
+        assert curr_frames <= self.num_frames                                  # :74
+        P_ = self.patch_embed.patch_size[0]
         if aug is not None:
             if x.dtype != torch.uint8:
                 raise ValueError("set_input_augmentation expects decoded uint8 frames")
@@ -681,7 +724,7 @@ class SpaceTimeTransformer(nn.Module):
         # `input_norm` = (mean, std) of the loader's Normalize (data_loader/transforms.py:34-39); only used when the frames
         # arrive as decoded uint8 (then x / 255 and the normalisation are fused into the patch gather on the device)
         geom = (b, curr_frames, n, P_, self.embed_dim, self.num_frames,
-                getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug)
+                getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev)
         ec = self.exec_ctx
         x = _PatchTokensFn.apply(x, geom, ec, self.patch_embed.proj.weight, self.patch_embed.proj.bias,
                                  self.cls_token, self.pos_embed, self.temporal_embed)

@@ -989,6 +989,44 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
     return pl
 
 
+def patch_gather_eval(frames, index, T, P, passes, center_crop=256, out_res=224, norm_mean=IMAGENET_MEAN,
+                      norm_std=IMAGENET_STD) -> Planes:
+    """im2col planes of the VAL / TEST transform (Resize(center_crop) -> CenterCrop(center_crop) -> Resize(out_res) -> Normalize,
+    data_loader/transforms.py:49-60) of decoded uint8 frames, made inside the patch gather (egv_patch_gather_u8_eval).
+    frames: uint8 [F, C, Hs, Ws], the frame bank.  index: None (the bank is the batch: F % T == 0) or an integer tensor of B*T
+    entries -- output frame bt is bank frame index[bt], so [B, T] rows are windows of a clip.  A host index is checked against the
+    bank (ValueError) and moved to the device; a device index cannot be checked without a sync and is clamped in the kernel.
+    -> Planes [B*T*(out_res/P)^2, K = C*P*P padded to a multiple of 64], as patch_gather."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError("the fused eval transform takes a bank of decoded uint8 frames [F, C, Hs, Ws]")
+    if not frames.is_contiguous():
+        raise ValueError("patch_gather_eval: the frame bank must be contiguous")
+    _need_cuda(frames)
+    Fn, Cc, Hs, Ws = frames.shape
+    S, R = int(center_crop), int(out_res)
+    if len(norm_mean) != Cc or len(norm_std) != Cc:
+        raise ValueError("patch_gather_eval: one mean / std per channel")
+    if index is None:
+        BT = Fn
+    else:
+        if not torch.is_tensor(index) or index.dtype not in (torch.int32, torch.int64) or index.numel() == 0:
+            raise ValueError("patch_gather_eval: index is a non-empty int32 / int64 tensor of bank frame numbers")
+        if not index.is_cuda and (int(index.min()) < 0 or int(index.max()) >= Fn):
+            raise ValueError(f"patch_gather_eval: index leaves the bank of {Fn} frames")
+        index = index.to(device=frames.device, dtype=torch.int32).contiguous()
+        BT = index.numel()
+    if T <= 0 or BT % T != 0:
+        raise ValueError(f"patch_gather_eval: {BT} frames do not make windows of {T}")
+    rows = BT * (R // P) * (R // P)
+    K = Cc * P * P
+    Kp = (K + 63) // 64 * 64
+    pl = empty_planes(rows, Kp, passes, frames.device, zero=(Kp != K))
+    mean, std = (C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)
+    check(_lib.lib().egv_patch_gather_u8_eval(_p(frames), Fn, _p(index), BT, Cc, Hs, Ws, S, R, P, mean, std, _p(pl.hi), _p(pl.lo),
+                                              pl.ld, _stream(frames)), "egv_patch_gather_u8_eval")
+    return pl
+
+
 def assemble_tokens(pe, cls, pos, temporal, B, T, n, D):
     x = torch.empty((B, 1 + T * n, D), dtype=torch.float32, device=pe.device)
     check(_lib.lib().egv_assemble_tokens(_p(pe), _p(cls), _p(pos), _p(temporal), B, T, n, D, _p(x), _stream(pe)),

@@ -290,6 +290,17 @@ int egv_patch_gather_u8(const uint8_t* video, int32_t BT, int32_t C, int32_t H, 
 int egv_patch_gather_u8_aug(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
                             int32_t P, const int32_t* boxes, const float* mean, const float* std, egv_bf16* a_hi,
                             egv_bf16* a_lo, int64_t lda, void* stream);
+/* The same gather with the VAL / TEST transform of the loader fused in (data_loader/transforms.py:49-60: Resize(S) -> CenterCrop(S)
+ * -> Resize(R) -> Normalize, applied to x / 255 in fp32; bilinear, align_corners = False, no antialias).  `frames` is a bank of F
+ * decoded uint8 frames [F, C, Hs, Ws]; output frame bt is made from bank frame index[bt] (`index`: int32 [BT] on the DEVICE, entries
+ * clamped into [0, F-1]; NULL = bt, then BT <= F), so windows of a clip -- overlapping, sub-sampled, a ragged last batch -- are
+ * rows of a table and the frames are never copied.  Stage 1: short side -> S, long side -> int(S * long / short); centre crop at
+ * int(round((H1 - S) / 2.0)); stage 2: S x S -> R x R, every tap of it a bilinear sample of the source (four source bytes per output
+ * pixel where the short side already equals S, sixteen otherwise).  Planes as egv_patch_gather_u8_aug (R % P == 0, R % 4 == 0,
+ * P even, a_lo == NULL: one plane); `mean` / `std` HOST arrays of C <= 4 floats.  EGV_ERR_ARG (nothing launched) for anything else. */
+int egv_patch_gather_u8_eval(const uint8_t* frames, int32_t F, const int32_t* index, int32_t BT, int32_t C, int32_t Hs,
+                             int32_t Ws, int32_t S, int32_t R, int32_t P, const float* mean, const float* std,
+                             egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
 /* x[b,0,:] = cls + pos[0]; x[b,1+f*n+i,:] = pe[(b*T+f)*n+i,:] + pos[1+i] + temporal[f]
  * (model/video_transformer.py:305-320; pos tiling by the MODEL's num_frames, sliced to T).          */
 int egv_assemble_tokens(const float* pe, const float* cls, const float* pos, const float* temporal,
