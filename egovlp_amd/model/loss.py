@@ -15,7 +15,7 @@ node: the narrow projection (egv_cls_head_fwd), one packed collective, loss and 
 import torch
 from torch import nn
 
-from .. import loss_ops, ops
+from .. import gather, loss_ops, ops
 
 
 class _LossFromSimFn(torch.autograd.Function):
@@ -174,13 +174,12 @@ class CrossEntropy(nn.Module):
 class _ClsHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, bias, target, state, world, rank, ec=None):
-        from ..trainer import trainer_egoclip as T
         B, C = feats.shape[0], weight.shape[0]
         lay = loss_ops.ClsLayout(C, 'oscc' if state is None else 'pnr')
         packed = torch.empty((B, lay.ld), dtype=torch.float32, device=feats.device)
         loss_ops.cls_head_fwd(feats, weight, bias, out=packed)
         lay.fill(packed, target, state)
-        allp = T._gather_rows(packed, world)                  # the ONE collective of the step; nothing is sent at world size 1
+        allp = gather._gather_rows(packed, world)             # the ONE collective of the step; nothing is sent at world size 1
         loss, dW, db, dx, _ = loss_ops.cls_head_loss_bwd(allp, C, lay.target, lay.state, row0=rank * B, B=B, feats=feats,
                                                          weight=weight)
         ctx.ec, ctx.has_bias = ec, bias is not None

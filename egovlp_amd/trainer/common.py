@@ -1,0 +1,181 @@
+"""What the five trainers share: the two ends of an optimisation step, the prefetching host-to-device feed and `TrainerBase`
+(constructor, LR rule, precision guard, host batch order and the training epoch of the reference's trainer files, which repeat
+them line for line: trainer/trainer_egoclip.py:29-180 == trainer_epic.py:29-171 == trainer_oscc.py:237-380 ...)."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..base.base_trainer import Multi_BaseTrainer_dist
+from ..gather import AllGather_multi
+
+
+def step_prologue(model, optimizer, scaler):
+    """Opens egoclip_step / retrieval_step / classification_step -> (the unwrapped model, its execution context, the scaler):
+    `scaler` defaults to the model's own when its backward precision is 'f16'; then zero_grad."""
+    core = getattr(model, 'module', model)
+    ec = getattr(core, 'exec_ctx', None)
+    if scaler is None and ec is not None and ec.bwd_passes == 4:
+        # fp16 gradient planes flush un-scaled gradients of 1e-6 to zero: the model's own scaler (on the device its parameters live on)
+        scaler = ec.loss_scaler(device=next(core.parameters()).device)
+    optimizer.zero_grad(set_to_none=True)
+    return core, ec, scaler
+
+
+def step_epilogue(loss, ec, optimizer, grad_sync, scaler):
+    """Closes the three steps: (scaled) backward, wait for the side stream and the gradient exchange, optimizer.step.
+    -> the detached (device) loss; no host sync."""
+    (loss if scaler is None else scaler.scale(loss)).backward()
+    if ec is not None:
+        ec.join_side_stream()       # idempotent; covers a backward whose end-of-pass callback did not run
+    if grad_sync is not None:
+        grad_sync.finish()
+    if scaler is None:
+        optimizer.step()
+    else:
+        optimizer.step(scaler=scaler)
+    return loss.detach()
+
+
+def _to_device_async(data, device, stream):
+    """Host batch -> device on `stream`: tensors go through pinned staging copies (a pageable source makes the copy synchronous);
+    -> (device batch, event of the last copy).  Keys that are not tensors are passed through."""
+    out = {}
+
+    def put(t):
+        if not torch.is_tensor(t) or t.device.type != 'cpu' or torch.device(device).type != 'cuda':
+            return t.to(device) if torch.is_tensor(t) else t
+        src = t if t.is_pinned() else t.contiguous().pin_memory()
+        return src.to(device, non_blocking=True)
+    if torch.device(device).type == 'cuda':
+        with torch.cuda.stream(stream):
+            for k, v in data.items():
+                out[k] = {kk: put(vv) for kk, vv in v.items()} if isinstance(v, dict) or hasattr(v, 'items') else put(v)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        return out, ev
+    for k, v in data.items():
+        out[k] = {kk: put(vv) for kk, vv in v.items()} if isinstance(v, dict) or hasattr(v, 'items') else put(v)
+    return out, None
+
+
+def _prefetched(host_iter, device):
+    """Yield (batch_idx, dl_idx, device batch) with the copy of batch i + 1 in flight on a copy stream while batch i is consumed;
+    ends with (None, None, None)."""
+    cuda = torch.device(device).type == 'cuda'
+    stream = torch.cuda.Stream() if cuda else None
+    it = iter(host_iter)
+
+    def start():
+        try:
+            bi, di, data = next(it)
+        except StopIteration:
+            return None
+        dev, ev = _to_device_async(data, device, stream)
+        return bi, di, dev, ev
+    nxt = start()
+    while nxt is not None:
+        bi, di, dev, ev = nxt
+        nxt = start()                    # the next batch's host work + copy start BEFORE this batch's step is enqueued
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+            for v in dev.values():       # the tensors were allocated on the copy stream: tell the allocator who uses them
+                for t in (v.values() if isinstance(v, dict) else [v]):
+                    if torch.is_tensor(t) and t.is_cuda:
+                        t.record_stream(torch.cuda.current_stream())
+        yield bi, di, dev
+    yield None, None, None
+
+
+class TrainerBase(Multi_BaseTrainer_dist):
+    """The reference's trainer constructor and training hot loop (trainer/trainer_egoclip.py:29-180); `train()` / checkpointing
+    come from egovlp_amd.base.Multi_BaseTrainer_dist.  A trainer adds `_step` (its optimisation step), `_valid_epoch` and, where
+    its batches need other host work than tokenising, `_host_batch`."""
+
+    fused_head = True               # False: the steps take the reference's own decomposition (sim_matrix + loss / projection + loss)
+    _guard = None
+
+    def __init__(self, args, model, loss, metrics, optimizer, config, data_loader, valid_data_loader=None,
+                 lr_scheduler=None, len_epoch=None, writer=None, visualizer=None, tokenizer=None,
+                 max_samples_per_epoch=50000):
+        super().__init__(args, model, loss, metrics, optimizer, config, writer)
+        self.config = config
+        self.args = args
+        self.data_loader = data_loader
+        self.len_epoch = min(len(x) for x in data_loader) if len_epoch is None else len_epoch    # epoch-based training (:44-47)
+        self.valid_data_loader = valid_data_loader
+        self.do_validation = self.valid_data_loader is not None
+        self.lr_scheduler = lr_scheduler
+        self.visualizer = visualizer
+        self.val_chunking = True
+        self.metrics = metrics if metrics is not None else []
+        self.batch_size = self.data_loader[0].batch_size
+        self.log_step = int(np.sqrt(self.batch_size))
+        self.total_batch_sum = sum(x.batch_size for x in self.data_loader)
+        self.tokenizer = tokenizer
+        self.max_samples_per_epoch = max_samples_per_epoch
+        self.n_gpu = self.args.world_size
+        self.allgather = AllGather_multi.apply
+
+    def _host_batch(self, data):
+        """Host-side preparation of one loader batch before it is staged for the device: the captions are tokenised."""
+        if self.tokenizer is not None:
+            data['text'] = self.tokenizer(data['text'], return_tensors='pt', padding=True, truncation=True)
+        return data
+
+    def _host_batches(self):
+        """(batch_idx, dl_idx, data on the HOST) in the reference's order and with its stopping rules (:104-108,158-159)."""
+        for batch_idx, data_li in enumerate(zip(*self.data_loader)):
+            if (batch_idx + 1) * self.total_batch_sum > self.max_samples_per_epoch:
+                break
+            for dl_idx, data in enumerate(data_li):
+                yield batch_idx, dl_idx, self._host_batch(data)
+            if batch_idx == self.len_epoch:
+                break
+
+    def _adjust_learning_rate(self, optimizer, epoch, args):
+        lr = args.learning_rate1                                            # :75-80
+        for milestone in args.schedule:
+            lr *= 0.1 if epoch >= milestone else 1.
+        for param_group in optimizer.param_groups:
+            param_group['lr'] = lr
+
+    def _step(self, data):
+        """The optimisation step of one device batch -> its (device) loss."""
+        raise NotImplementedError
+
+    def _train_epoch(self, epoch):
+        self.model.train()
+        total_loss = [torch.zeros((), device=self.device) for _ in self.data_loader]
+        for loader in self.data_loader:
+            if hasattr(loader, 'train_sampler'):
+                loader.train_sampler.set_epoch(epoch)                       # :101-102
+        # The reference moves every batch to the device with blocking `.to(device)` calls on the compute stream right before the
+        # step (:115-121).  Here the NEXT batch is prepared (negatives concatenated, captions tokenised), staged in pinned host
+        # memory and copied on a private copy stream while the current step runs; the step only waits for the copy's event.
+        feed = _prefetched(self._host_batches(), self.device)
+        for batch_idx, dl_idx, data in feed:
+            if batch_idx is None:
+                break
+            # the per-block precision policy is measured on the weights at hand: first batch, then every `precision_guard_interval`
+            # steps (egovlp_amd.guard.PrecisionGuard; a no-op unless the forward runs fp16 products)
+            if self._guard is None:
+                from ..guard import PrecisionGuard
+                self._guard = PrecisionGuard(self.model, interval=int(getattr(self.args, 'precision_guard_interval', 1000)))
+            self._guard.maybe_check(data)
+            loss = self._step(data)
+            total_loss[dl_idx] += loss      # stays on the device: no per-step .item() sync (reference :148,150)
+            if self.writer is not None and self.args.rank == 0 and batch_idx % self.log_step == 0:
+                total = int(self.data_loader[dl_idx].n_samples / self.n_gpu) if hasattr(self.data_loader[dl_idx], 'n_samples') else 0
+                current = batch_idx * self.data_loader[dl_idx].batch_size
+                self.writer.add_scalar(f'Loss_training/loss_{dl_idx}', float(loss), (epoch - 1) * total + current)   # :143-148
+        log = {f'loss_{dl_idx}': float(total_loss[dl_idx]) / self.len_epoch for dl_idx in range(len(self.data_loader))}   # :162-164
+        if self.writer is not None and self.args.rank == 0:
+            for dl_idx in range(len(self.data_loader)):
+                self.writer.add_scalar(f'Loss_training/loss_total_{dl_idx}', log[f'loss_{dl_idx}'], epoch - 1)
+        if self.do_validation:                                              # :172-175
+            val_log = self._valid_epoch(epoch)
+            if self.args.rank == 0:
+                log.update(val_log)
+        self._adjust_learning_rate(self.optimizer, epoch, self.args)        # :178
+        return log

@@ -11,8 +11,8 @@ import os
 
 import torch
 
+from ..gather import _gather_rows, _world
 from ..model.model import sim_matrix
-from .trainer_egoclip import _gather_rows, _world
 from .trainer_epic import RetrievalTrainerBase, format_nested_metrics_for_writer  # noqa: F401  (re-exported, as the reference file has it)
 
 CHARADES_CLASSES_FILE = 'dataset/charades/CharadesEgo/Charades_v1_classes.txt'      # trainer/trainer_charades.py:187

@@ -9,7 +9,7 @@ collective instead of two or three, egv_cls_head_loss_bwd) where the padded-GEMM
 fifteen launches for a [4, 768] x [768, 2] product.  `fused_head=False` (or a shape outside `cls_head_ok`) is that earlier route.
 
 `Multi_Trainer_dist_OSCC` keeps the reference's constructor and `train()` flow; constructor, batch feed, LR rule, precision guard
-and epoch loop are RetrievalTrainerBase's.  Validation (:382-467) runs on the device: one forward, one gathered block and one
+and epoch loop are TrainerBase's (trainer/common.py).  Validation (:382-467) runs on the device: one forward, one gathered block and one
 egv_cls_eval_update per batch, the rank-local validation loss (:428) summed there too (`monitor: "min val_loss_0"`).
 """
 from __future__ import annotations
@@ -17,9 +17,10 @@ from __future__ import annotations
 import torch
 
 from .. import loss_ops
+from ..gather import AllGatherRows, _gather_rows, _world
 from ..loss_ops import ClsLayout, cls_head_ok
 from .classification_eval import ClassificationEvaluator
-from .trainer_egoclip import AllGatherRows, _gather_rows, _world
+from .common import step_epilogue, step_prologue
 from .trainer_epic import RetrievalTrainerBase, format_nested_metrics_for_writer  # noqa: F401  (re-exported, as the reference file has it)
 
 
@@ -43,11 +44,7 @@ def classification_step(model, loss_fn, optimizer, data, world_size=1, rank=0, t
                         scaler=None):
     """One fine-tuning step on a batch {'video', 'state'[, 'labels']} already on the device.  Returns the (device) loss tensor; no
     host sync.  `grad_sync` / `scaler`: as egoclip_step."""
-    core = getattr(model, 'module', model)
-    ec = getattr(core, 'exec_ctx', None)
-    if scaler is None and ec is not None and ec.bwd_passes == 4:
-        scaler = ec.loss_scaler(device=next(core.parameters()).device)
-    optimizer.zero_grad(set_to_none=True)                                       # trainer_oscc.py:333
+    core, ec, scaler = step_prologue(model, optimizer, scaler)                  # trainer_oscc.py:333
     video = data['video']
     target, state = _targets(data, task, video.device)
     lin, B = _head(core), video.shape[0]
@@ -63,16 +60,7 @@ def classification_step(model, loss_fn, optimizer, data, world_size=1, rank=0, t
         else:
             scores, target, state = AllGatherRows.apply(world_size, rank, scores, target, state)   # pnr :345-347
             loss = torch.mean(state * loss_fn(scores, target))                  # pnr :350
-    (loss if scaler is None else scaler.scale(loss)).backward()                 # :339
-    if ec is not None:
-        ec.join_side_stream()
-    if grad_sync is not None:
-        grad_sync.finish()
-    if scaler is None:
-        optimizer.step()                                                        # :341
-    else:
-        optimizer.step(scaler=scaler)
-    return loss.detach()
+    return step_epilogue(loss, ec, optimizer, grad_sync, scaler)                # :339-341
 
 
 class ClassificationTrainerBase(RetrievalTrainerBase):
@@ -82,14 +70,8 @@ class ClassificationTrainerBase(RetrievalTrainerBase):
     task = 'oscc'
     keep_val_blocks = False         # checks only: keep every gathered validation block in `last_val_blocks`
 
-    def _host_batches(self):
-        for batch_idx, data_li in enumerate(zip(*self.data_loader)):
-            if (batch_idx + 1) * self.total_batch_sum > self.max_samples_per_epoch:             # :326-327
-                break
-            for dl_idx, data in enumerate(data_li):
-                yield batch_idx, dl_idx, data
-            if batch_idx == self.len_epoch:                                                      # :361-362
-                break
+    def _host_batch(self, data):
+        return data
 
     def _step(self, data):
         return classification_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank, task=self.task,
@@ -136,22 +118,13 @@ class ClassificationTrainerBase(RetrievalTrainerBase):
         self.last_val_blocks = evaluator.blocks
         nested_metrics, losses = evaluator.compute()
         val_loss = [losses[dl_idx] / len(self.valid_data_loader[dl_idx]) for dl_idx in range(n_loaders)]
-        if self.args.rank == 0:
-            for dl_idx in range(n_loaders):
-                name = getattr(self.valid_data_loader[dl_idx], 'dataset_name', 'TEST')
-                if self.writer is not None:
-                    self.writer.add_scalar(f'Loss_val/loss_total_{dl_idx}', val_loss[dl_idx], epoch - 1)     # :431-434
-                for metric_name, res in nested_metrics[dl_idx].items():
-                    self.logger.info(self._verbose(epoch=epoch, metrics=res, name=name))         # :449-450
-                    if self.writer is not None:
-                        for key, val in format_nested_metrics_for_writer(res, mode=metric_name, name=name).items():
-                            key = key.replace('[', '_').replace(']', '_')
-                            self.writer.add_scalar(f'Val_metrics_{dl_idx}/{key}', val, epoch - 1)            # :453-459
-        res_dict = {}
-        if self.args.rank == 0:                                                                  # :461-465
-            res_dict = {f'val_loss_{dl_idx}': val_loss[dl_idx] for dl_idx in range(n_loaders)}
-            res_dict['nested_val_metrics'] = nested_metrics
-        return res_dict
+        for dl_idx in range(n_loaders):
+            if self.writer is not None and self.args.rank == 0:
+                self.writer.add_scalar(f'Loss_val/loss_total_{dl_idx}', val_loss[dl_idx], epoch - 1)         # :431-434
+            for metric_name, res in nested_metrics[dl_idx].items():
+                # :449-459; the reference's verbose() of these two trainers takes no `mode`
+                self._report(epoch, dl_idx, metric_name, res, lambda mode, **kw: self._verbose(**kw))
+        return self._val_result(nested_metrics, val_loss)                                        # :461-465
 
 
 def verbose(epoch, metrics, name="TEST"):

@@ -218,7 +218,7 @@ def test_gathered_block_has_the_documented_layout(monkeypatch):
     kernel is handed the gathered block and this rank's row offset."""
     from egovlp_amd import loss_ops
     from egovlp_amd.model.loss import _ClsHeadFn
-    from egovlp_amd.trainer import trainer_egoclip as T
+    from egovlp_amd import gather as T
     monkeypatch.setattr(T, "_gather_rows", lambda t, world: torch.cat([t + 100.0, t]))
     seen = {}
     real = loss_ops.cls_head_loss_bwd

@@ -195,7 +195,7 @@ def test_adaptive_loss_needs_its_weight(model):
 def test_gather_rows_packs_and_unpacks(monkeypatch):
     """AllGatherRows with the collective replaced by a two-rank stand-in: columns are split back into the inputs' shapes, the
     backward hands each input its local rows."""
-    from egovlp_amd.trainer import trainer_egoclip as T
+    from egovlp_amd import gather as T
     monkeypatch.setattr(T, "_gather_rows", lambda t, world: torch.cat([t, t + 100.0]))
     v = torch.arange(12.0).reshape(3, 4).requires_grad_(True)
     t = torch.arange(6.0).reshape(3, 2).requires_grad_(True)

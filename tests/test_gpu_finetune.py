@@ -387,7 +387,7 @@ def test_forced_gather_path_gives_the_same_loss(monkeypatch, adaptive):
     from egovlp_amd.model.loss import AdaptiveMaxMarginRankingLoss, MaxMarginRankingLoss
     from egovlp_amd.optim import AdamW
     from egovlp_amd.synth import synth_batch
-    from egovlp_amd.trainer import trainer_egoclip
+    from egovlp_amd import gather
     from egovlp_amd.trainer.trainer_epic import retrieval_step
     batch = synth_batch(4, T=2, L=16, seed=11, ragged=True)
     data = {"video": batch["video"].cuda(), "text": {k: v.cuda() for k, v in batch["text"].items()},
@@ -396,8 +396,8 @@ def test_forced_gather_path_gives_the_same_loss(monkeypatch, adaptive):
     m, _ = _synth_model()
     plain = float(retrieval_step(m, loss_fn, AdamW(m.parameters(), lr=3e-5), data))
     gathers = []
-    orig = trainer_egoclip._gather_rows
-    monkeypatch.setattr(trainer_egoclip, "_gather_rows", lambda t, world: gathers.append(tuple(t.shape)) or orig(t, world))
+    orig = gather._gather_rows
+    monkeypatch.setattr(gather, "_gather_rows", lambda t, world: gathers.append(tuple(t.shape)) or orig(t, world))
     monkeypatch.setenv("EGV_FORCE_GATHER", "1")
     monkeypatch.setenv("MASTER_ADDR", "127.0.0.1")
     with socket.socket() as s:

@@ -4,6 +4,7 @@ in which gradients become final is the real one -- which is what the hook-free g
 (round-2 advisor finding: with the wrong order every bucket left from finish(), fully exposed).  No numerics here."""
 import collections
 import os
+import types
 
 import pytest
 import torch
@@ -59,6 +60,62 @@ def test_full_step_wiring_and_launch_census(model):
     # GEMM calls: 12 video blocks x (6 forward + 6 dgrad + 6 wgrad), patch embed (forward + wgrad), 6 DistilBERT layers x
     # (4 forward + 4 dgrad + 4 wgrad; q/k/v fused), two projections x (forward + dgrad + wgrad)
     assert c["egv_gemm_nt"] == 12 * 18 + 2 + 6 * 12 + 2 * 3, c["egv_gemm_nt"]
+
+
+class _Tok:
+    def __call__(self, texts, return_tensors='pt', padding=True, truncation=True):
+        ids = torch.full((len(texts), 8), 1500, dtype=torch.long)
+        ids[:, 0] = 101
+        return {"input_ids": ids, "attention_mask": torch.ones(len(texts), 8, dtype=torch.long)}
+
+
+class _NegLoader:
+    """Two EgoClip batches of B clips, each with B scene-aware negatives (data_loader/EgoClip_EgoMCQ_dataset.py: the `_neg` keys)."""
+    batch_size, n_samples = 2, 4
+
+    def __len__(self):
+        return 2
+
+    def __iter__(self):
+        for i in range(2):
+            d, neg = _batch(self.batch_size), _batch(self.batch_size)
+            d["text"] = ["a caption"] * self.batch_size
+            d.update(text_neg=["another caption"] * self.batch_size, video_neg=neg["video"], noun_vec_neg=neg["noun_vec"],
+                     verb_vec_neg=neg["verb_vec"])
+            yield d
+
+
+def test_egoclip_trainer_epoch_loop_dry_run(model):
+    """Multi_Trainer_dist._train_epoch on two batches with scene-aware negatives: the host side doubles every batch (clips,
+    captions, noun / verb rows) and drops the `_neg` keys before the copy, each step takes the one-call EgoNCE head, the log holds
+    the training loss alone (no validation loader) and the LR rule is applied after the epoch."""
+    from egovlp_amd.model.loss import EgoNCE
+    from egovlp_amd.optim import AdamW
+    from egovlp_amd.trainer.trainer_egoclip import AllGather_multi, Multi_Trainer_dist
+    tr = Multi_Trainer_dist.__new__(Multi_Trainer_dist)          # without Multi_BaseTrainer_dist.__init__, which needs a HIP device
+    tr.args = types.SimpleNamespace(world_size=1, rank=0, local_rank=0, learning_rate1=2e-4, schedule=[1, 80])
+    tr.model, tr.loss, tr.metrics, tr.device = model, EgoNCE(), [], torch.device("cpu")
+    tr.optimizer = AdamW(model.parameters(), lr=3e-5)
+    tr.data_loader, tr.valid_data_loader, tr.do_validation = [_NegLoader()], None, False
+    tr.len_epoch, tr.total_batch_sum, tr.max_samples_per_epoch = 2, 2, 50000
+    tr.batch_size, tr.log_step, tr.n_gpu = 2, 1, 1
+    tr.tokenizer, tr.writer, tr.grad_sync, tr.allgather = _Tok(), None, None, AllGather_multi.apply
+    seen = []
+    hook = model.register_forward_pre_hook(lambda mod, args: seen.append(
+        (args[0]["video"].shape[0], args[0]["text"]["input_ids"].shape[0], args[0]["noun_vec"].shape[0], args[0]["verb_vec"].shape[0],
+         sorted(k for k in args[0] if k.endswith("_neg")))))
+    with mock_hip() as calls:
+        model.exec_ctx.set_precision("bf16x3", "bf16")
+        try:
+            log = tr._train_epoch(1)
+        finally:
+            model.exec_ctx.unset("fwd_passes", "bwd_passes")
+            hook.remove()
+    c = collections.Counter(calls)
+    assert seen == [(4, 4, 4, 4, [])] * 2                          # 2B clips, 2B token rows, 2B noun / verb rows; no `_neg` key left
+    assert c["egv_egonce_fwd_bwd"] == 2 and c["egv_sim_matrix_fwd"] == 0 and c["egv_sim_matrix_bwd"] == 0 and c["egv_egonce_from_sim"] == 0
+    assert set(log) == {"loss_0"}
+    assert tr.optimizer.param_groups[0]["lr"] == pytest.approx(2e-5)          # schedule [1, 80] at epoch 1
 
 
 def test_each_model_has_its_own_execution_context():
