@@ -173,7 +173,92 @@ __global__ void loss_scale_update_kernel(int* __restrict__ state, float* __restr
   hyper_out[3] = skip;
 }
 
+// ---- gradient accumulation of the embedding-cache step ------------------------------------------------------------------------------
+// dst[i][j] += src[i][j]: the chunk gradients of a step that re-encodes its batch in chunks are summed into one accumulator per
+// parameter.  Pure HBM traffic (8 B read + 4 B written per element).  Work list: (tensor, CHUNK-element piece) per block, 16-byte
+// pieces inside it; every element has exactly one writer (no atomics: the sum does not depend on the grid).  120 tensors per launch
+// keep the pointer table inside the 4 KB of kernel arguments.
+constexpr int ACC_MAX_T = 120;
+struct AccumTable {
+  float* d[ACC_MAX_T];
+  const float* s[ACC_MAX_T];
+  long numel[ACC_MAX_T];
+  int blk_start[ACC_MAX_T + 1];
+  int count;
+};
+static_assert(sizeof(AccumTable) <= 4096, "the table travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccumTable t) {
+  int lo = 0, hi = t.count - 1;          // the tensor this block works on: last ti with blk_start[ti] <= blockIdx.x (<= 7 scalar steps)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int)blockIdx.x >= t.blk_start[mid]) lo = mid; else hi = mid - 1;
+  }
+  const int ti = lo;
+  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * CHUNK;
+  const long n = t.numel[ti];
+  float* __restrict__ d = t.d[ti];
+  const float* __restrict__ s = t.s[ti];
+  const long end = min(n, base + CHUNK);
+  // 16-byte pieces where both bases allow them (a view at an odd offset takes the scalar loop), then the tensor's last n % 4 elements
+  const bool vec = (((((size_t)d) | ((size_t)s)) & 15) == 0);
+  const long vend = vec ? min(end, n & ~3L) : base;
+  long i = base + threadIdx.x * 4;
+  for (; i + 3 * 1024 < vend; i += 4 * 1024) {       // four independent 16-byte load pairs per lane in flight
+    f32x4_t a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a[u] = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(d + i + u * 1024);
+      b[u] = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(s + i + u * 1024);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) egv_store<EGV_NT_ADAMW_ST>(d + i + u * 1024, a[u] + b[u]);
+  }
+  for (; i < vend; i += 1024) {
+    const f32x4_t a = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(d + i), b = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(s + i);
+    egv_store<EGV_NT_ADAMW_ST>(d + i, a + b);
+  }
+  for (long j = max(base, vend) + threadIdx.x; j < end; j += 256) d[j] = d[j] + s[j];
+}
+
 }  // namespace
+
+extern "C" int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* const* src, const int64_t* numel, void* stream) {
+  if (count < 0 || (count > 0 && (!dst || !src || !numel))) return EGV_ERR_ARG;
+  for (int i = 0; i < count; ++i) {      // validate everything before the first launch: a bad argument enqueues nothing
+    if (numel[i] < 0) return EGV_ERR_ARG;
+    if (numel[i] == 0) continue;
+    if (!dst[i] || !src[i]) return EGV_ERR_ARG;
+    if (dst[i] < src[i] + numel[i] && src[i] < dst[i] + numel[i]) return EGV_ERR_ARG;      // overlapping ranges
+  }
+  hipStream_t s = (hipStream_t)stream;
+  AccumTable t;
+  int nt = 0, nb = 0;
+  auto flush = [&]() -> int {
+    if (nt == 0) return EGV_OK;
+    t.blk_start[nt] = nb;
+    t.count = nt;
+    EGV_LAUNCH(grad_accumulate_kernel, dim3(nb), dim3(256), 0, s, t);
+    EGV_CHECK_LAUNCH();
+    nt = 0;
+    nb = 0;
+    return EGV_OK;
+  };
+  for (int i = 0; i < count; ++i) {
+    if (numel[i] == 0) continue;
+    if (nt == ACC_MAX_T) {
+      const int rc = flush();
+      if (rc) return rc;
+    }
+    t.d[nt] = dst[i];
+    t.s[nt] = src[i];
+    t.numel[nt] = numel[i];
+    t.blk_start[nt] = nb;
+    nb += (int)((numel[i] + CHUNK - 1) / CHUNK);
+    ++nt;
+  }
+  return flush();
+}
 
 extern "C" int egv_grad_nonfinite_multi(int32_t count, const float* const* g, const int64_t* numel, int32_t* state, void* stream) {
   if (count < 0 || !g || !numel || !state) return EGV_ERR_ARG;

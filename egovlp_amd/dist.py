@@ -34,6 +34,7 @@ layout, hook accounting, collective calls) can be exercised on CPU tensors with 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Callable, List, Optional
 
@@ -154,6 +155,8 @@ class Bf16GradSync:
         self._seen = set()
         self.stats = {"buckets": 0, "collectives_last_step": 0, "bytes_last_step": 0, "launched_during_backward": 0}
         self._handles = []
+        self._held = False              # hold(): gradients that appear are not final yet -- nothing leaves
+        self._was_held = False
         if not use_hooks:
             if order_hint is not None:
                 hinted = [p for p in order_hint if p.requires_grad]
@@ -173,6 +176,20 @@ class Bf16GradSync:
             else:
                 self._handles.append(p.register_post_accumulate_grad_hook(self._on_ready))
 
+    @contextlib.contextmanager
+    def hold(self):
+        """Inside: no bucket leaves -- `poll()` and the grad-ready hooks launch nothing.  For a step that runs several backward
+        passes and sums their gradients itself (the embedding-cache step, egovlp_amd/trainer/cached_step.py): a gradient that
+        exists after the first pass is a partial sum, and "p.grad is not None" / "the hook fired" no longer mean "final".
+        `finish()`, called after the block, launches every bucket on the summed gradients: the exchange of such a step is not
+        overlapped with its backward passes."""
+        prev, self._held = self._held, True
+        self._was_held = True
+        try:
+            yield self
+        finally:
+            self._held = prev
+
     # ---- hooks (run on the autograd engine thread, in the order gradients become final) ----------------------------
     def _on_ready(self, p):
         i = self._index[id(p)]
@@ -180,6 +197,8 @@ class Bf16GradSync:
             if i not in self._seen:
                 self._seen.add(i)
                 self._ready_order.append(i)
+            return
+        if self._held:
             return
         b = self._bucket_of.get(i)
         if b is None:
@@ -247,7 +266,7 @@ class Bf16GradSync:
 
     def poll(self):
         """Hook-free mode: launch every not-yet-launched bucket (in order) whose parameters all have their gradient."""
-        if self.use_hooks or self._buckets is None:
+        if self.use_hooks or self._buckets is None or self._held:
             return
         while self._next < len(self._buckets):
             b = self._buckets[self._next]
@@ -293,8 +312,15 @@ class Bf16GradSync:
         return timed("grad_sync_exposed", self._finish)
 
     def _finish(self):
+        if self._held:
+            raise RuntimeError("Bf16GradSync.finish() inside hold(): leave the hold first (the gradients are final only then)")
         if self._buckets is not None:      # how many buckets had already left when backward returned (the rest is exposed)
             self.stats["launched_during_backward"] = self.stats["collectives_last_step"]
+        if self.use_hooks and self._was_held and self._buckets is not None:
+            for b in self._buckets:        # hook mode after a hold: the hooks launched nothing, every bucket leaves here
+                if b.work is None:
+                    self._launch(b)
+        self._was_held = False
         if not self.use_hooks:
             self.poll()
             if self._next < len(self._buckets):

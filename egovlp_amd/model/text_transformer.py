@@ -80,7 +80,8 @@ class _TextLayerFn(torch.autograd.Function):
         wc = ec.wc
         dev = x.device
         x2 = x.contiguous().view(M, D)
-        train = any(ctx.needs_input_grad)
+        save = any(ctx.needs_input_grad)
+        train = ec.forward_is_train(ctx)
 
         def W(p):
             return wc.get(p, need_t=False)[0]
@@ -106,7 +107,7 @@ class _TextLayerFn(torch.autograd.Function):
         else:
             ops.gemm_nt(h, W(f2_w), passes=P, bias=f2_b, residual=sa, out_f32=s2, ec=ec)
         _, out, mean2, rstd2, _ = ops.layernorm_fwd(s2, ln2_w, ln2_b, eps, P, want_f32=True, want_planes=False)
-        if train:
+        if save:
             ctx.geom, ctx.ec, ctx.P = geom, ec, P
             ctx.planes = (x_pl, c_pl, sa_pl, h)
             ctx.save_for_backward(mask, qkv, lse, s1, mean1, rstd1, z, s2, mean2, rstd2,
@@ -229,7 +230,8 @@ class _TextLayerCFn(torch.autograd.Function):
         dev = x.device
         x2 = x.contiguous().view(M, D)
         mask = mask.contiguous()
-        train = any(ctx.needs_input_grad)
+        save = any(ctx.needs_input_grad)
+        train = ec.forward_is_train(ctx)
         g, ks = _text_geom(B, L, H, D, Hd, P, Pb, train, eps, drop, ec)
         key = (B, L, H, D, Hd, P, Pb, train, drop[2] > 0, ks)
         ent = _TEXT_CACHE.get(key)
@@ -247,7 +249,7 @@ class _TextLayerCFn(torch.autograd.Function):
         prm = _text_params(ec.wc, ln, (q_w, k_w, v_w), (q_b, k_b, v_b), (o_w, f1_w, f2_w), (o_b, f1_b, f2_b), need_t=False)
         _lib.check(_lib.lib().egv_text_layer_fwd(C.byref(g), C.byref(prm), x2.data_ptr(), mask.data_ptr(), out.data_ptr(),
                                                  arena.data_ptr(), ops._stream(x2)), "egv_text_layer_fwd")
-        if train:
+        if save:
             ctx.g, ctx.ec, ctx.arena, ctx.sizes, ctx.P = g, ec, arena, ent, P
             ctx.seed_dev = drop[4]           # keeps the device seed word alive (the geometry holds its address)
             ctx.save_for_backward(mask, q_w, k_w, v_w, q_b, k_b, v_b, o_w, f1_w, f2_w, o_b, f1_b, f2_b, *ln)

@@ -136,7 +136,8 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         wc = ec.wc
         dev = x.device
         x2 = x.contiguous().view(M, D)
-        train = any(ctx.needs_input_grad)   # grad mode is off inside Function.forward; this is the reliable signal
+        save = any(ctx.needs_input_grad)    # grad mode is off inside Function.forward; this is the reliable signal
+        train = ec.forward_is_train(ctx)    # = save, or the train-mode kernels were asked for under no_grad (the embedding-cache step)
         Hd = fc1_w.shape[0]
         # 'f16x2': the LayerNorm -> qkv / fc1 and fc1 -> fc2 hand-overs are in the f16x2 operand format (two fp16 products instead of
         # three bf16 ones, big-tile kernel only); attention and the proj Linears keep split-bf16 three-product operands (Pa).  Token
@@ -190,7 +191,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
         ops.gemm_nt(h, W(fc2_w, wf), passes=P_fc2, bias=fc2_b, residual=sr, out_f32=out, ec=ec)
 
-        if train:
+        if save:
             ctx.geom, ctx.ec, ctx.P, ctx.h16 = geom, ec, P, h16
             ctx.planes = (n3, a_t, n1, a_s, n2, h, qkv_t, qkv_s)
             ctx.save_for_backward(x2, mean3, rstd3, lse_t, tr, mean1, rstd1, lse_s, sr, mean2, rstd2, z,
@@ -329,7 +330,8 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         single = (geom[5] if len(geom) > 5 else 0) if P == 2 else 0     # ops.F16_SINGLE_BITS of this block
         dev = x.device
         x2 = x.contiguous().view(M, D)
-        train = any(ctx.needs_input_grad)
+        save = any(ctx.needs_input_grad)
+        train = ec.forward_is_train(ctx)
         z_bf16 = Pb in (1, 4) and ops.uses_big_gemm(M, Hd, D, P)      # fc1 saves gelu' in 16 bits (bf16; fp16 for the fp16 backward)
         key = (B, T, n, H, D, Hd, P, Pb, train, z_bf16, single)
         g = _block_geom(*key, eps, ec.gemm_grid)
@@ -349,7 +351,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         prm = _block_params(ec.wc, ln, biases, weights, need_t=False, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4)
         _lib.check(_lib.lib().egv_block_fwd(C.byref(g), C.byref(prm), x2.data_ptr(), out.data_ptr(), arena.data_ptr(), ops._stream(x2)),
                    "egv_block_fwd")
-        if train:
+        if save:
             ctx.key, ctx.eps, ctx.ec, ctx.arena, ctx.sizes = key, eps, ec, arena, ent
             ctx.save_for_backward(x2, *ln, *biases, *weights)
         return out.view(B, S, D)

@@ -10,6 +10,7 @@ MFMA), `passes` = 1 uses hi only (plain bf16).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import time
@@ -131,6 +132,26 @@ class ExecContext:
         self._wc = None
         self._scaler = None
         self._pol_cache = {}
+        self._train_kernels = False                     # see train_kernels_without_grad
+
+    @contextlib.contextmanager
+    def train_kernels_without_grad(self):
+        """Inside: a forward under `torch.no_grad()` runs the very kernels, geometry and precision choices of a forward that will be
+        back-propagated (the autograd functions read `forward_is_train`), and still saves nothing -- the first pass of the
+        embedding-cache step (egovlp_amd/trainer/cached_step.py), whose embeddings must be the ones its second, differentiated pass
+        computes again."""
+        prev, self._train_kernels = self._train_kernels, True
+        try:
+            yield self
+        finally:
+            self._train_kernels = prev
+
+    def forward_is_train(self, ctx):
+        """What the `train` flag of a block / layer forward is: some input needs a gradient (grad mode is off inside
+        Function.forward, `ctx.needs_input_grad` is the reliable signal -- it follows requires_grad, so trainable parameters set it
+        under no_grad as well), or the caller asked for the train-mode kernels anyway (a block of frozen parameters is train only
+        when its INPUT carries a gradient, which it does not under no_grad)."""
+        return self._train_kernels or any(ctx.needs_input_grad)
 
     # ---- settings (inherited) ------------------------------------------------------------------------------------------
     def get(self, key):
@@ -1183,6 +1204,25 @@ def grad_nonfinite_multi(grads, state):
     G = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
     N = (C.c_int64 * n)(*[g.numel() for g in grads])
     check(_lib.lib().egv_grad_nonfinite_multi(n, G, N, _p(state), _stream(grads[0])), "egv_grad_nonfinite_multi")
+
+
+def grad_accumulate_multi(dst_list, src_list):
+    """dst[i] += src[i] in fp32 for every pair of the two lists, in ONE egv_grad_accumulate_multi call (the chunk gradients of the
+    embedding-cache step; autograd's own accumulation would issue one ATen add per parameter).  Tensors are dense contiguous fp32 of
+    equal sizes; views at any 4-byte offset are fine (pairs that are not 16-byte aligned take the kernel's scalar path)."""
+    n = len(dst_list)
+    if n != len(src_list):
+        raise ValueError("grad_accumulate_multi: as many sources as destinations")
+    if n == 0:
+        return
+    for d, s in zip(dst_list, src_list):
+        if d.dtype != torch.float32 or s.dtype != torch.float32 or d.numel() != s.numel() or not (d.is_contiguous() and s.is_contiguous()):
+            raise ValueError("grad_accumulate_multi: pairs of dense contiguous fp32 tensors of equal size")
+    _need_cuda(*dst_list, *src_list)
+    D = (C.c_void_p * n)(*[d.data_ptr() for d in dst_list])
+    S = (C.c_void_p * n)(*[s.data_ptr() for s in src_list])
+    N = (C.c_int64 * n)(*[d.numel() for d in dst_list])
+    check(_lib.lib().egv_grad_accumulate_multi(n, D, S, N, _stream(dst_list[0])), "egv_grad_accumulate_multi")
 
 
 def loss_scale_update(state, hyper_out, lr, beta1, beta2, step, correct_bias, growth, backoff, interval, max_scale, advance):

@@ -37,6 +37,25 @@ def step_epilogue(loss, ec, optimizer, grad_sync, scaler):
     return loss.detach()
 
 
+def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fused_head=True):
+    """Similarity + loss of the EgoClip step on the (gathered) global batch, trainer/trainer_egoclip.py:130-137 -- shared by
+    `egoclip_step` and `egoclip_step_cached`."""
+    from ..model.model import sim_matrix
+    is_ego = type(loss_fn).__name__ == 'EgoNCE'
+    n, D = text_embeds.shape
+    # the one-launch head covers global batches up to 1024 rows of <= 256 features (8 x 128 per GPU); beyond that the
+    # API-compatible sim_matrix + loss.forward path takes over (n <= 4096)
+    if fused_head and hasattr(loss_fn, 'fused') and n <= 1024 and D <= 256 and D % 4 == 0:
+        return loss_fn.fused(text_embeds, video_embeds, n_embeds, v_embeds) if is_ego \
+            else loss_fn.fused(text_embeds, video_embeds)
+    output = sim_matrix(text_embeds, video_embeds)                          # :130
+    if is_ego:
+        sim_v = sim_matrix(v_embeds, v_embeds)                              # :133
+        sim_n = sim_matrix(n_embeds, n_embeds)                              # :134
+        return loss_fn(output, sim_v, sim_n)                                # :135
+    return loss_fn(output)
+
+
 def _to_device_async(data, device, stream):
     """Host batch -> device on `stream`: tensors go through pinned staging copies (a pageable source makes the copy synchronous);
     -> (device batch, event of the last copy).  Keys that are not tensors are passed through."""
@@ -144,6 +163,11 @@ class TrainerBase(Multi_BaseTrainer_dist):
         """The optimisation step of one device batch -> its (device) loss."""
         raise NotImplementedError
 
+    def _guard_batch(self, data):
+        """What the precision guard measures the policy on: the device batch (a trainer whose step runs the batch in pieces hands
+        over one piece)."""
+        return data
+
     def _train_epoch(self, epoch):
         self.model.train()
         total_loss = [torch.zeros((), device=self.device) for _ in self.data_loader]
@@ -162,7 +186,7 @@ class TrainerBase(Multi_BaseTrainer_dist):
             if self._guard is None:
                 from ..guard import PrecisionGuard
                 self._guard = PrecisionGuard(self.model, interval=int(getattr(self.args, 'precision_guard_interval', 1000)))
-            self._guard.maybe_check(data)
+            self._guard.maybe_check(self._guard_batch(data))
             loss = self._step(data)
             total_loss[dl_idx] += loss      # stays on the device: no per-step .item() sync (reference :148,150)
             if self.writer is not None and self.args.rank == 0 and batch_idx % self.log_step == 0:

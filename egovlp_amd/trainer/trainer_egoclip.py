@@ -13,7 +13,8 @@ from ..gather import AllGather_multi  # noqa: F401  (re-exported, as the referen
 from ..gather import AllGatherFused, _gather_rows, _world
 from ..model.model import sim_matrix
 from .common import _prefetched  # noqa: F401  (re-exported: the feed of the epoch loop, timed on its own by bench.py)
-from .common import TrainerBase, step_epilogue, step_prologue
+from .cached_step import egoclip_step_cached  # noqa: F401  (re-exported: the same step over a batch larger than memory)
+from .common import TrainerBase, egoclip_head_loss, step_epilogue, step_prologue
 
 
 def _pad_tokens(text, multiple):
@@ -37,21 +38,7 @@ def egoclip_step(model, loss_fn, optimizer, data, world_size=1, rank=0, fused_he
     n_embeds, v_embeds = data['noun_vec'], data['verb_vec']
     video_embeds, text_embeds, n_embeds, v_embeds = AllGatherFused.apply(
         video_embeds, text_embeds, n_embeds, v_embeds, world_size, rank)
-    is_ego = type(loss_fn).__name__ == 'EgoNCE'
-    n, D = text_embeds.shape
-    # the one-launch head covers global batches up to 1024 rows of <= 256 features (8 x 128 per GPU); beyond that the
-    # API-compatible sim_matrix + loss.forward path takes over (n <= 4096)
-    if fused_head and hasattr(loss_fn, 'fused') and n <= 1024 and D <= 256 and D % 4 == 0:
-        loss = loss_fn.fused(text_embeds, video_embeds, n_embeds, v_embeds) if is_ego \
-            else loss_fn.fused(text_embeds, video_embeds)
-    else:
-        output = sim_matrix(text_embeds, video_embeds)                      # :130
-        if is_ego:
-            sim_v = sim_matrix(v_embeds, v_embeds)                          # :133
-            sim_n = sim_matrix(n_embeds, n_embeds)                          # :134
-            loss = loss_fn(output, sim_v, sim_n)                            # :135
-        else:
-            loss = loss_fn(output)
+    loss = egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fused_head)   # :130-137
     return step_epilogue(loss, ec, optimizer, grad_sync, scaler)            # :139-141
 
 
@@ -70,7 +57,20 @@ class Multi_Trainer_dist(TrainerBase):
                 data.pop(k, None)        # concatenated above: not staged / copied to the device a second time
         return super()._host_batch(data)
 
+    def _embed_cache_chunk(self):
+        """`args.embed_cache_chunk` > 0: the step re-encodes its batch in chunks of that many rows (egoclip_step_cached) -- the
+        contrastive batch is then no longer bounded by the activations that fit in memory."""
+        return int(getattr(self.args, 'embed_cache_chunk', 0) or 0)
+
+    def _guard_batch(self, data):
+        chunk = self._embed_cache_chunk()
+        return {'video': data['video'][:chunk]} if chunk > 0 else data       # the guard's forwards must fit where a chunk fits
+
     def _step(self, data):
+        chunk = self._embed_cache_chunk()
+        if chunk > 0:
+            return egoclip_step_cached(self.model, self.loss, self.optimizer, data, chunk, self.n_gpu, self.args.rank,
+                                       grad_sync=self.grad_sync, fused_head=self.fused_head)
         return egoclip_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank,
                             fused_head=self.fused_head, grad_sync=self.grad_sync)
 

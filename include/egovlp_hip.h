@@ -515,6 +515,15 @@ int egv_adamw_multi(int32_t count, float* const* p, const float* const* g, float
                     egv_bf16* const* w_hi, egv_bf16* const* w_lo, const int64_t* numel,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
                     int32_t correct_bias, float grad_scale, const float* hyper_dev, void* stream);
+/* Gradient accumulation of the embedding-cache step (egovlp_amd/trainer/cached_step.py; no counterpart in the reference, whose
+ * trainer/trainer_egoclip.py:123-141 runs one backward per step): dst[i][j] += src[i][j] in fp32 for `count` tensors given as HOST
+ * arrays of device pointers / sizes, as above.  One call for the whole model (the table is copied into kernel arguments 120 tensors at
+ * a time); 16-byte accesses where both bases of a pair are 16-byte aligned, scalar otherwise and for the last numel % 4 elements;
+ * every element has one writer, so the result does not depend on the grid.  count == 0 enqueues nothing; a negative size, a NULL
+ * pointer of a non-empty tensor or a pair whose ranges overlap (dst == src included: harmless, but never meant) is an invalid
+ * argument (nothing enqueued).  An inf / NaN in either
+ * operand survives the sum, so egv_grad_nonfinite_multi on the accumulators sees the overflow of any chunk.                       */
+int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* const* src, const int64_t* numel, void* stream);
 
 /* ---- dynamic loss scale (the fp16 backward) ---------------------------------------------------------------
  * The reference back-propagates in fp32 (trainer/trainer_egoclip.py:139-141); here the backward GEMMs of the video blocks can run on
