@@ -43,7 +43,7 @@ class Multi_BaseTrainer_dist:
         # this trainer owns every gradient hook of the run (Bf16GradSync joins the streams): weight gradients may go to the
         # side stream (egovlp_amd.ops.side_stream); EGV_WGRAD_SIDE=0 keeps them on the main stream
         # (safe with one backward per step and zero_grad(set_to_none=True), which egoclip_step does; a wgrad whose parameter
-        # already holds a gradient stays on the main stream by itself -- model/video_transformer.py::_lin_bwd).
+        # already holds a gradient stays on the main stream by itself -- model/layer_common.py::_lin_bwd).
         # Settings go to the MODEL's execution context: nothing here is process-wide.
         from .. import ops
         ec = getattr(self.model, "exec_ctx", None) or ops.DEFAULT

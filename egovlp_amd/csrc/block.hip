@@ -6,22 +6,9 @@
 // bit-identical (tests/test_gpu_block.py).  The layout of the two arenas is a pure function of the geometry (egv_block_layout).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
-#include "egovlp_hip.h"
+#include "layer_call.h"
 
 namespace {
-
-constexpr int64_t ALIGN = 256;
-inline int64_t up(int64_t b) { return (b + ALIGN - 1) / ALIGN * ALIGN; }
-
-struct Bump {
-  int64_t off = 0;
-  int64_t take(int64_t bytes) {
-    const int64_t o = off;
-    off += up(bytes);
-    return o;
-  }
-};
 
 // forward arena: what the block's kernels hand to each other and what the backward needs again
 struct FwdLayout {
@@ -154,29 +141,6 @@ BwdLayout bwd_layout(const egv_block_geom& g, const int32_t* ksplit) {
   L.total = b.off;
   return L;
 }
-
-template <class T>
-T* at(void* base, int64_t off) { return off < 0 ? nullptr : (T*)((char*)base + off); }
-template <class T>
-const T* at(const void* base, int64_t off) { return off < 0 ? nullptr : (const T*)((const char*)base + off); }
-
-egv_gemm_desc nt_desc(const egv_bf16* a_hi, const egv_bf16* a_lo, int64_t lda, const egv_bf16* b_hi, const egv_bf16* b_lo, int64_t ldb,
-                      int64_t M, int64_t N, int64_t K, int passes, int grid_cap) {
-  egv_gemm_desc d = {};
-  d.a_hi = a_hi; d.a_lo = a_lo; d.lda = lda;
-  d.b_hi = b_hi; d.b_lo = b_lo; d.ldb = ldb;
-  d.M = (int32_t)M; d.N = (int32_t)N; d.K = (int32_t)K; d.passes = passes;
-  d.alpha = 1.0f;
-  d.ksplit = 1;
-  d.grid_cap = grid_cap;
-  return d;
-}
-
-#define EGV_TRY(call)            \
-  do {                           \
-    const int rc__ = (call);     \
-    if (rc__ != EGV_OK) return rc__; \
-  } while (0)
 
 }  // namespace
 
@@ -320,15 +284,16 @@ extern "C" int egv_block_bwd(const egv_block_geom* gp, const egv_block_params* p
   const char* FA = (const char*)io.fwd_arena;
   char* A = (char*)io.bwd_arena;
   hipStream_t main_s = (hipStream_t)stream;
-  auto fpl = [&](int64_t hi, int64_t lo, const egv_bf16*& ph, const egv_bf16*& pl) {
-    ph = at<egv_bf16>(FA, hi);
-    pl = Pb == 3 ? at<egv_bf16>(FA, lo) : nullptr;
-  };
   const bool x2 = o.P == 2 && !h16;      // f16x2 forward, bf16 backward: the activations' single-pass operands are their bf16 copies
   const egv_bf16 *n3_hi, *n3_lo, *at_hi, *at_lo, *n1_hi, *n1_lo, *as_hi, *as_lo, *n2_hi, *n2_lo, *h_hi, *h_lo, *qt_hi, *qt_lo, *qs_hi, *qs_lo;
-  fpl(x2 ? F.n3_bf : F.n3_hi, F.n3_lo, n3_hi, n3_lo); fpl(F.at_hi, F.at_lo, at_hi, at_lo); fpl(x2 ? F.n1_bf : F.n1_hi, F.n1_lo, n1_hi, n1_lo);
-  fpl(F.as_hi, F.as_lo, as_hi, as_lo); fpl(x2 ? F.n2_bf : F.n2_hi, F.n2_lo, n2_hi, n2_lo); fpl(x2 ? F.h_bf : F.h_hi, F.h_lo, h_hi, h_lo);
-  fpl(F.qkvt_hi, F.qkvt_lo, qt_hi, qt_lo); fpl(F.qkvs_hi, F.qkvs_lo, qs_hi, qs_lo);
+  saved_planes(FA, Pb, x2 ? F.n3_bf : F.n3_hi, F.n3_lo, n3_hi, n3_lo);
+  saved_planes(FA, Pb, F.at_hi, F.at_lo, at_hi, at_lo);
+  saved_planes(FA, Pb, x2 ? F.n1_bf : F.n1_hi, F.n1_lo, n1_hi, n1_lo);
+  saved_planes(FA, Pb, F.as_hi, F.as_lo, as_hi, as_lo);
+  saved_planes(FA, Pb, x2 ? F.n2_bf : F.n2_hi, F.n2_lo, n2_hi, n2_lo);
+  saved_planes(FA, Pb, x2 ? F.h_bf : F.h_hi, F.h_lo, h_hi, h_lo);
+  saved_planes(FA, Pb, F.qkvt_hi, F.qkvt_lo, qt_hi, qt_lo);
+  saved_planes(FA, Pb, F.qkvs_hi, F.qkvs_lo, qs_hi, qs_lo);
   // the attention backward takes the forward output's lo plane whenever the forward wrote one, also in a single-pass backward
   // (delta = rowsum(dO o O) exact in O: egv_divided_attn_bwd)
   // (not when that plane holds fp16(value) for a single-product proj, egv_block_geom.f16_single bit 3: delta then comes from the bf16 plane)
@@ -362,17 +327,9 @@ extern "C" int egv_block_bwd(const egv_block_geom* gp, const egv_block_params* p
       if (hipEventRecord((hipEvent_t)io.side_event[i], main_s) != hipSuccess) return EGV_ERR_LAUNCH;
       if (hipStreamWaitEvent(s, (hipEvent_t)io.side_event[i], 0) != hipSuccess) return EGV_ERR_LAUNCH;
     }
-    egv_gemm_desc d = {};
-    d.a_hi = dy_hi; d.a_lo = dy_lo; d.lda = lddy;
-    d.b_hi = x_hi; d.b_lo = x_lo; d.ldb = ldx;
-    d.M = (int32_t)N; d.N = (int32_t)K; d.K = M; d.passes = Pg;
+    egv_gemm_desc d = tn_desc(dy_hi, dy_lo, lddy, x_hi, x_lo, ldx, N, K, M, Pg, grads + goff[i], grads + goff[6 + i], io.wgrad_ksplit[i],
+                              at<float>(A, L.partial[i]), g.grid_cap);
     d.alpha = walpha[i];
-    d.out_f32 = grads + goff[i]; d.ldo = K;
-    d.ksplit = io.wgrad_ksplit[i] > 1 ? io.wgrad_ksplit[i] : 1;
-    d.partial = at<float>(A, L.partial[i]);
-    d.trans = 1;
-    d.colsum = grads + goff[6 + i];
-    d.grid_cap = g.grid_cap;
     if (defer_reduce && d.ksplit > 1) d.accumulate = 2;        // slabs only; reduced below
     return egv_gemm_nt(&d, s);
   };

@@ -1,0 +1,64 @@
+// Host-side scaffolding of the one-C-call-per-layer entry points (block.hip: egv_block_fwd / _bwd, text_layer.hip: egv_text_layer_fwd /
+// _bwd): the workspace-arena allocator, pointers into an arena, the early return on a failed launch, and the GEMM descriptors every
+// such call fills the same way.  Internal to csrc/; no device code.
+#pragma once
+#include <stdint.h>
+
+#include "common.h"
+#include "egovlp_hip.h"
+
+// bump allocator over one arena: byte offsets, every allocation 256-byte aligned
+struct Bump {
+  static constexpr int64_t ALIGN = 256;
+  int64_t off = 0;
+  int64_t take(int64_t bytes) {
+    const int64_t o = off;
+    off += (bytes + ALIGN - 1) / ALIGN * ALIGN;
+    return o;
+  }
+};
+
+// arena base + byte offset (-1: absent -> null)
+template <class T>
+T* at(void* base, int64_t off) { return off < 0 ? nullptr : (T*)((char*)base + off); }
+template <class T>
+const T* at(const void* base, int64_t off) { return off < 0 ? nullptr : (const T*)((const char*)base + off); }
+
+#define EGV_TRY(call)                \
+  do {                               \
+    const int rc__ = (call);         \
+    if (rc__ != EGV_OK) return rc__; \
+  } while (0)
+
+// an operand the forward saved in its arena, as the backward reads it: the hi plane, the lo plane only in a three-product backward
+static inline void saved_planes(const void* fwd_arena, int bwd_passes, int64_t hi, int64_t lo, const egv_bf16*& ph, const egv_bf16*& pl) {
+  ph = at<egv_bf16>(fwd_arena, hi);
+  pl = bwd_passes == 3 ? at<egv_bf16>(fwd_arena, lo) : nullptr;
+}
+
+// C[M,N] = A[M,K] . B[N,K]^T (forward Linears, dgrads); the caller adds the epilogue fields
+static inline egv_gemm_desc nt_desc(const egv_bf16* a_hi, const egv_bf16* a_lo, int64_t lda, const egv_bf16* b_hi, const egv_bf16* b_lo,
+                                    int64_t ldb, int64_t M, int64_t N, int64_t K, int passes, int grid_cap, int ksplit = 1,
+                                    float* partial = nullptr) {
+  egv_gemm_desc d = {};
+  d.a_hi = a_hi; d.a_lo = a_lo; d.lda = lda;
+  d.b_hi = b_hi; d.b_lo = b_lo; d.ldb = ldb;
+  d.M = (int32_t)M; d.N = (int32_t)N; d.K = (int32_t)K; d.passes = passes;
+  d.alpha = 1.0f;
+  d.ksplit = ksplit;
+  d.partial = ksplit > 1 ? partial : nullptr;
+  d.grid_cap = grid_cap;
+  return d;
+}
+
+// the weight gradient dW[N,K] = dY[M,N]^T X[M,K] (TN kernel), the bias gradient (column sums of dY) from the same pass; the caller
+// sets alpha / accumulate where they differ from 1 / 0 and chooses the stream
+static inline egv_gemm_desc tn_desc(const egv_bf16* dy_hi, const egv_bf16* dy_lo, int64_t lddy, const egv_bf16* x_hi, const egv_bf16* x_lo,
+                                    int64_t ldx, int64_t N, int64_t K, int64_t M, int passes, float* out, float* colsum, int ksplit,
+                                    float* partial, int grid_cap) {
+  egv_gemm_desc d = nt_desc(dy_hi, dy_lo, lddy, x_hi, x_lo, ldx, N, K, M, passes, grid_cap, ksplit > 1 ? ksplit : 1, partial);
+  d.out_f32 = out; d.ldo = K;
+  d.trans = 1;
+  d.colsum = colsum;
+  return d;
+}

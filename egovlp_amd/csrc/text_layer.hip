@@ -6,33 +6,9 @@
 // results are bit-identical (tests/test_gpu_block.py).  Weight index: 0 = q/k/v fused [3D, D], 1 = out_lin, 2 = lin1, 3 = lin2.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
-#include "egovlp_hip.h"
+#include "layer_call.h"
 
 namespace {
-
-constexpr int64_t ALIGN = 256;
-inline int64_t up(int64_t b) { return (b + ALIGN - 1) / ALIGN * ALIGN; }
-
-struct Bump {
-  int64_t off = 0;
-  int64_t take(int64_t bytes) {
-    const int64_t o = off;
-    off += up(bytes);
-    return o;
-  }
-};
-
-template <class T>
-T* at(void* base, int64_t off) { return off < 0 ? nullptr : (T*)((char*)base + off); }
-template <class T>
-const T* at(const void* base, int64_t off) { return off < 0 ? nullptr : (const T*)((const char*)base + off); }
-
-#define EGV_TRY(call)                \
-  do {                               \
-    const int rc__ = (call);         \
-    if (rc__ != EGV_OK) return rc__; \
-  } while (0)
 
 bool geom_ok(const egv_text_geom& g) {
   if (g.B <= 0 || g.L <= 0 || g.H <= 0 || g.D != g.H * 64 || g.Hd <= 0 || g.D % 32 || g.Hd % 32) return false;
@@ -146,19 +122,6 @@ void grad_layout(const egv_text_geom& g, int64_t off[12], int64_t& total) {
   total = p;
 }
 
-egv_gemm_desc nt_desc(const egv_bf16* a_hi, const egv_bf16* a_lo, int64_t lda, const egv_bf16* b_hi, const egv_bf16* b_lo, int64_t ldb,
-                      int64_t M, int64_t N, int64_t K, int passes, int grid_cap, int ksplit, float* partial) {
-  egv_gemm_desc d = {};
-  d.a_hi = a_hi; d.a_lo = a_lo; d.lda = lda;
-  d.b_hi = b_hi; d.b_lo = b_lo; d.ldb = ldb;
-  d.M = (int32_t)M; d.N = (int32_t)N; d.K = (int32_t)K; d.passes = passes;
-  d.alpha = 1.0f;
-  d.ksplit = ksplit;
-  d.partial = ksplit > 1 ? partial : nullptr;
-  d.grid_cap = grid_cap;
-  return d;
-}
-
 }  // namespace
 
 extern "C" int64_t egv_text_layer_fwd_arena_bytes(const egv_text_geom* g) { return (g && geom_ok(*g)) ? fwd_layout(*g).total : -1; }
@@ -241,12 +204,11 @@ extern "C" int egv_text_layer_bwd(const egv_text_geom* gp, const egv_text_params
     if (!p.wt_hi[i] || (Pb == 3 && !p.wt_lo[i])) return EGV_ERR_ARG;
   const char* FA = (const char*)fwd_arena;
   char* A = (char*)bwd_arena;
-  auto fpl = [&](int64_t hi, int64_t lo, const egv_bf16*& ph, const egv_bf16*& pl) {
-    ph = at<egv_bf16>(FA, hi);
-    pl = Pb == 3 ? at<egv_bf16>(FA, lo) : nullptr;
-  };
   const egv_bf16 *x_hi, *x_lo, *c_hi, *c_lo, *sa_hi, *sa_lo, *h_hi, *h_lo;
-  fpl(F.x_hi, F.x_lo, x_hi, x_lo); fpl(F.c_hi, F.c_lo, c_hi, c_lo); fpl(F.sa_hi, F.sa_lo, sa_hi, sa_lo); fpl(F.h_hi, F.h_lo, h_hi, h_lo);
+  saved_planes(FA, Pb, F.x_hi, F.x_lo, x_hi, x_lo);
+  saved_planes(FA, Pb, F.c_hi, F.c_lo, c_hi, c_lo);
+  saved_planes(FA, Pb, F.sa_hi, F.sa_lo, sa_hi, sa_lo);
+  saved_planes(FA, Pb, F.h_hi, F.h_lo, h_hi, h_lo);
   const float *qkv = at<float>(FA, F.qkv), *s1 = at<float>(FA, F.s1), *s2 = at<float>(FA, F.s2);
   float* part = at<float>(A, L.partial);
   float* ln_work = at<float>(A, L.ln_work);
@@ -256,17 +218,8 @@ extern "C" int egv_text_layer_bwd(const egv_text_geom* gp, const egv_text_params
                    int64_t lda) -> int {
     int64_t N, K;
     wshape(g, i, N, K);
-    egv_gemm_desc d = {};
-    d.a_hi = dy_hi; d.a_lo = dy_lo; d.lda = lddy;
-    d.b_hi = a_hi; d.b_lo = a_lo; d.ldb = lda;
-    d.M = (int32_t)N; d.N = (int32_t)K; d.K = M; d.passes = Pb;
-    d.alpha = 1.0f;
-    d.out_f32 = grads + goff[i]; d.ldo = K;
-    d.ksplit = g.wgrad_ksplit[i];
-    d.partial = g.wgrad_ksplit[i] > 1 ? part : nullptr;
-    d.trans = 1;
-    d.colsum = grads + goff[4 + i];
-    d.grid_cap = g.grid_cap;
+    const egv_gemm_desc d = tn_desc(dy_hi, dy_lo, lddy, a_hi, a_lo, lda, N, K, M, Pb, grads + goff[i], grads + goff[4 + i], g.wgrad_ksplit[i],
+                                    part, g.grid_cap);       // every slab in the one shared region: the GEMMs follow each other on one stream
     return egv_gemm_nt(&d, stream);
   };
 

@@ -21,8 +21,9 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops import ACT_RELU_BWD, ExecContext
 from ..utils.util import load_checkpoint_file, state_dict_data_parallel_fix
+from .layer_common import _lin_bwd
 from .text_transformer import DistilBertModel
-from .video_transformer import SpaceTimeTransformer, _lin_bwd
+from .video_transformer import SpaceTimeTransformer
 
 
 class _ProjFn(torch.autograd.Function):

@@ -14,14 +14,16 @@ rate, the 1 / (1 - p) scaling and the forward / backward consistency.
 """
 from __future__ import annotations
 
+import ctypes as C
 from types import SimpleNamespace
 
 import torch
 from torch import nn
 
-from .. import ops
+from .. import _lib, ops
+from .._lib import TextGeom, TextParams
 from ..ops import ACT_GELU, ACT_GELU_BWD, ExecContext
-from .video_transformer import _lin_bwd
+from .layer_common import _lin_bwd, bwd_arena_bytes, grad_views, layer_sizes, need_fwd_arena, param_struct
 
 
 class DistilBertConfig:
@@ -159,9 +161,6 @@ class _TextLayerFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------- one C call per layer
-_TEXT_CACHE = {}       # geometry key -> (forward arena bytes, backward arena bytes, gradient offsets, gradient floats)
-
-
 def text_calls_ok(ec: ExecContext, M, D, Hd, H):
     """May this layer run through the C layer calls?  (split-bf16 / bf16 precision, no per-kernel timer, widths the TN kernel takes
     without an explicit transpose, and the weight gradients on the layer's own stream: the text tower on its side stream -- the
@@ -174,8 +173,6 @@ def text_calls_ok(ec: ExecContext, M, D, Hd, H):
 
 
 def _text_geom(B, L, H, D, Hd, P, Pb, train, eps, drop, ec):
-    from .._lib import TextGeom
-    import ctypes as C
     M = B * L
     I4 = C.c_int32 * 4
     ksf = I4(*[ops.auto_ksplit_nt(M, n_, k_) for n_, k_ in ((3 * D, D), (D, D), (Hd, D), (D, Hd))])
@@ -190,28 +187,10 @@ def _text_geom(B, L, H, D, Hd, P, Pb, train, eps, drop, ec):
 def _text_params(wc, ln, qkv_w, qkv_b, others_w, others_b, need_t):
     """egv_text_params: LayerNorm affine (sa_layer_norm w, b, output_layer_norm w, b), the fused q/k/v weight planes and bias (the
     weight cache keeps the concatenation), out_lin / lin1 / lin2.  Built once per layer and direction and kept on the model's weight
-    cache (see video_transformer._block_params)."""
-    import ctypes as C
-    from .._lib import TextParams
+    cache (layer_common.param_struct)."""
     pls = [wc.get_cat(qkv_w, need_t=need_t)] + [wc.get(w, need_t=need_t) for w in others_w]
     bias = [wc.get_bias_cat(qkv_b)] + list(others_b)
-    small = tuple(t.data_ptr() for t in ln) + tuple(b.data_ptr() for b in bias)
-    key = (id(qkv_w[0]), need_t)
-    hit = wc.param_structs.get(key)
-    if hit is not None and hit[1] == small and all(a[0] is b[0] and a[1] is b[1] for a, b in zip(hit[0], pls)):
-        return hit[2]
-    P4, L4 = C.c_void_p * 4, C.c_int64 * 4
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-    whi, wlo, ldw = P4(*[p.hi.data_ptr() for p, _ in pls]), P4(*[ptr(p.lo) for p, _ in pls]), L4(*[p.ld for p, _ in pls])
-    if need_t:
-        thi, tlo, ldt = P4(*[t.hi.data_ptr() for _, t in pls]), P4(*[ptr(t.lo) for _, t in pls]), L4(*[t.ld for _, t in pls])
-    else:
-        thi, tlo, ldt = P4(), P4(), L4()
-    prm = TextParams(*[t.data_ptr() for t in ln], P4(*[b.data_ptr() for b in bias]), whi, wlo, ldw, thi, tlo, ldt)
-    wc.param_structs[key] = (pls, small, prm)
-    return prm
+    return param_struct(wc, TextParams, (id(qkv_w[0]), need_t), need_t, ln, bias, pls)
 
 
 class _TextLayerCFn(torch.autograd.Function):
@@ -220,8 +199,6 @@ class _TextLayerCFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, geom, ec: ExecContext,
                 q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, ln1_w, ln1_b, f1_w, f1_b, f2_w, f2_b, ln2_w, ln2_b):
-        import ctypes as C
-        from .. import _lib
         B, L, H, eps, drop = geom
         D = x.shape[-1]
         M = B * L
@@ -234,15 +211,7 @@ class _TextLayerCFn(torch.autograd.Function):
         train = ec.forward_is_train(ctx)
         g, ks = _text_geom(B, L, H, D, Hd, P, Pb, train, eps, drop, ec)
         key = (B, L, H, D, Hd, P, Pb, train, drop[2] > 0, ks)
-        ent = _TEXT_CACHE.get(key)
-        if ent is None:
-            off, tot = (C.c_int64 * 12)(), C.c_int64()
-            nf = int(_lib.lib().egv_text_layer_fwd_arena_bytes(C.byref(g)))
-            nb = int(_lib.lib().egv_text_layer_bwd_arena_bytes(C.byref(g)))
-            _lib.check(_lib.lib().egv_text_layer_grad_layout(C.byref(g), off, C.byref(tot)), "egv_text_layer_grad_layout")
-            if nf <= 0 or nb <= 0:
-                raise _lib.EgovlpHipError("egv_text_layer_fwd_arena_bytes: unsupported layer geometry")
-            ent = _TEXT_CACHE[key] = (nf, nb, tuple(int(o) for o in off), int(tot.value))
+        ent = layer_sizes("egv_text_layer", key, g, 12)
         arena = torch.empty(ent[0], dtype=torch.uint8, device=dev)
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
         ln = (ln1_w, ln1_b, ln2_w, ln2_b)
@@ -250,37 +219,32 @@ class _TextLayerCFn(torch.autograd.Function):
         _lib.check(_lib.lib().egv_text_layer_fwd(C.byref(g), C.byref(prm), x2.data_ptr(), mask.data_ptr(), out.data_ptr(),
                                                  arena.data_ptr(), ops._stream(x2)), "egv_text_layer_fwd")
         if save:
-            ctx.g, ctx.ec, ctx.arena, ctx.sizes, ctx.P = g, ec, arena, ent, P
+            ctx.g, ctx.key, ctx.ec, ctx.arena, ctx.sizes = g, key, ec, arena, ent
             ctx.seed_dev = drop[4]           # keeps the device seed word alive (the geometry holds its address)
             ctx.save_for_backward(mask, q_w, k_w, v_w, q_b, k_b, v_b, o_w, f1_w, f2_w, o_b, f1_b, f2_b, *ln)
         return out.view(B, L, D)
 
     @staticmethod
     def backward(ctx, g_out):
-        import ctypes as C
-        from .. import _lib
         saved = ctx.saved_tensors
         mask, qkv_w, qkv_b, others_w, others_b, ln = saved[0], saved[1:4], saved[4:7], saved[7:10], saved[10:13], saved[13:17]
         g, ec = ctx.g, ctx.ec
-        if ctx.arena is None:
-            raise RuntimeError("the C layer calls release their forward workspace after the first backward: a second backward through "
-                               "the same graph (retain_graph=True) needs the per-kernel path (exec_ctx.set(block_calls=False))")
+        need_fwd_arena(ctx.arena, "layer")
         if ec.bwd_passes_split != g.bwd_passes:
             raise RuntimeError("the backward precision changed between this layer's forward and its backward")
         B, L, D = g.B, g.L, g.D
         M = B * L
         dev = mask.device
         G = g_out.contiguous().view(M, D)
-        _, nb, goff, gtot = ctx.sizes
-        barena = torch.empty(nb, dtype=torch.uint8, device=dev)
+        _, goff, gtot = ctx.sizes
+        barena = torch.empty(bwd_arena_bytes("egv_text_layer", ctx.key, g), dtype=torch.uint8, device=dev)
         grads = torch.empty(gtot, dtype=torch.float32, device=dev)
         d_x = torch.empty((M, D), dtype=torch.float32, device=dev)
         prm = _text_params(ec.wc, ln, qkv_w, qkv_b, others_w, others_b, need_t=True)
         _lib.check(_lib.lib().egv_text_layer_bwd(C.byref(g), C.byref(prm), G.data_ptr(), mask.data_ptr(), ctx.arena.data_ptr(),
                                                  barena.data_ptr(), d_x.data_ptr(), grads.data_ptr(), ops._stream(G)), "egv_text_layer_bwd")
         ctx.arena = None
-        sizes = [goff[i + 1] - goff[i] for i in range(11)] + [gtot - goff[11]]
-        parts = grads.split_with_sizes(sizes)
+        parts = grad_views(grads, goff, gtot)
         dW3 = parts[0].view(3 * D, D)
         db3 = parts[4]
         dW = [parts[i].view(others_w[i - 1].shape) for i in (1, 2, 3)]

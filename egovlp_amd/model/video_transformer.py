@@ -12,98 +12,17 @@ identical to the reference); their own forward is never called.
 """
 from __future__ import annotations
 
+import ctypes as C
 from functools import partial
-
 
 import torch
 from torch import nn
 
-from .. import ops
-from ..ops import ACT_GELU, ACT_GELU_BWD, ExecContext, Planes
-
-
-# The dgrad GEMMs that feed LayerNorm-backward write fp32: handing dy over as bf16 planes instead halves those bytes but measured
-# 0.5 ms/step SLOWER in round 2 and within noise in round 3 (the split epilogue's VALU work and 8-byte stores / loads cost what the
-# bytes save; profiles/r03_stream_ab.txt) -- the switch is gone, egv_layernorm_bwd still accepts planes (tests).
-
-
-def _lin_bwd(dy, x_pl: Planes, wt: Planes, Pb, need_dx=True, dx_planes=False, params=(), ec: ExecContext = None, allow_side=True):
-    """Backward of y = x W^T + b.  `dy` is fp32 [M,N] (split to bf16 planes here, one pass, no transpose) or
-    already-split row-major Planes.  The SAME row-major planes feed both gradients: dgrad contracts over N
-    (dy . W, weights cached transposed) and wgrad contracts over the M token rows with the TN kernel
-    (dy^T x via the CDNA4 transpose read, bias gradient from the same pass).
-    `params`: the parameters (weight, bias) the returned dW / db will be accumulated into by autograd; `ec`: the model's
-    execution context (side stream, grid cap); `allow_side=False`: the caller reads dW / db right away on ITS stream (slices of a
-    padded head), so the weight gradient stays on the current stream.
-    -> (dx fp32 [M,K] | None, dW fp32 [N,K], db [N])."""
-    ec = ops.DEFAULT if ec is None else ec
-    alpha = 1.0
-    if Pb == 4:
-        # the fp16 backward: dy = ONE plane of un-clamped fp16 (a scaled gradient), X = plane 1 of the forward's own fp16 operand (the
-        # weight gradient is rescaled when that plane is a1 = fp16((1 - 2^-6) x) of an f16x2 encoding), W^T an fp16 plane
-        if not isinstance(dy, Planes):
-            dy = ops.f16_cast(dy)
-        x_pl, alpha = x_pl.bwd16()
-    else:
-        if not isinstance(dy, Planes):
-            dy = ops.split_f32(dy, Pb)[0]
-        x_pl = x_pl.bwd()              # an f16x2 forward operand hands over its bf16 plane
-    M, K = x_pl.rows, x_pl.cols
-    N = dy.cols
-    dev = x_pl.hi.device
-    # off the critical path: fills the CUs the dgrad chain leaves idle (ops.side_stream); the text tower's own backward is
-    # already off the video tower's stream (ops.TEXT_SIDE_STREAM) and keeps its small wgrads where they are.
-    # The side stream is only safe while autograd's AccumulateGrad STEALS dW (parameter.grad is None: zero_grad(set_to_none=True),
-    # one backward per step): with a gradient already in place it enqueues `grad += dW` on the node's stream, which is not
-    # ordered behind the side stream -- such wgrads (gradient accumulation, set_to_none=False) stay on the main stream.
-    accumulating = any(p_ is not None and p_.grad is not None for p_ in params)
-    if allow_side and ec.wgrad_side_stream and not ec.on_text_stream() and not accumulating:
-        with ec.side_stream(dy.hi, dy.lo, x_pl.hi, x_pl.lo, cost=float(M) * N * K):
-            dW = torch.empty((N, K), dtype=torch.float32, device=dev)
-            db = ops.gemm_tn(dy, x_pl, passes=Pb, out_f32=dW, want_colsum=True, ec=ec, alpha=alpha)
-    else:
-        dW = torch.empty((N, K), dtype=torch.float32, device=dev)
-        db = ops.gemm_tn(dy, x_pl, passes=Pb, out_f32=dW, want_colsum=True, ec=ec, alpha=alpha)
-    dx = None
-    if need_dx and dx_planes:      # dx feeds a kernel that consumes planes (attention backward): no fp32 copy at all
-        if Pb == 4:                # dO of the fp16 attention backward: one plane of un-clamped fp16
-            dx = ops.empty_planes_f16x2(M, K, dev, single=True)
-            ops.gemm_nt(dy, wt, passes=4, out_planes=dx, K=N, ec=ec, grad_out=True)
-        else:
-            dx = ops.empty_planes(M, K, Pb, dev)
-            ops.gemm_nt(dy, wt, passes=Pb, out_planes=dx, K=N, ec=ec)
-    elif need_dx:
-        dx = torch.empty((M, K), dtype=torch.float32, device=dev)
-        ops.gemm_nt(dy, wt, passes=Pb, out_f32=dx, K=N, ec=ec)
-    return dx, dW, db
-
-
-# Gradient hand-off between consecutive blocks' backward passes: the LayerNorm-backward kernel that produces a block's
-# input gradient d_x also emits it as split-bf16 planes (the format the previous block's GEMMs consume).  autograd only
-# carries the fp32 tensor, so the planes ride along ON that tensor object (`_egv_planes`: PyTorch preserves a tensor's Python
-# object, attributes included, across the engine), stamped with the tensor's version counter.  Anything that replaces the
-# tensor (gradient accumulation from a second consumer, hooks that return a new tensor) drops the attribute; anything that
-# modifies it in place bumps the version -- either way the consumer falls back to one egv_split_f32 pass of the real values.
-PLANE_HANDOFF = {"hit": 0, "miss": 0}     # diagnostics / tests
-
-
-def _attach_grad_planes(g, Pb, planes):
-    g._egv_planes = (Pb, planes, g._version)
-    return g
-
-
-def _take_grad_planes(g_out, g2d, Pb):
-    ent = getattr(g_out, "_egv_planes", None)
-    if ent is not None:
-        try:
-            del g_out._egv_planes
-        except AttributeError:
-            pass
-        if ent[0] == Pb and ent[2] == g_out._version and ent[1].rows == g2d.shape[0] and ent[1].cols == g2d.shape[1]:
-            PLANE_HANDOFF["hit"] += 1
-            return ent[1]
-    PLANE_HANDOFF["miss"] += 1
-    return ops.f16_cast(g2d) if Pb == 4 else ops.split_f32(g2d, Pb)[0]
+from .. import _lib, ops
+from .._lib import BlockBwdIO, BlockGeom, BlockParams
+from ..ops import ACT_GELU, ACT_GELU_BWD, ExecContext
+from .layer_common import (PLANE_HANDOFF, _attach_grad_planes, _lin_bwd, _take_grad_planes, bwd_arena_bytes,  # noqa: F401  (PLANE_HANDOFF: tests)
+                           gelu_grad_16bit, grad_views, layer_sizes, need_fwd_arena, param_struct)
 
 
 def f16x2_block_ok(M, D, Hd, train):
@@ -184,7 +103,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         # anyway, gelu'(z) itself as bf16 -- the epilogue has Phi(z) and phi(z) in registers, the buffer is half the bytes,
         # and the fc2-dgrad epilogue becomes one multiply instead of a second erf evaluation over 77 M elements
         # (the fp16 backward keeps gelu' as fp16: bf16's 2^-9 on the derivative would cap dZ's accuracy)
-        z_dtype = torch.float16 if h16 else (torch.bfloat16 if (ec.bwd_passes in (1, 4) and ops.uses_big_gemm(M, Hd, D, P)) else torch.float32)
+        z_dtype = torch.float16 if h16 else (torch.bfloat16 if gelu_grad_16bit(ec, M, Hd, D, P) else torch.float32)
         z = torch.empty((M, Hd), dtype=z_dtype, device=dev) if train else None
         ops.gemm_nt(n2, W(fc1_w, wf), passes=P_fc1, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h,
                     aux_is_grad=z is not None and z_dtype != torch.float32, ec=ec)
@@ -224,7 +143,9 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
             return wc.get(p, need_t=True)[1]
 
         # ---- MLP backward.  dZ = (G . W2) * gelu'(z) comes out of the fc2-dgrad epilogue already split.
-        G_pl = _take_grad_planes(g_out, G, Pb)
+        G_pl = _take_grad_planes(g_out, M, D, Pb)
+        if G_pl is None:
+            G_pl = ops.f16_cast(G) if h16 else ops.split_f32(G, Pb)[0]
         Hd = fc1_w.shape[0]
         dZ = ops.empty_planes_f16x2(M, Hd, G.device, single=True) if h16 else ops.empty_planes(M, Hd, Pb, G.device)
         ops.gemm_nt(G_pl, Wt(fc2_w), passes=Pb, act=ACT_GELU_BWD, aux_in=z, out_planes=dZ, K=D,
@@ -257,9 +178,6 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
 # The same block through egv_block_fwd / egv_block_bwd (csrc/block.hip): the C side enqueues the block's kernels with pointers into
 # one workspace arena per direction.  What stays in Python is policy: which precision, which stream each weight gradient goes to,
 # how many k-slices it gets, the gradient-plane hand-over between blocks, the backward poll of the gradient exchange.
-_BLOCK_CACHE = {}      # geometry -> (forward arena bytes, gradient offsets, gradient floats)
-_BLOCK_BWD_BYTES = {}  # (geometry, k-slices) -> backward arena bytes
-_W_ORDER = ("tqkv", "tproj", "sqkv", "sproj", "fc1", "fc2")
 
 
 def block_calls_ok(ec: ExecContext, M, D, Hd):
@@ -276,7 +194,6 @@ def block_calls_ok(ec: ExecContext, M, D, Hd):
 
 
 def _block_geom(B, T, n, H, D, Hd, P, Pb, train, z_bf16, single, eps, grid):
-    from .._lib import BlockGeom
     return BlockGeom(B, T, n, H, D, Hd, P, Pb, int(train), int(z_bf16), float(eps), int(grid), int(single))
 
 
@@ -285,30 +202,13 @@ _X2_FMTS = ("f16x2", "bf16", "f16x2", "bf16", "f16x2", "f16x2")     # f16x2 mode
 
 def _block_params(wc, ln, biases, weights, need_t, x2=False, proj_x2=False, t16=False):
     """egv_block_params from the parameter tensors: LayerNorm affine (n3w, n3b, n1w, n1b, n2w, n2b), the six biases and the
-    cached operand planes of the six weights (W^T planes too when `need_t`).  The planes are refreshed IN PLACE after an optimizer
-    step, so the struct stays the same from step to step: it is kept on the model's weight cache, keyed by the block's first weight
-    and the direction, and reused while the cache still holds the very same plane objects and the small parameters have not moved."""
-    import ctypes as C
-    from .._lib import BlockParams
-    P6, L6 = C.c_void_p * 6, C.c_int64 * 6
+    cached operand planes of the six weights (W^T planes too when `need_t`), kept on the model's weight cache, keyed by the block's
+    first weight, the direction and the formats (layer_common.param_struct)."""
     # proj_x2: the proj Linears run one fp16 product in this block -- their forward weights are f16x2 encodings too
     # t16 (the fp16 backward): the transposed weights are single fp16 planes (wt_lo unused)
     fmts = [("f16x2" if (proj_x2 and i in (1, 3)) else _X2_FMTS[i]) if x2 else "bf16" for i in range(6)]
     pls = [wc.get(w, need_t=need_t, fmt=fmts[i], t_fmt="f16" if t16 else "bf16") for i, w in enumerate(weights)]
-    small = tuple(t.data_ptr() for t in ln) + tuple(b.data_ptr() for b in biases)
-    key = (id(weights[0]), need_t, x2, proj_x2, t16)
-    hit = wc.param_structs.get(key)
-    if hit is not None and hit[1] == small and all(a[0] is b[0] and a[1] is b[1] for a, b in zip(hit[0], pls)):
-        return hit[2]
-    whi, wlo, ldw = P6(*[p.hi.data_ptr() for p, _ in pls]), P6(*[p.lo.data_ptr() for p, _ in pls]), L6(*[p.ld for p, _ in pls])
-    if need_t:
-        thi, tlo, ldt = P6(*[t.hi.data_ptr() for _, t in pls]), P6(*[(t.lo.data_ptr() if t.lo is not None else None) for _, t in pls]), \
-            L6(*[t.ld for _, t in pls])
-    else:
-        thi, tlo, ldt = P6(), P6(), L6()
-    prm = BlockParams(*[t.data_ptr() for t in ln], P6(*[b.data_ptr() for b in biases]), whi, wlo, ldw, thi, tlo, ldt)
-    wc.param_structs[key] = (pls, small, prm)
-    return prm
+    return param_struct(wc, BlockParams, (id(weights[0]), need_t, x2, proj_x2, t16), need_t, ln, biases, pls)
 
 
 class _SpaceTimeBlockCFn(torch.autograd.Function):
@@ -319,8 +219,6 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
                 n3w, n3b, tqkv_w, tqkv_b, tproj_w, tproj_b,
                 n1w, n1b, sqkv_w, sqkv_b, sproj_w, sproj_b,
                 n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b):
-        import ctypes as C
-        from .. import _lib
         B, T, n, H, eps = geom[:5]
         S = 1 + T * n
         D = x.shape[-1]
@@ -332,17 +230,9 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         x2 = x.contiguous().view(M, D)
         save = any(ctx.needs_input_grad)
         train = ec.forward_is_train(ctx)
-        z_bf16 = Pb in (1, 4) and ops.uses_big_gemm(M, Hd, D, P)      # fc1 saves gelu' in 16 bits (bf16; fp16 for the fp16 backward)
-        key = (B, T, n, H, D, Hd, P, Pb, train, z_bf16, single)
+        key = (B, T, n, H, D, Hd, P, Pb, train, gelu_grad_16bit(ec, M, Hd, D, P), single)
         g = _block_geom(*key, eps, ec.gemm_grid)
-        ent = _BLOCK_CACHE.get(key)
-        if ent is None:
-            off, tot = (C.c_int64 * 18)(), C.c_int64()
-            nb = int(_lib.lib().egv_block_fwd_arena_bytes(C.byref(g)))
-            _lib.check(_lib.lib().egv_block_grad_layout(C.byref(g), off, C.byref(tot)), "egv_block_grad_layout")
-            if nb <= 0:
-                raise _lib.EgovlpHipError("egv_block_fwd_arena_bytes: unsupported block geometry")
-            ent = _BLOCK_CACHE[key] = (nb, tuple(int(o) for o in off), int(tot.value))
+        ent = layer_sizes("egv_block", key, g, 18)
         arena = torch.empty(ent[0], dtype=torch.uint8, device=dev)
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
         ln = (n3w, n3b, n1w, n1b, n2w, n2b)
@@ -358,14 +248,9 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        import ctypes as C
-        from .. import _lib
-        from .._lib import BlockBwdIO
         saved = ctx.saved_tensors
         x2, ln, biases, weights = saved[0], saved[1:7], saved[7:13], saved[13:19]
-        if ctx.arena is None:
-            raise RuntimeError("the C block calls release their forward workspace after the first backward: a second backward through "
-                               "the same graph (retain_graph=True) needs the per-kernel path (exec_ctx.set(block_calls=False))")
+        need_fwd_arena(ctx.arena, "block")
         B, T, n, H, D, Hd, P, Pb, train, z_bf16, single = ctx.key
         ec = ctx.ec
         ec.poll_backward()              # gradients of the blocks behind this one are final: the data-parallel exchange may start
@@ -376,20 +261,9 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         M = B * S
         dev = x2.device
         G = g_out.contiguous().view(M, D)
-        # the gradient-plane hand-over of the block behind this one (see _attach_grad_planes)
-        g_hi = g_lo = None
-        ent = getattr(g_out, "_egv_planes", None)
-        if ent is not None:
-            try:
-                del g_out._egv_planes
-            except AttributeError:
-                pass
-            if ent[0] == Pb and ent[2] == g_out._version and ent[1].rows == M and ent[1].cols == D:
-                PLANE_HANDOFF["hit"] += 1
-                g_pl = ent[1]
-                g_hi, g_lo = g_pl.hi.data_ptr(), (g_pl.lo.data_ptr() if g_pl.lo is not None else None)
-        if g_hi is None:
-            PLANE_HANDOFF["miss"] += 1
+        # the gradient-plane hand-over of the block behind this one (layer_common._attach_grad_planes); without it the C side formats G
+        g_pl = _take_grad_planes(g_out, M, D, Pb)
+        g_hi, g_lo = (g_pl.hi.data_ptr(), ops._p(g_pl.lo)) if g_pl is not None else (None, None)
         # weight gradients in the order the C side enqueues them (fc2, fc1, attn.proj, attn.qkv, timeattn.proj, timeattn.qkv): stream,
         # event and k-slices of each -- the policy of _lin_bwd / ops.gemm_tn
         shapes = [(w.shape[0], w[0].numel()) for w in weights]
@@ -404,11 +278,8 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
                 streams[i], events[i] = next(it)
         ks = [ops.wgrad_ksplit(shapes[i][0], shapes[i][1], M, ec, use[i]) for i in range(6)]
         g = _block_geom(*ctx.key, ctx.eps, ec.gemm_grid)
-        bkey = (ctx.key, tuple(ks))
-        nb = _BLOCK_BWD_BYTES.get(bkey)
-        if nb is None:
-            nb = _BLOCK_BWD_BYTES[bkey] = int(_lib.lib().egv_block_bwd_arena_bytes(C.byref(g), (C.c_int32 * 6)(*ks)))
-        barena = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ks6 = (C.c_int32 * 6)(*ks)
+        barena = torch.empty(bwd_arena_bytes("egv_block", (ctx.key, tuple(ks)), g, ks6), dtype=torch.uint8, device=dev)
         _, goff, gtot = ctx.sizes
         grads = torch.empty(gtot, dtype=torch.float32, device=dev)
         d_x = torch.empty((M, D), dtype=torch.float32, device=dev)
@@ -420,18 +291,17 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
             # bf16x3 backward reads the lo plane in the fc2 weight gradient as well).  record_stream leaves an event per block and
             # stream with the caching allocator, which polls every outstanding event on every allocation: with 24 blocks and a host
             # that runs two steps ahead that was ~10 ms of host time per ViT-L/14 step (host_enqueue 26 ms against 16 from idle).
-            ec.hold_until_join(ctx.arena, barena, grads, *((g_pl.hi, g_pl.lo) if g_hi is not None else ()))
+            ec.hold_until_join(ctx.arena, barena, grads, *((g_pl.hi, g_pl.lo) if g_pl is not None else ()))
         prm = _block_params(ec.wc, ln, biases, weights, need_t=True, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4, t16=Pb == 4)
         P6 = C.c_void_p * 6
         io = BlockBwdIO(G.data_ptr(), g_hi, g_lo, x2.data_ptr(), ctx.arena.data_ptr(), barena.data_ptr(),
-                        d_x.data_ptr(), dx_pl.hi.data_ptr(), dx_pl.lo.data_ptr() if dx_pl.lo is not None else None, grads.data_ptr(),
+                        d_x.data_ptr(), dx_pl.hi.data_ptr(), ops._p(dx_pl.lo), grads.data_ptr(),
                         P6(*[s_.cuda_stream if s_ is not None else None for s_ in streams]),
-                        P6(*[e.cuda_event if e is not None else None for e in events]), (C.c_int32 * 6)(*ks))
+                        P6(*[e.cuda_event if e is not None else None for e in events]), ks6)
         _lib.check(_lib.lib().egv_block_bwd(C.byref(g), C.byref(prm), C.byref(io), ops._stream(x2)), "egv_block_bwd")
         ctx.arena = None
 
-        sizes = [goff[i + 1] - goff[i] for i in range(17)] + [gtot - goff[17]]
-        parts = grads.split_with_sizes(sizes)                 # 18 views of the one buffer (the layout is back to back)
+        parts = grad_views(grads, goff, gtot)                 # 18 views of the one buffer
         dW = [parts[i].view(weights[i].shape) for i in range(6)]
         db = parts[6:12]
         dln = parts[12:18]                                  # norm3 g/b, norm1 g/b, norm2 g/b

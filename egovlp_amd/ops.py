@@ -292,12 +292,12 @@ class ExecContext:
         measure, the callers pass MACs)."""
         return _SideStream(self, inputs, cost)
 
-    def assign_side_streams(self, costs):
-        """The dealing of `side_stream()` for a batch of weight-gradient GEMMs that a C block call will enqueue itself: -> for each
-        cost a (torch stream, torch event) pair -- the event is recorded on the current stream and waited for by the side stream
-        INSIDE the C call -- and the same bookkeeping (`dirty`, the end-of-backward join callback, load accounting)."""
+    def _deal_side_streams(self, costs):
+        """The one dealing routine of the wgrad side streams: -> for each cost (any additive measure, the callers pass MACs) the
+        stream of the pool that takes it -- round-robin under EGV_WGRAD_DEAL=rr, else the one with the least work dealt to it so far in
+        this step (ties: the first).  Creates the pool on first use, notes the stream the work is forked from (`main`) and that
+        there is something to join (`dirty`), and queues the end-of-backward join once per backward pass."""
         sd = self._side
-        main = torch.cuda.current_stream()
         if sd["stream"] is None:
             sd["stream"] = torch.cuda.Stream()
             sd["extra"] = [torch.cuda.Stream() for _ in range(_wgrad_stream_count() - 1)]
@@ -305,28 +305,36 @@ class ExecContext:
         load = sd.get("load")
         if load is None or len(load) != len(pool):
             load = sd["load"] = [0.0] * len(pool)
-        evs = sd.get("events")
-        if evs is None or len(evs) < len(costs):
-            evs = sd["events"] = [torch.cuda.Event() for _ in range(max(6, len(costs)))]
-            for e in evs:
-                e.record(main)                 # materialises the underlying hipEvent_t
         out = []
-        for i, c in enumerate(costs):
+        for c in costs:
             if _WGRAD_DEAL == "rr":
                 k = sd["rr"] % len(pool)
                 sd["rr"] += 1
             else:
                 k = min(range(len(pool)), key=load.__getitem__)
             load[k] += float(c)
-            out.append((pool[k], evs[i]))
-        sd["main"], sd["dirty"] = main, True
+            out.append(pool[k])
+        sd["main"], sd["dirty"] = torch.cuda.current_stream(), True
         if not sd["queued"]:
-            try:
+            try:   # inside a backward pass: join when the pass ends, whoever called backward()
                 torch.autograd.Variable._execution_engine.queue_callback(self._join_callback)
                 sd["queued"] = True
             except RuntimeError:
                 pass
         return out
+
+    def assign_side_streams(self, costs):
+        """The dealing of `side_stream()` for a batch of weight-gradient GEMMs that a C block call will enqueue itself: -> for each
+        cost a (torch stream, torch event) pair -- the event is recorded on the current stream and waited for by the side stream
+        INSIDE the C call."""
+        streams = self._deal_side_streams(costs)
+        sd = self._side
+        evs = sd.get("events")
+        if evs is None or len(evs) < len(costs):
+            evs = sd["events"] = [torch.cuda.Event() for _ in range(max(6, len(costs)))]
+            for e in evs:
+                e.record(sd["main"])           # materialises the underlying hipEvent_t
+        return list(zip(streams, evs))
 
     def begin_step(self):
         """Start of a forward / backward pass: forget a join callback that never ran (a backward that raised leaves
@@ -422,32 +430,10 @@ class _SideStream:
         self.inputs = [t for t in inputs if t is not None]
 
     def __enter__(self):
-        sd = self.ec._side
-        main = torch.cuda.current_stream()
-        if sd["stream"] is None:
-            sd["stream"] = torch.cuda.Stream()
-            sd["extra"] = [torch.cuda.Stream() for _ in range(_wgrad_stream_count() - 1)]
-        pool = [sd["stream"]] + sd["extra"]
-        load = sd.get("load")
-        if load is None or len(load) != len(pool):
-            load = sd["load"] = [0.0] * len(pool)
-        if _WGRAD_DEAL == "rr":
-            k = sd["rr"] % len(pool)
-            sd["rr"] += 1
-        else:
-            k = min(range(len(pool)), key=load.__getitem__)      # least-loaded stream (ties: the first)
-        load[k] += self.cost
-        side = pool[k]
-        side.wait_stream(main)
+        side, = self.ec._deal_side_streams([self.cost])
+        side.wait_stream(self.ec._side["main"])
         for t in self.inputs:
             t.record_stream(side)
-        sd["main"], sd["dirty"] = main, True
-        if not sd["queued"]:
-            try:   # inside a backward pass: join when the pass ends, whoever called backward()
-                torch.autograd.Variable._execution_engine.queue_callback(self.ec._join_callback)
-                sd["queued"] = True
-            except RuntimeError:
-                pass
         self.ctx = torch.cuda.stream(side)
         self.ctx.__enter__()
         return side

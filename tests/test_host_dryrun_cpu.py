@@ -293,6 +293,7 @@ def test_block_parameter_structs_follow_the_weight_planes(model):
     """The C structs of the block / layer calls hold raw plane addresses and are reused from step to step; they live on the model's
     own weight cache and are rebuilt the moment the cache holds different plane objects (a struct keyed by addresses alone once
     survived its model: the next model's tensors landed on the same addresses with the lo planes elsewhere -> NaN scores)."""
+    from egovlp_amd.model.text_transformer import _text_params
     from egovlp_amd.model.video_transformer import _block_params
     from egovlp_amd.ops import Planes
     ec = model.exec_ctx
@@ -300,15 +301,23 @@ def test_block_parameter_structs_follow_the_weight_planes(model):
     ln = (blk.norm3.weight, blk.norm3.bias, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias)
     ws = (blk.timeattn.qkv.weight, blk.timeattn.proj.weight, blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight)
     bs = (blk.timeattn.qkv.bias, blk.timeattn.proj.bias, blk.attn.qkv.bias, blk.attn.proj.bias, blk.mlp.fc1.bias, blk.mlp.fc2.bias)
-    with mock_hip():
-        a = _block_params(ec.wc, ln, bs, ws, need_t=False)
-        assert _block_params(ec.wc, ln, bs, ws, need_t=False) is a                  # same planes: same struct
-        ent = ec.wc._c[id(ws[4])]
-        old = ent.pl
-        ent.pl = Planes(old.hi.clone(), old.lo.clone(), old.rows, old.cols)
-        b = _block_params(ec.wc, ln, bs, ws, need_t=False)
-        assert b is not a and b.w_hi[4] == ent.pl.hi.data_ptr() and b.w_lo[4] == ent.pl.lo.data_ptr()
-        assert all(b.w_hi[i] == a.w_hi[i] for i in (0, 1, 2, 3, 5))
+    lay = model.text_model.transformer.layer[0]
+    at, ff = lay.attention, lay.ffn
+    tln = (lay.sa_layer_norm.weight, lay.sa_layer_norm.bias, lay.output_layer_norm.weight, lay.output_layer_norm.bias)
+    qkv_w, qkv_b = (at.q_lin.weight, at.k_lin.weight, at.v_lin.weight), (at.q_lin.bias, at.k_lin.bias, at.v_lin.bias)
+    tws, tbs = (at.out_lin.weight, ff.lin1.weight, ff.lin2.weight), (at.out_lin.bias, ff.lin1.bias, ff.lin2.bias)
+    # the shared builder at both widths: the six weights of a video block, the four of a DistilBERT layer (index 2: lin1)
+    for build, cache_key, k, n in ((lambda: _block_params(ec.wc, ln, bs, ws, need_t=False), id(ws[4]), 4, 6),
+                                   (lambda: _text_params(ec.wc, tln, qkv_w, qkv_b, tws, tbs, need_t=False), id(tws[1]), 2, 4)):
+        with mock_hip():
+            a = build()
+            assert build() is a                                                        # same planes: same struct
+            ent = ec.wc._c[cache_key]
+            old = ent.pl
+            ent.pl = Planes(old.hi.clone(), old.lo.clone(), old.rows, old.cols)
+            b = build()
+            assert b is not a and b.w_hi[k] == ent.pl.hi.data_ptr() and b.w_lo[k] == ent.pl.lo.data_ptr()
+            assert all(b.w_hi[i] == a.w_hi[i] for i in range(n) if i != k)
     other = _model()
     assert other.exec_ctx.wc.param_structs is not ec.wc.param_structs and not other.exec_ctx.wc.param_structs
 
