@@ -140,6 +140,9 @@ PROTOTYPES = {
     "egv_splitk_reduce_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_grad_nonfinite_multi": (i32, [i32, c_p, c_p, c_p, c_p]),
     "egv_loss_scale_update": (i32, [c_p, c_p, f32, f32, f32, i32, i32, f32, f32, i32, f32, i32, c_p]),
+    "egv_grad_sqnorm_parts": (i32, [i32, c_p]),
+    "egv_grad_sqnorm_multi": (i32, [i32, c_p, c_p, c_p, i32, c_p, c_p]),
+    "egv_grad_clip_update": (i32, [c_p, i32, c_p, f32, f32, i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_split_f32_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_f16x2_encode": (i32, [c_p, i64, i32, i32, c_p, c_p, c_p, i64, i32, c_p]),
     "egv_f16x2_encode_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p]),

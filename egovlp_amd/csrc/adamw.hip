@@ -221,6 +221,109 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccumTable t
   for (long j = max(base, vend) + threadIdx.x; j < end; j += 256) d[j] = d[j] + s[j];
 }
 
+// ---- gradient clipping by global norm --------------------------------------------------------------------------------------------------
+// (1) the scan above and sum(g * g) in ONE read of the gradients.  Work list of grad_nonfinite_kernel (tensor, 4 * CHUNK-element piece
+// per block); 16-byte loads, four in flight, where the base is 16-byte aligned, a scalar loop otherwise and for the tensor's last
+// n % 4 elements.  fp32 throughout: four accumulators per lane (<= 64 adds each; one accumulator with <= 256 adds on the scalar path),
+// combined, the wave's butterfly (6 levels), the block's four waves through LDS in a fixed order -> ONE partial per block, stored at
+// partials[first + blockIdx.x].  No floating-point atomics: a partial depends on its 65 536 elements alone, never on the schedule.
+// All terms are >= 0, so the relative error of a partial is <= (256 + 8) * 2^-24 = 1.6e-5, half that on the root.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const NonfiniteTable t, float* __restrict__ partials, int first,
+                                                          int* __restrict__ state) {
+  __shared__ float sh[4];
+  int ti = 0;
+  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
+  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * (4 * CHUNK);
+  const long n = t.numel[ti];
+  const float* __restrict__ g = t.g[ti];
+  const long end = min(n, base + 4 * CHUNK);
+  const long vend = ((((size_t)g) & 15) == 0) ? min(end, n & ~3L) : base;
+  unsigned bad = 0u;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  long i = base + threadIdx.x * 4;
+  for (; i + 3 * 1024 < vend; i += 4 * 1024) {
+    f32x4_t w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w[u] = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(g + i + u * 1024);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bad |= ((__float_as_uint(w[u][e]) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+        acc[e] = fmaf(w[u][e], w[u][e], acc[e]);
+      }
+  }
+  for (; i < vend; i += 1024) {
+    const f32x4_t w = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(g + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      bad |= ((__float_as_uint(w[e]) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+      acc[e] = fmaf(w[e], w[e], acc[e]);
+    }
+  }
+  for (long j = max(base, vend) + threadIdx.x; j < end; j += 256) {
+    const float x = g[j];
+    bad |= ((__float_as_uint(x) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+    acc[0] = fmaf(x, x, acc[0]);
+  }
+  if (state && __any(bad != 0u) && (threadIdx.x & 63) == 0) atomicOr(state + 2, 1);      // as the scan: an integer OR, normally none
+  const float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[first + (int)blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// (2) the clip decision, one workgroup.  norm block (8 x 32 bits, DEVICE): [0] float norm of the UN-scaled gradients before clipping;
+// [1] float coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), 0 in a step that is not applied; [2] int this
+// step's norm was not finite; [3] int steps clipped so far (coef < 1); [4] int steps not applied for a non-finite norm; [5..7] unused.
+constexpr int CLIP_MAX_H = 64;   // hyper blocks (parameter groups / launch groups) one decision serves
+struct ClipTable {
+  float* hyper[CLIP_MAX_H];
+  float lr[CLIP_MAX_H];
+  float step_size[CLIP_MAX_H];
+  int count;
+};
+__global__ __launch_bounds__(256) void grad_clip_update_kernel(const float* __restrict__ partials, int parts, const int* state,
+                                                               float grad_scale, float max_norm, const ClipTable t, int fill,
+                                                               int* norm_block) {
+  __shared__ double sh[4];
+  // the partials in a fixed order, in double: lane-strided, the wave's butterfly, the four waves
+  double s = 0.0;
+  for (int i = threadIdx.x; i < parts; i += 256) s += (double)partials[i];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double total = (sh[0] + sh[1]) + (sh[2] + sh[3]);            // norm^2 of the gradients as they are (scaled by S)
+  // with a scaler: 1 / S and the skip of THIS step, as egv_loss_scale_update (advance) left them; both are read before any hyper
+  // block is written (the first group's block IS state + 4)
+  const float* fs = (const float*)state;
+  const float inv = state ? fs[6] : grad_scale;
+  const bool skipped = state ? (fs[7] != 0.f) : false;
+  const float norm = (float)(sqrt(total) * (double)inv);
+  const bool nonfinite = skipped || ((__float_as_uint(norm) & 0x7fffffffu) >= 0x7f800000u);
+  float coef = 0.f;
+  if (nonfinite) {
+    norm_block[4] += 1;
+  } else {
+    coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+    if (coef < 1.0f) norm_block[3] += 1;
+  }
+  ((float*)norm_block)[0] = norm;
+  ((float*)norm_block)[1] = coef;
+  norm_block[2] = nonfinite ? 1 : 0;
+  for (int k = 0; k < t.count; ++k) {
+    float* h = t.hyper[k];
+    if (fill) {
+      h[0] = t.lr[k];
+      h[1] = t.step_size[k];
+    }
+    h[2] = inv * coef;
+    h[3] = nonfinite ? 1.0f : 0.0f;
+  }
+}
+
 }  // namespace
 
 extern "C" int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* const* src, const int64_t* numel, void* stream) {
@@ -289,6 +392,75 @@ extern "C" int egv_grad_nonfinite_multi(int32_t count, const float* const* g, co
     ++nt;
   }
   return flush();
+}
+
+// blocks (= partials) of a gradient list, or -1 for a list no launch sequence can take
+static int64_t sqnorm_parts(int32_t count, const int64_t* numel) {
+  if (count < 0 || (count > 0 && !numel)) return -1;
+  int64_t parts = 0;
+  for (int i = 0; i < count; ++i) {
+    if (numel[i] < 0) return -1;
+    parts += (numel[i] + 4 * CHUNK - 1) / (4 * CHUNK);
+    if (parts > 0x7fffffff) return -1;
+  }
+  return parts;
+}
+
+extern "C" int egv_grad_sqnorm_parts(int32_t count, const int64_t* numel) { return (int)sqnorm_parts(count, numel); }
+
+extern "C" int egv_grad_sqnorm_multi(int32_t count, const float* const* g, const int64_t* numel, float* partials,
+                                     int32_t parts_capacity, int32_t* state, void* stream) {
+  const int64_t parts = sqnorm_parts(count, numel);      // validate everything before the first launch: a bad argument enqueues nothing
+  if (parts < 0 || parts_capacity < parts || (parts > 0 && (!g || !partials))) return EGV_ERR_ARG;
+  for (int i = 0; i < count; ++i)
+    if (numel[i] > 0 && !g[i]) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  NonfiniteTable t;
+  int nt = 0, nb = 0, first = 0;
+  auto flush = [&]() -> int {
+    if (nt == 0) return EGV_OK;
+    t.blk_start[nt] = nb;
+    t.count = nt;
+    EGV_LAUNCH(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, t, partials, first, state);
+    EGV_CHECK_LAUNCH();
+    first += nb;
+    nt = 0;
+    nb = 0;
+    return EGV_OK;
+  };
+  for (int i = 0; i < count; ++i) {
+    if (numel[i] == 0) continue;
+    if (nt == NF_MAX_T) {
+      const int rc = flush();
+      if (rc) return rc;
+    }
+    t.g[nt] = g[i];
+    t.numel[nt] = numel[i];
+    t.blk_start[nt] = nb;
+    nb += (int)((numel[i] + 4 * CHUNK - 1) / (4 * CHUNK));
+    ++nt;
+  }
+  return flush();
+}
+
+extern "C" int egv_grad_clip_update(const float* partials, int32_t parts, const int32_t* state, float grad_scale, float max_norm,
+                                    int32_t n_hyper, float* const* hyper, const float* lr, const float* step_size,
+                                    int32_t* norm_block, void* stream) {
+  if (parts < 0 || (parts > 0 && !partials) || !(max_norm > 0.f) || n_hyper < 1 || n_hyper > CLIP_MAX_H || !hyper || !norm_block)
+    return EGV_ERR_ARG;
+  if (!state && (!lr || !step_size)) return EGV_ERR_ARG;      // no scaler: the blocks are filled here, from the host's scalars
+  ClipTable t;
+  for (int k = 0; k < n_hyper; ++k) {
+    if (!hyper[k]) return EGV_ERR_ARG;
+    t.hyper[k] = hyper[k];
+    t.lr[k] = state ? 0.f : lr[k];
+    t.step_size[k] = state ? 0.f : step_size[k];
+  }
+  t.count = n_hyper;
+  EGV_LAUNCH(grad_clip_update_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, parts, (const int*)state, grad_scale,
+             max_norm, t, state ? 0 : 1, (int*)norm_block);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
 }
 
 extern "C" int egv_loss_scale_update(int32_t* state, float* hyper_out, float lr, float beta1, float beta2, int32_t step,

@@ -1217,6 +1217,52 @@ def loss_scale_update(state, hyper_out, lr, beta1, beta2, step, correct_bias, gr
           "egv_loss_scale_update")
 
 
+def grad_sqnorm_parts(grads):
+    """How many partial sums grad_sqnorm_multi writes for this list (egv_grad_sqnorm_parts: one per 65 536-element piece of a tensor)."""
+    n = len(grads)
+    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    parts = int(_lib.lib().egv_grad_sqnorm_parts(n, N))
+    if parts < 0:
+        raise ValueError("grad_sqnorm_parts: the gradient list is beyond 2^31 - 1 pieces")
+    return parts
+
+
+def grad_sqnorm_multi(grads, partials, state=None):
+    """The non-finite scan of grad_nonfinite_multi (only with `state`, the int32[8] block of a LossScaler) and sum(g * g) in ONE read
+    of the gradients (egv_grad_sqnorm_multi): one fp32 partial per piece into `partials` (fp32, at least grad_sqnorm_parts(grads)
+    elements), bit-reproducible.  Dense contiguous fp32 tensors; views at any 4-byte offset are fine."""
+    n = len(grads)
+    if n == 0:
+        return
+    for g in grads:
+        if g.dtype != torch.float32 or g.is_sparse or not g.is_contiguous():
+            raise ValueError("grad_sqnorm_multi: dense contiguous fp32 gradients")
+    if partials.dtype != torch.float32 or not partials.is_contiguous():
+        raise ValueError("grad_sqnorm_multi: `partials` is a contiguous fp32 tensor")
+    _need_cuda(*grads, partials)
+    G = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
+    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    check(_lib.lib().egv_grad_sqnorm_multi(n, G, N, _p(partials), partials.numel(), _p(state), _stream(grads[0])),
+          "egv_grad_sqnorm_multi")
+
+
+def grad_clip_update(partials, parts, norm_block, max_norm, hyper_blocks, state=None, grad_scale=1.0, lrs=None, step_sizes=None):
+    """The clip decision of one step, on the device (egv_grad_clip_update): norm = sqrt(sum of the first `parts` partials) * (1 / S
+    from `state`, or grad_scale), coef = min(1, max_norm / (norm + 1e-6)) -> `norm_block` (int32[8]: norm, coef, non-finite flag,
+    counters) and [2] = (1 / S or grad_scale) * coef, [3] = skip of every block of `hyper_blocks` (fp32[4] device tensors, at most 64).
+    Without `state` the blocks' lr / step size come from `lrs` / `step_sizes` (host floats, one per block)."""
+    n = len(hyper_blocks)
+    if not 1 <= n <= 64:
+        raise ValueError("grad_clip_update: 1 .. 64 hyper blocks (parameter groups / launch groups) per step")
+    if state is None and (lrs is None or step_sizes is None or len(lrs) != n or len(step_sizes) != n):
+        raise ValueError("grad_clip_update: without a scaler state, one lr and one step size per hyper block")
+    H = (C.c_void_p * n)(*[h.data_ptr() for h in hyper_blocks])
+    L = (C.c_float * n)(*[float(x) for x in lrs]) if state is None else None
+    S = (C.c_float * n)(*[float(x) for x in step_sizes]) if state is None else None
+    check(_lib.lib().egv_grad_clip_update(_p(partials), int(parts), _p(state), float(grad_scale), float(max_norm), n, H, L, S,
+                                          _p(norm_block), _stream(norm_block)), "egv_grad_clip_update")
+
+
 def adamw_tables(params, ms, vs):
     """The argument tables of egv_adamw_multi that do not change from step to step (parameter / moment addresses, sizes)."""
     n = len(params)

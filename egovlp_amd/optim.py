@@ -73,7 +73,21 @@ class LossScaler:
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    """`max_grad_norm` (None, 0 or inf: off): clip the gradients by their GLOBAL norm over all parameter groups, as
+    `torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)` before the step would -- on the device, inside the step:
+    the pass that scans the gradients for inf / NaN also reduces sum(g * g) (egv_grad_sqnorm_multi replaces egv_grad_nonfinite_multi:
+    the gradients are still read once), one workgroup forms norm = sqrt(sum) / S and coef = min(1, max_grad_norm / (norm + 1e-6))
+    (egv_grad_clip_update) and every hyper block of the step carries (1 / S) * coef where it carried 1 / S, the factor the update
+    multiplies each gradient by anyway.  No host synchronisation, no extra pass.  Without a scaler the optimizer owns the hyper
+    blocks and the kernel fills them with {lr, step size, grad_scale * coef, skip}.
+    ONE DEVIATION from clip_grad_norm_ (whose default would scale every gradient by NaN and write NaN into every parameter): a step
+    whose norm is not finite is NOT APPLIED, with or without a scaler -- parameters and moments stay, `nonfinite_steps()` counts it;
+    with a scaler the scale backs off by its usual rule as well.
+    `grad_norm()` (un-scaled, before clipping), `clip_coef()`, `clipped_steps()`, `nonfinite_steps()` read the last step's decision
+    back (they synchronise: logs, tests, checkpoints).  It is a property of the step, not of a group: stored on the optimizer and in
+    `state_dict()['max_grad_norm']`."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -85,6 +99,13 @@ class AdamW(torch.optim.Optimizer):
         self._scaler = None     # the LossScaler of the step() in progress (None: un-scaled gradients, host-side hyper-parameters)
         self._scaler_first = False
         self._plans = {}        # id(param group) -> (params, states, exp_avg, exp_avg_sq, argument tables) of the steady-state launch
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)     # None: clipping is off, step() is the step it always was
+        self._pending = None    # clipping: the launches of the step in progress, collected before the decision kernel runs
+        self._clip_numels = None        # sizes of the gradient list `_clip_partials` was sized for
+        self._clip_partials = None      # fp32[parts]: one sum of squares per block of egv_grad_sqnorm_multi
+        self._clip_parts = 0
+        self._norm_block = None         # int32[8] on the device: {norm, coef, nonfinite, clipped steps, non-finite steps, -, -, -}
+        self._clip_hyper = None         # fp32[64, 4]: the hyper blocks of a step without a scaler
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, scaler=None):
@@ -92,6 +113,10 @@ class AdamW(torch.optim.Optimizer):
         applied (and with which S next), un-scale inside the update.  No host synchronisation either way."""
         loss = closure() if closure is not None else None
         groups = [(g, [p for p in g["params"] if p.grad is not None]) for g in self.param_groups]
+        if self.max_grad_norm is not None:
+            self._step_clipped(groups, grad_scale, scaler)
+            weights.bump_epoch()
+            return loss
         if scaler is not None:
             grads = [p.grad for _, ps in groups for p in ps]
             if any(g.is_sparse or not g.is_contiguous() for g in grads):
@@ -107,8 +132,91 @@ class AdamW(torch.optim.Optimizer):
         weights.bump_epoch()   # parameters were written through raw pointers: invalidate the bf16 planes
         return loss
 
+    def _step_clipped(self, groups, grad_scale, scaler):
+        """The step with max_grad_norm: scan + sum of squares (one read of the gradients), the scale decision and every launch's hyper
+        block, ONE clip decision for all of them, then the updates."""
+        grads = [p.grad for _, ps in groups for p in ps]
+        if not grads:
+            return
+        if any(g.is_sparse or not g.is_contiguous() for g in grads):
+            raise RuntimeError("AdamW (HIP) needs contiguous dense gradients")
+        numels = [g.numel() for g in grads]
+        dev = grads[0].device
+        if numels != self._clip_numels or self._clip_partials.device != dev:
+            # the parameter set changed (or this is the first step): size the partials for it.  Comparing the sizes themselves catches
+            # every change the plans' identity test catches, and a `p.data = ...` of another size as well
+            self._clip_parts = ops.grad_sqnorm_parts(grads)
+            self._clip_partials = torch.empty(max(self._clip_parts, 1), dtype=torch.float32, device=dev)
+            self._clip_numels = numels
+        if self._norm_block is None or self._norm_block.device != dev:
+            self._norm_block = torch.zeros(8, dtype=torch.int32, device=dev)      # the counters live as long as the optimizer
+        ops.grad_sqnorm_multi(grads, self._clip_partials, scaler.state if scaler is not None else None)
+        self._pending = []
+        try:
+            for gi, (group, params) in enumerate(groups):
+                self._group_index = gi
+                self._update_group(group, params, grad_scale)
+            launches = self._pending
+        finally:
+            self._pending = None
+        hypers, lrs, sizes, seen = [], [], [], {}
+        for k, (group, gi, ps, gs, ms, vs, step, tables) in enumerate(launches):
+            b1, b2 = group["betas"]
+            if scaler is not None:
+                # a group's first launch takes the scaler's block of that group, as the un-clipped step does; launches of the same
+                # group at another step count (rare) get blocks of their own, since all blocks are written BEFORE the first update
+                j = seen[gi] = seen.get(gi, -1) + 1
+                hyper = scaler.hyper_block(gi if j == 0 else (gi, j))
+                ops.loss_scale_update(scaler.state, hyper, group["lr"], b1, b2, step, group["correct_bias"], scaler.growth_factor,
+                                      scaler.backoff_factor, scaler.growth_interval, scaler.max_scale, advance=(k == 0))
+            else:
+                if self._clip_hyper is None or self._clip_hyper.device != dev:
+                    self._clip_hyper = torch.zeros((64, 4), dtype=torch.float32, device=dev)
+                if k >= 64:
+                    raise RuntimeError("AdamW (HIP): max_grad_norm serves at most 64 launch groups (parameter groups x step counts)")
+                hyper = self._clip_hyper[k]
+                lrs.append(group["lr"])
+                sizes.append(_step_size_f32(group["lr"], b1, b2, step, group["correct_bias"]))
+            hypers.append(hyper)
+        ops.grad_clip_update(self._clip_partials, self._clip_parts, self._norm_block, self.max_grad_norm, hypers,
+                             state=scaler.state if scaler is not None else None, grad_scale=grad_scale, lrs=lrs, step_sizes=sizes)
+        for hyper, (group, gi, ps, gs, ms, vs, step, tables) in zip(hypers, launches):
+            b1, b2 = group["betas"]
+            ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
+                            group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)
+
+    # ---- host readbacks of the clip decision (synchronise: logs, tests, checkpoints); None while clipping is off / before a step ----
+    def _norm_host(self):
+        return None if self._norm_block is None else self._norm_block.cpu()
+
+    def grad_norm(self):
+        """Global norm of the last step's gradients, un-scaled (divided by the loss scale), BEFORE clipping."""
+        nb = self._norm_host()
+        return None if nb is None else float(nb.view(torch.float32)[0])
+
+    def clip_coef(self):
+        """The factor the last step's gradients were multiplied by: min(1, max_grad_norm / (norm + 1e-6)); 0 in a step not applied."""
+        nb = self._norm_host()
+        return None if nb is None else float(nb.view(torch.float32)[1])
+
+    def clipped_steps(self):
+        nb = self._norm_host()
+        return 0 if nb is None else int(nb[3])
+
+    def nonfinite_steps(self):
+        """Steps not applied because their gradient norm was inf / NaN (with a scaler these are also among its skipped steps)."""
+        nb = self._norm_host()
+        return 0 if nb is None else int(nb[4])
+
+    def state_dict(self):
+        d = super().state_dict()
+        d["max_grad_norm"] = self.max_grad_norm
+        return d
+
     def load_state_dict(self, state_dict):
         self._plans.clear()
+        if "max_grad_norm" in state_dict:
+            self.max_grad_norm = _check_max_grad_norm(state_dict["max_grad_norm"])
         return super().load_state_dict(state_dict)
 
     def _update_group(self, group, params, grad_scale):
@@ -160,6 +268,9 @@ class AdamW(torch.optim.Optimizer):
     def _launch(self, group, ps, gs, ms, vs, step, grad_scale, tables=None):
         if not ps:
             return
+        if self._pending is not None:       # clipping: the hyper blocks of ALL launches are decided first (_step_clipped)
+            self._pending.append((group, getattr(self, "_group_index", 0), ps, gs, ms, vs, step, tables))
+            return
         b1, b2 = group["betas"]
         hyper = None
         sc = self._scaler
@@ -172,6 +283,28 @@ class AdamW(torch.optim.Optimizer):
             self._scaler_first = False
         ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
                         group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)
+
+
+def _check_max_grad_norm(v):
+    """None, 0 and inf mean "off" (-> None); a negative value or NaN is an error."""
+    if v is None:
+        return None
+    v = float(v)
+    if not v >= 0.0:
+        raise ValueError("Invalid max_grad_norm: {} - should be >= 0.0 (None, 0 or inf: no clipping)".format(v))
+    return None if v == 0.0 or v == float("inf") else v
+
+
+def clip_coefficient(norm, max_norm):
+    """torch.nn.utils.clip_grad_norm_'s rule, which egv_grad_clip_update applies on the device: gradients are multiplied by this."""
+    return min(1.0, float(max_norm) / (float(norm) + 1e-6))
+
+
+def _step_size_f32(lr, beta1, beta2, step, correct_bias):
+    """adamw_step_size on the fp32 roundings of lr / betas: what egv_adamw_multi computes from its float arguments."""
+    import ctypes
+    f = lambda x: ctypes.c_float(x).value
+    return adamw_step_size(f(lr), f(beta1), f(beta2), step, correct_bias)
 
 
 def adamw_step_size(lr, beta1, beta2, step, correct_bias=True):

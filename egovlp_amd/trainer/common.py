@@ -193,6 +193,11 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 total = int(self.data_loader[dl_idx].n_samples / self.n_gpu) if hasattr(self.data_loader[dl_idx], 'n_samples') else 0
                 current = batch_idx * self.data_loader[dl_idx].batch_size
                 self.writer.add_scalar(f'Loss_training/loss_{dl_idx}', float(loss), (epoch - 1) * total + current)   # :143-148
+                # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has
+                # just synchronised anyway (off: nothing is computed, nothing is read)
+                if getattr(self.optimizer, 'max_grad_norm', None) is not None:
+                    self.writer.add_scalar(f'Grad_training/grad_norm_{dl_idx}', self.optimizer.grad_norm(), (epoch - 1) * total + current)
+                    self.writer.add_scalar(f'Grad_training/clip_coef_{dl_idx}', self.optimizer.clip_coef(), (epoch - 1) * total + current)
         log = {f'loss_{dl_idx}': float(total_loss[dl_idx]) / self.len_epoch for dl_idx in range(len(self.data_loader))}   # :162-164
         if self.writer is not None and self.args.rank == 0:
             for dl_idx in range(len(self.data_loader)):

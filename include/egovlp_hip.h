@@ -542,6 +542,34 @@ int egv_loss_scale_update(int32_t* state, float* hyper_out, float lr, float beta
                           float growth_factor, float backoff_factor, int32_t growth_interval, float max_scale, int32_t advance,
                           void* stream);
 
+/* ---- gradient clipping by global norm (no counterpart in the reference, which never clips) -------------------------------
+ * torch.nn.utils.clip_grad_norm_ over all parameters, decided on the device and folded into the factor egv_adamw_multi already
+ * multiplies every gradient by (hyper_dev[2]): no host synchronisation, no second read of the gradients.
+ * egv_grad_sqnorm_parts: the number of partial sums (floats) egv_grad_sqnorm_multi writes for a list: one per block, a block
+ * covers 65 536 elements of one tensor, empty tensors take none; -1 for a negative count / size or a list beyond 2^31 - 1 blocks.
+ * egv_grad_sqnorm_multi: the scan of egv_grad_nonfinite_multi (state[2] |= 1 on an inf / NaN; `state` may be NULL: no scan) and
+ * sum(g * g) in ONE read of the `count` fp32 gradient tensors (HOST arrays of device pointers / sizes; any 4-byte-aligned base,
+ * 16-byte loads where the base allows them).  partials[0 .. parts) receive one fp32 sum per block, in list order; no
+ * floating-point atomics: the same input gives the same bits, whatever the schedule; a partial is within 1.6e-5 relative of the
+ * exact sum of its squares.  Everything is validated before the first launch: a negative count / size, a NULL pointer of a
+ * non-empty tensor, or parts_capacity (floats behind `partials`) below the count above is an invalid argument and enqueues
+ * nothing.
+ * egv_grad_clip_update (one workgroup): norm^2 = the `parts` partials summed in a fixed order in double; norm = sqrt(norm^2) *
+ * (state ? state[6], the 1 / S egv_loss_scale_update(advance) left for this step : grad_scale); coef = min(1, max_norm / (norm +
+ * 1e-6)); a norm that is not finite (with `state`: also a step the scaler skips) makes the step NOT APPLIED: coef = 0, skip = 1.
+ *   norm block (8 x 32 bits, DEVICE): [0] float norm (un-scaled, before clipping); [1] float coef; [2] int32 this step's norm was
+ *                        not finite; [3] int32 steps clipped so far (coef < 1); [4] int32 steps not applied so far; [5..7] unused.
+ * Then every one of the n_hyper (1..64) hyper blocks (`hyper`: HOST array of device pointers to 4 floats each, the hyper_dev of
+ * the egv_adamw_multi calls that follow) gets [2] = (1 / S or grad_scale) * coef and [3] = skip.  With `state` the blocks must
+ * already hold what egv_loss_scale_update wrote ([0], [1] stay; lr / step_size are ignored and may be NULL); without it [0] = lr[k],
+ * [1] = step_size[k] (HOST arrays) are filled in as well.  max_norm > 0.                                                        */
+int egv_grad_sqnorm_parts(int32_t count, const int64_t* numel);
+int egv_grad_sqnorm_multi(int32_t count, const float* const* grads, const int64_t* numel, float* partials, int32_t parts_capacity,
+                          int32_t* state, void* stream);
+int egv_grad_clip_update(const float* partials, int32_t parts, const int32_t* state, float grad_scale, float max_norm,
+                         int32_t n_hyper, float* const* hyper, const float* lr, const float* step_size, int32_t* norm_block,
+                         void* stream);
+
 /* ---- misc -----------------------------------------------------------------------------------------------
  * gather rows: out[r,:] = x[idx_stride * r * ld ...] helper for CLS-row extraction is done with strides in
  * egv_layernorm_fwd (ldx = S*D, rows = B).  relu on fp32 -> split planes: */
