@@ -110,6 +110,9 @@ PROTOTYPES = {
     "egv_text_attn_bwd": (i32, [c_p, c_p, c_p, i64, c_p, c_p, c_p, i32, i32, i32, i32, f32, u64, c_p, c_p, c_p, c_p, i64, c_p, c_p]),
     "egv_zero": (i32, [c_p, i64, c_p]),
     "egv_dropout": (i32, [c_p, c_p, c_p, i64, f32, u64, c_p, c_p]),
+    "egv_drop_path_scales": (i32, [i32, f32, u64, c_p, c_p, c_p]),
+    "egv_drop_path_add": (i32, [c_p, c_p, c_p, i32, i32, i32, f32, u64, c_p, c_p]),
+    "egv_drop_path_grad": (i32, [c_p, i64, i32, i32, i32, f32, u64, c_p, i32, c_p, c_p, i64, c_p]),
     "egv_egonce_fwd_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, f32, f32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_egonce_work_floats": (i64, [i32, i32]),
     "egv_sim_matrix_fwd": (i32, [c_p, c_p, i32, i32, i32, f32, c_p, c_p, c_p, c_p, c_p]),

@@ -57,9 +57,9 @@ class Multi_BaseTrainer_dist:
         self.grad_sync = None
         if self.world_size > 1:
             from ..dist import Bf16GradSync
-            text = getattr(self.model, "text_model", None)
-            if text is not None and hasattr(text, "seed_rank"):
-                text.seed_rank = dist.get_rank()           # ranks must not draw identical dropout masks
+            for tower in (getattr(self.model, "text_model", None), getattr(self.model, "video_model", None)):
+                if tower is not None and hasattr(tower, "seed_rank"):
+                    tower.seed_rank = dist.get_rank()      # ranks must not draw identical dropout / drop-path masks
             if hasattr(self.model, "gradient_ready_order"):
                 # hook-free: buckets are launched from the polls of the video tower's backward (autograd grad-ready hooks
                 # cost 0.6 ms per step more on this model, profiles/r02_d_dp_overhead.txt)

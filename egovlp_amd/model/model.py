@@ -113,18 +113,21 @@ class FrozenInTime(BaseModel):
             time_init = video_params.get('time_init', 'zeros')
             attention_style = video_params.get('attention_style', 'frozen-in-time')
             arch_config = video_params.get('arch_config', 'base_patch16_224')
+            # extension key (the reference's configs carry none and build rate 0): stochastic depth of the video tower, the usual
+            # ViT fine-tuning regulariser (0.1 - 0.2); SpaceTimeTransformer(drop_path_rate=...) as in the reference's class
+            drop_path_rate = video_params.get('drop_path_rate', 0.)
             if arch_config == 'base_patch16_224':
                 model = SpaceTimeTransformer(num_frames=num_frames, time_init=time_init,
-                                             attention_style=attention_style)
+                                             attention_style=attention_style, drop_path_rate=drop_path_rate)
                 vit_path = "pretrained/jx_vit_base_p16_224-80ecf9dd.pth"
             elif arch_config == 'large_patch14_224':          # extension: BASELINE config 5
                 model = SpaceTimeTransformer(patch_size=14, embed_dim=1024, depth=24, num_heads=16,
                                              num_frames=num_frames, time_init=time_init,
-                                             attention_style=attention_style)
+                                             attention_style=attention_style, drop_path_rate=drop_path_rate)
                 vit_path = None
             elif arch_config == 'custom':                     # extension (tests): SpaceTimeTransformer(**video_params['arch_kwargs'])
                 model = SpaceTimeTransformer(num_frames=num_frames, time_init=time_init, attention_style=attention_style,
-                                             **video_params['arch_kwargs'])
+                                             **{'drop_path_rate': drop_path_rate, **video_params['arch_kwargs']})
                 vit_path = None
             else:
                 raise NotImplementedError                                                        # :53

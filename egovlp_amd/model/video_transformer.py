@@ -39,6 +39,10 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
          t  = timeattn(norm3(x));  tr = x + t
          s  = attn(norm1(tr));     sr = x + s          (residual from x, NOT tr -- :171)
          out = sr + mlp(norm2(sr))
+    With stochastic depth (:155,:171,:175; geom[6] = (p, seed_space, seed_mlp, seed_dev), set by a train-mode block with p > 0):
+         sr = x + s1[b] * attn(..);  out = sr + s2[b] * mlp(..)       s[b] in {0, 1 / (1 - p)} per sample, ops.drop_path_*
+    the proj / fc2 Linears then run without their residual and one egv_drop_path_add merges it; the backward scales the two branch
+    gradients while it formats them (egv_drop_path_grad) from the seeds of the forward.
     """
 
     @staticmethod
@@ -48,6 +52,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
                 n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b):
         B, T, n, H, eps = geom[:5]
         single = geom[5] if len(geom) > 5 else 0     # ops.F16_SINGLE_BITS: Linears of THIS block that run ONE fp16 product (f16x2 mode)
+        dp = geom[6] if len(geom) > 6 else None      # stochastic depth of this forward: (p, seed_space, seed_mlp, seed_dev) or None
         S = 1 + T * n
         D = x.shape[-1]
         M = B * S
@@ -95,7 +100,9 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         ops.gemm_nt(n1, W(sqkv_w, wf), passes=P_qkv, bias=sqkv_b, out_planes=qkv_s, ec=ec)
         a_s, lse_s = ops.divided_attn_fwd(qkv_s, B, T, n, H, 0, Pa, out_fmt=afmt)
         sr = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ops.gemm_nt(a_s, W(sproj_w, wp), passes=P_proj, bias=sproj_b, residual=x2, out_f32=sr, ec=ec)
+        ops.gemm_nt(a_s, W(sproj_w, wp), passes=P_proj, bias=sproj_b, residual=None if dp else x2, out_f32=sr, ec=ec)
+        if dp:      # sr = x + s1[b] * attn(..), in place on the branch
+            ops.drop_path_add(sr, x2, S, dp[0], dp[1], dp[3])
         # ---- MLP (:175, Mlp.forward :46-52), exact-erf GELU fused into the fc1 epilogue
         n2, _, mean2, rstd2, _ = ops.layernorm_fwd(sr, n2w, n2b, eps, P, want_bf=want_bf, single=s_fc1)
         h = ops.empty_planes_f16x2(M, Hd, dev, want_bf=want_bf, single=s_fc2) if fx2 else ops.empty_planes(M, Hd, P, dev)
@@ -108,7 +115,9 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         ops.gemm_nt(n2, W(fc1_w, wf), passes=P_fc1, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h,
                     aux_is_grad=z is not None and z_dtype != torch.float32, ec=ec)
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ops.gemm_nt(h, W(fc2_w, wf), passes=P_fc2, bias=fc2_b, residual=sr, out_f32=out, ec=ec)
+        ops.gemm_nt(h, W(fc2_w, wf), passes=P_fc2, bias=fc2_b, residual=None if dp else sr, out_f32=out, ec=ec)
+        if dp:      # out = sr + s2[b] * mlp(..)
+            ops.drop_path_add(out, sr, S, dp[0], dp[2], dp[3])
 
         if save:
             ctx.geom, ctx.ec, ctx.P, ctx.h16 = geom, ec, P, h16
@@ -142,9 +151,14 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
                 return wc.get(p, need_t=True, fmt="f16x2", t_fmt="f16")[1]
             return wc.get(p, need_t=True)[1]
 
+        dp = ctx.geom[6] if len(ctx.geom) > 6 else None     # the forward's stochastic-depth draws
+        S = 1 + T * n
         # ---- MLP backward.  dZ = (G . W2) * gelu'(z) comes out of the fc2-dgrad epilogue already split.
         G_pl = _take_grad_planes(g_out, M, D, Pb)
-        if G_pl is None:
+        if dp:
+            # the branch gradient is s2[b] * G: planes handed over by the block behind this one are those of the un-scaled G
+            G_pl = ops.drop_path_grad(G, S, dp[0], dp[2], Pb, dp[3])
+        elif G_pl is None:
             G_pl = ops.f16_cast(G) if h16 else ops.split_f32(G, Pb)[0]
         Hd = fc1_w.shape[0]
         dZ = ops.empty_planes_f16x2(M, Hd, G.device, single=True) if h16 else ops.empty_planes(M, Hd, Pb, G.device)
@@ -154,7 +168,11 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         ln16 = Pb == 4          # fp16 backward: the dgrads in front of a LayerNorm backward hand it ONE plane of un-clamped fp16 (no fp32 copy)
         d_n2, d_fc1_w, d_fc1_b = _lin_bwd(dZ, n2, Wt(fc1_w), Pb, dx_planes=ln16, params=(fc1_w,), ec=ec)
         # d_sr = G + LN2'(d_n2)
-        d_sr, d_n2w, d_n2b, d_sr_pl = ops.layernorm_bwd(d_n2, sr, n2w, mean2, rstd2, add1=G, planes_passes=Pb)
+        if dp:      # the space branch's gradient is s1[b] * d_sr, formatted from the fp32 d_sr
+            d_sr, d_n2w, d_n2b = ops.layernorm_bwd(d_n2, sr, n2w, mean2, rstd2, add1=G)
+            d_sr_pl = ops.drop_path_grad(d_sr, S, dp[0], dp[1], Pb, dp[3])
+        else:
+            d_sr, d_n2w, d_n2b, d_sr_pl = ops.layernorm_bwd(d_n2, sr, n2w, mean2, rstd2, add1=G, planes_passes=Pb)
         # ---- spatial attention backward
         d_as, d_sproj_w, d_sproj_b = _lin_bwd(d_sr_pl, a_s, Wt(sproj_w), Pb, dx_planes=True, params=(sproj_w,), ec=ec)
         d_qkv_s = ops.divided_attn_bwd(qkv_s, a_s, d_as, lse_s, B, T, n, H, 0, 1 if h16 else Pb, grad_f16=h16)
@@ -167,7 +185,6 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         # x feeds norm3, the tr residual and the sr residual: dx = d_tr + d_sr + LN3'(d_n3)
         d_x, d_n3w, d_n3b, d_x_pl = ops.layernorm_bwd(d_n3, x2, n3w, mean3, rstd3, add1=d_tr, add2=d_sr,
                                                        planes_passes=Pb)
-        S = 1 + T * n
         return (_attach_grad_planes(d_x.view(B, S, D), Pb, d_x_pl), None, None,
                 d_n3w, d_n3b, d_tqkv_w, d_tqkv_b, d_tproj_w, d_tproj_b,
                 d_n1w, d_n1b, d_sqkv_w, d_sqkv_b, d_sproj_w, d_sproj_b,
@@ -180,10 +197,11 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
 # how many k-slices it gets, the gradient-plane hand-over between blocks, the backward poll of the gradient exchange.
 
 
-def block_calls_ok(ec: ExecContext, M, D, Hd):
+def block_calls_ok(ec: ExecContext, M, D, Hd, drop_path=False):
     """May this block run through the C block calls?  (split-bf16 / bf16 precision, no per-kernel timer attached, every GEMM of
-    the block un-split and at least one 256-wide tile: the per-kernel path covers the toy shapes)"""
-    if not ec.block_calls or ec.kernel_timer is not None or (ec.bwd_passes == 3 and ec.fwd_passes != 3) or \
+    the block un-split and at least one 256-wide tile: the per-kernel path covers the toy shapes, and every forward that drops
+    paths -- `drop_path`: stochastic depth is not in the C calls)"""
+    if drop_path or not ec.block_calls or ec.kernel_timer is not None or (ec.bwd_passes == 3 and ec.fwd_passes != 3) or \
             (ec.bwd_passes == 4 and ec.fwd_passes != 2):
         return False
     if ec.fwd_passes == 2 and not f16x2_block_ok(M, D, Hd, True):
@@ -443,8 +461,9 @@ class SpaceTimeBlock(nn.Module):
                  drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm, time_init='zeros',
                  attention_style='frozen-in-time'):
         super().__init__()
-        if drop_path != 0.:
-            raise NotImplementedError("stochastic depth is 0 on the EgoClip hot path")
+        if not 0. <= drop_path < 1.:
+            raise ValueError("drop_path is a probability in [0, 1)")
+        self.drop_path = float(drop_path)     # :155 (timm DropPath, scale_by_keep): Identity at 0, as in the reference
         if attention_style != 'frozen-in-time':
             raise NotImplementedError  # model/video_transformer.py:173
         self.norm1 = norm_layer(dim)
@@ -458,11 +477,18 @@ class SpaceTimeBlock(nn.Module):
         self.num_heads = num_heads
         self.attention_style = attention_style
 
-    def forward(self, x, B, T, n, ec):
+    def forward(self, x, B, T, n, ec, drop_seeds=None):
+        """`drop_seeds` = (seed_space, seed_mlp, seed_dev): this forward's stochastic-depth seeds (SpaceTimeTransformer._seed); without
+        them, in eval() and at drop_path == 0 the block is the deterministic one."""
         # which Linears of THIS block run one fp16 product in the f16x2 mode: the model's precision policy (ops.single_product_policy)
         single = ec.f16_single_mask(getattr(self, "layer_index", None), getattr(self, "depth", None)) if ec.fwd_passes == 2 else 0
         geom = (B, T, n, self.num_heads, self.norm1.eps, single)
-        fn = _SpaceTimeBlockCFn if block_calls_ok(ec, B * (1 + T * n), x.shape[-1], self.mlp.fc1.weight.shape[0]) else _SpaceTimeBlockFn
+        if self.training and self.drop_path > 0.:
+            if drop_seeds is None:
+                raise ValueError("SpaceTimeBlock: a train-mode forward with drop_path > 0 needs its seeds (drop_seeds)")
+            geom = geom + ((self.drop_path,) + tuple(drop_seeds),)
+        fn = _SpaceTimeBlockCFn if block_calls_ok(ec, B * (1 + T * n), x.shape[-1], self.mlp.fc1.weight.shape[0], drop_path=len(geom) > 6) \
+            else _SpaceTimeBlockFn
         return fn.apply(
             x, geom, ec,
             self.norm3.weight, self.norm3.bias, self.timeattn.qkv.weight, self.timeattn.qkv.bias,
@@ -483,8 +509,10 @@ class SpaceTimeTransformer(nn.Module):
         super().__init__()
         if hybrid_backbone is not None:
             raise NotImplementedError('hybrid backbone not implemented')       # :231
-        if drop_rate != 0. or attn_drop_rate != 0. or drop_path_rate != 0.:
-            raise NotImplementedError("non-zero video drop rates are not on the EgoClip hot path (model/model.py:49-51)")
+        if drop_rate != 0. or attn_drop_rate != 0.:
+            raise NotImplementedError("element-wise dropout is not in the video tower (stochastic depth is: drop_path_rate)")
+        if not 0. <= drop_path_rate < 1.:
+            raise ValueError("drop_path_rate is a probability in [0, 1)")
         if representation_size:
             raise NotImplementedError("representation_size (pre_logits) is not on the EgoClip hot path")
         self.num_classes = num_classes
@@ -498,11 +526,13 @@ class SpaceTimeTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patches_per_frame + 1, embed_dim))
         self.temporal_embed = nn.Parameter(torch.zeros(1, num_frames, embed_dim))
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]     # :246, stochastic depth decay rule
+        self.drop_path_rate, self.dpr = float(drop_path_rate), dpr
         self.blocks = nn.ModuleList([
             SpaceTimeBlock(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                           qk_scale=qk_scale, norm_layer=norm_layer, time_init=time_init,
+                           qk_scale=qk_scale, drop_path=dpr[i], norm_layer=norm_layer, time_init=time_init,
                            attention_style=attention_style)
-            for _ in range(depth)])
+            for i in range(depth)])
         for i, blk in enumerate(self.blocks):
             blk.layer_index, blk.depth = i, depth     # the precision policy is per block (ExecContext.f16_single_mask)
         self.norm = norm_layer(embed_dim)
@@ -513,6 +543,24 @@ class SpaceTimeTransformer(nn.Module):
         if num_frames == 1:                                                    # :272-273
             self.apply(self._init_weights)
         self.exec_ctx = ops.new_context()     # FrozenInTime replaces it with the dual encoder's shared context
+        # stochastic-depth seeds, as the text tower's dropout seeds (text_transformer.DistilBertModel): a call counter advanced by every
+        # train-mode forward that drops paths, the data-parallel rank, an optional capture-safe device word XOR-ed in by the kernels
+        # (the counter stops while it is set), and a site id per block and branch
+        self._drop_calls = 0
+        self.seed_rank = 0
+        self.seed_device = None
+
+    def _seed(self, site):
+        # 64-bit seed of one drop-path site of one forward call: torch's seed, the call counter, the site id and the rank, mixed
+        x = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xD1B54A32D192ED03 + site * 0x94D049BB133111EB
+             + self.seed_rank * 0xA24BAED4963EE407) & (2 ** 64 - 1)
+        x ^= x >> 31
+        return (x * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+
+    def drop_path_seeds(self, layer):
+        """(seed_space, seed_mlp, seed_dev) of block `layer` at the CURRENT call counter: what its last train-mode forward drew from."""
+        # sites 4096 + ...: apart from the text tower's dropout sites, which share the formula
+        return self._seed(4096 + 2 * layer), self._seed(4097 + 2 * layer), self.seed_device
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -600,8 +648,11 @@ class SpaceTimeTransformer(nn.Module):
         ec = self.exec_ctx
         x = _PatchTokensFn.apply(x, geom, ec, self.patch_embed.proj.weight, self.patch_embed.proj.bias,
                                  self.cls_token, self.pos_embed, self.temporal_embed)
-        for blk in self.blocks:                                                # :325-328
-            x = blk(x, b, curr_frames, n, ec)
+        drops = self.training and any(blk.drop_path > 0. for blk in self.blocks)
+        if drops and self.seed_device is None:
+            self._drop_calls += 1                                              # fresh draws in every train-mode forward
+        for li, blk in enumerate(self.blocks):                                 # :325-328
+            x = blk(x, b, curr_frames, n, ec, self.drop_path_seeds(li) if drops and blk.drop_path > 0. else None)
         x = _ClsNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, ec)   # :330
         return self.pre_logits(x)
 

@@ -1145,6 +1145,39 @@ def dropout(x, p, seed, add=None, seed_dev=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ stochastic depth
+def drop_path_scales(B, p, seed, seed_dev=None, device="cuda"):
+    """-> fp32 [B]: the per-sample scales s[b] in {0, 1 / (1 - p)} of one drop-path site (egv_drop_path_scales)."""
+    _need_cuda(seed_dev)
+    out = torch.empty(int(B), dtype=torch.float32, device=device)
+    _need_cuda(out)
+    check(_lib.lib().egv_drop_path_scales(int(B), float(p), int(seed), _p(seed_dev), _p(out), _stream(out)), "egv_drop_path_scales")
+    return out
+
+
+def drop_path_add(y, resid, rows_per_sample, p, seed, seed_dev=None, out=None):
+    """out[m, :] = resid[m, :] + s[m // rows_per_sample] * y[m, :] (contiguous fp32 [rows, cols]); `out` defaults to `y` (in place)."""
+    _need_cuda(y, resid, out, seed_dev)
+    out = y if out is None else out
+    rows, cols = y.shape
+    if resid.shape != y.shape or out.shape != y.shape or not (y.is_contiguous() and resid.is_contiguous() and out.is_contiguous()):
+        raise ValueError("drop_path_add: y, resid and out are contiguous fp32 [rows, cols] of one shape")
+    check(_lib.lib().egv_drop_path_add(_p(y), _p(resid), _p(out), rows, cols, int(rows_per_sample), float(p), int(seed), _p(seed_dev),
+                                       _stream(y)), "egv_drop_path_add")
+    return out
+
+
+def drop_path_grad(g2d, rows_per_sample, p, seed, passes, seed_dev=None) -> Planes:
+    """The operand planes of s[m // rows_per_sample] * g2d[m, :] for a backward of `passes` products: 1 / 3 split-bf16 (as split_f32),
+    4 one plane of un-clamped fp16 (as f16_cast)."""
+    _need_cuda(g2d, seed_dev)
+    rows, cols = g2d.shape
+    pl = empty_planes_f16x2(rows, cols, g2d.device, single=True) if passes == 4 else empty_planes(rows, cols, passes, g2d.device)
+    check(_lib.lib().egv_drop_path_grad(_p(g2d), g2d.stride(0), rows, cols, int(rows_per_sample), float(p), int(seed), _p(seed_dev),
+                                        int(passes), _p(pl.hi), _p(pl.lo), pl.ld, _stream(g2d)), "egv_drop_path_grad")
+    return pl
+
+
 def embed_fwd(ids, word, pos, D):
     B, L = ids.shape
     e = torch.empty((B * L, D), dtype=torch.float32, device=word.device)

@@ -45,8 +45,8 @@ def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, ra
 
     Replay: the gradient of the head is taken at the embeddings of pass 1 and applied through the graph of pass 3, so the two passes
     must compute the same embeddings.  Pass 1 therefore runs the train-mode kernels under no_grad
-    (ExecContext.train_kernels_without_grad) and the text tower's dropout call counter is put back before pass 3 re-encodes a chunk,
-    which regenerates the same counter-based masks.  `check_replay=True` (tests, diagnostics) leaves on the unwrapped model
+    (ExecContext.train_kernels_without_grad) and the call counters of the text tower's dropout and of the video tower's stochastic
+    depth are put back before pass 3 re-encodes a chunk, which regenerates the same counter-based masks.  `check_replay=True` (tests, diagnostics) leaves on the unwrapped model
     `last_replay_max_abs_diff` -- a device scalar, max over chunks of |pass-3 embedding - cached row| -- and `last_cached_embeddings`
     (text, video), the two [B, D] caches of the step (kept alive until the next such step; not set without `check_replay`).
     `fused_head=False`: the head takes the reference's own decomposition (sim_matrix + loss.forward), as in `egoclip_step`.
@@ -71,7 +71,7 @@ def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, ra
     t_cache = v_cache = None
     with torch.no_grad(), (ec.train_kernels_without_grad() if ec is not None else contextlib.nullcontext()):
         for lo, hi in spans:
-            counters.append(getattr(text_model, '_drop_calls', None))
+            counters.append((getattr(text_model, '_drop_calls', None), getattr(video_model, '_drop_calls', None)))
             text_k, video_k = encode(lo, hi)
             if t_cache is None:
                 t_cache = torch.empty((B, text_k.shape[1]), dtype=torch.float32, device=text_k.device)
@@ -98,8 +98,9 @@ def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, ra
         # None when a chunk's backward starts, so the wgrad side streams, the gradient planes and AccumulateGrad's steal path behave as
         # in the plain step; the first chunk's gradient tensors become the accumulators.
         for k, (lo, hi) in enumerate(spans):
-            if counters[k] is not None:
-                text_model._drop_calls = counters[k]
+            for tower, calls in zip((text_model, video_model), counters[k]):
+                if calls is not None:
+                    tower._drop_calls = calls
             text_k, video_k = encode(lo, hi)
             if check_replay:
                 with torch.no_grad():

@@ -371,6 +371,24 @@ int egv_zero(void* p, int64_t bytes, void* stream);
 int egv_dropout(const float* x, const float* add, float* out, int64_t n, float p, uint64_t seed, const uint64_t* seed_dev,
                 void* stream);
 
+/* ---- stochastic depth of the SpaceTimeBlock (timm DropPath with scale_by_keep, model/video_transformer.py:155,171,175) ----------
+ * One Bernoulli(1 - p) draw per SAMPLE and residual branch: s[b] = keep(seed, b) ? 1 / (1 - p) : 0 -- the counter-based mask of
+ * egv_dropout with the element index set to the sample number b (p == 0: all ones).  A pure function of (p, seed ^ *seed_dev, b):
+ * nothing is stored, the backward regenerates the forward's draws; seed_dev as in egv_text_attn_fwd.  0 <= p < 1.
+ * egv_drop_path_scales: out[b] = s[b], b < B (tests, logging, reference helpers).                                                 */
+int egv_drop_path_scales(int32_t B, float p, uint64_t seed, const uint64_t* seed_dev, float* out, void* stream);
+/* out[m, :] = resid[m, :] + s[m / rows_per_sample] * y[m, :] on contiguous fp32 [rows, cols] (cols % 4 == 0, 16-byte aligned,
+ * rows * cols / 4 < 2^31 - 2^19); `out` may be `y`.  The product and the sum are rounded separately (= `resid + s * y` of any fp32
+ * host); rows of a dropped sample are copies of resid and y is not read for them.                                                 */
+int egv_drop_path_add(const float* y, const float* resid, float* out, int32_t rows, int32_t cols, int32_t rows_per_sample,
+                      float p, uint64_t seed, const uint64_t* seed_dev, void* stream);
+/* The backward: the operand planes of s[m / rows_per_sample] * g[m, :] (g fp32 [rows, ldg], cols % 8 == 0, ldg % 4 == 0,
+ * ldo % 8 == 0, 16-byte aligned), the product rounded to fp32 first.  passes 1 / 3: split-bf16 hi[, lo] planes, bit for bit what
+ * egv_split_f32 writes from the scaled matrix; passes 4: ONE plane of un-clamped fp16 in `hi` (lo unused), bit for bit
+ * egv_f16x2_encode role 2.                                                                                                        */
+int egv_drop_path_grad(const float* g, int64_t ldg, int32_t rows, int32_t cols, int32_t rows_per_sample, float p, uint64_t seed,
+                       const uint64_t* seed_dev, int32_t passes, uint16_t* hi, uint16_t* lo, int64_t ldo, void* stream);
+
 /* ---- contrastive head ---------------------------------------------------------------------------------
  * sim_matrix x3 + EgoNCE/NormSoftmaxLoss forward AND backward in one launch
  * (model/model.py:189-197; model/loss.py:13-25,34-53; trainer/trainer_egoclip.py:130-137).
