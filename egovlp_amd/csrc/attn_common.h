@@ -270,3 +270,61 @@ struct AttGroup {
     return MODE == MODE_SPACE ? (j == 0 ? tok0 : tok0 + (long)f * g.n + j) : tok0 + j;
   }
 };
+
+// ---- backward: gradient-side arguments and the two helpers shared by attn_mfma_bwd.hip and attn_long.hip ---------------------
+struct AttGrad {
+  float* dq;           // MODE_TEXT: fp32 outputs
+  float* dk;
+  float* dv;
+  bf16_t* gh;          // MODE_SPACE: dqkv as split-bf16 planes [B, S, 3, H, 64] (gl == nullptr: hi only)
+  bf16_t* gl;
+  long tok_stride;     // elements between tokens in dq/dk/dv (or in the gradient planes)
+  const float* d_out;  // MODE_TEXT: [B, S, H*64] fp32
+  const bf16_t* doh;   // MODE_SPACE: d_out planes
+  const bf16_t* dol;
+  long do_stride;
+  const bf16_t* oh;    // MODE_SPACE: the forward's attention output planes (delta = rowsum(dO o O) in the streaming dQ kernel)
+  const bf16_t* ol;
+  const float* lse;    // [B, H, S]
+  float* delta;        // [B, H, S] workspace (written by dQ kernel, read by dKV kernel; slot 0 = the CLS row's delta,
+                       //  precomputed by egv_attn_cls_delta in MODE_SPACE)
+  float* dcls;         // MODE_SPACE: [B, H, 3, 64] fp32 accumulators of the CLS token's raw dq / dk / dv (zeroed first)
+  int o_fmt;           // MODE_SPACE: format of the forward's output planes (attn_common.h ATT_OUT_*)
+  int g_fmt;           // MODE_SPACE: format of the gradient planes: 0 = split-bf16 (hi[, lo]), ATT_GRAD_F16 = ONE plane of un-clamped fp16
+};
+
+__device__ __forceinline__ void store_planes4(bf16_t* hi, bf16_t* lo, long off, f32x4_t v, int fmt = 0) {
+  uint32_t h0, h1, l0, l1;
+  att_out2(v[0], v[1], fmt, h0, l0);
+  att_out2(v[2], v[3], fmt, h1, l1);
+  egv_store<EGV_NT_SPACE_ATTN>(hi + off, (u32x2_t){h0, h1});
+  if (lo) egv_store<EGV_NT_SPACE_ATTN>(lo + off, (u32x2_t){l0, l1});
+}
+
+// a = dO (split-bf16), b = O in the format the forward wrote it (b_fmt: ATT_OUT_*)
+template <bool F16 = false>
+__device__ __forceinline__ float frag_dot8(bf16x8_t ah, bf16x8_t al, bool a_lo, bf16x8_t bh, bf16x8_t bl, bool b_lo, int b_fmt) {
+  const u32x4_t a0 = __builtin_bit_cast(u32x4_t, ah), a1 = __builtin_bit_cast(u32x4_t, al);
+  const u32x4_t b0 = __builtin_bit_cast(u32x4_t, bh), b1 = __builtin_bit_cast(u32x4_t, bl);
+  float acc = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float ax, ay, bx, by;
+    if constexpr (F16) {
+      f16x2_unpack(a0[e], ax, ay);           // dO as an fp16 plane (the fp16 attention backward)
+    } else {
+      ax = __uint_as_float(a0[e] << 16), ay = __uint_as_float(a0[e] & 0xffff0000u);
+      if (a_lo) { ax += __uint_as_float(a1[e] << 16); ay += __uint_as_float(a1[e] & 0xffff0000u); }
+    }
+    att_o_unpack(b0[e], b1[e], b_lo, b_fmt, bx, by);
+    acc += ax * bx + ay * by;
+  }
+  return acc;
+}
+
+
+// Key-tiled ("long") kernels for groups of more than 288 keys (attn_long.hip); `mode` is MODE_SPACE or MODE_TEXT.  They take over
+// where dispatch_fwd / dispatch_bwd of the LDS-resident kernels end and accept / reject the same precision combinations.
+int egv_attn_long_fwd(int mode, const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
+                      float* cls_ws, hipStream_t s);
+int egv_attn_long_bwd(int mode, const AttGeom& g, const AttGrad& gr, int ngroups, int passes, hipStream_t s);

@@ -16,35 +16,6 @@
 
 namespace {
 
-struct AttGrad {
-  float* dq;           // MODE_TEXT: fp32 outputs
-  float* dk;
-  float* dv;
-  bf16_t* gh;          // MODE_SPACE: dqkv as split-bf16 planes [B, S, 3, H, 64] (gl == nullptr: hi only)
-  bf16_t* gl;
-  long tok_stride;     // elements between tokens in dq/dk/dv (or in the gradient planes)
-  const float* d_out;  // MODE_TEXT: [B, S, H*64] fp32
-  const bf16_t* doh;   // MODE_SPACE: d_out planes
-  const bf16_t* dol;
-  long do_stride;
-  const bf16_t* oh;    // MODE_SPACE: the forward's attention output planes (delta = rowsum(dO o O) in the streaming dQ kernel)
-  const bf16_t* ol;
-  const float* lse;    // [B, H, S]
-  float* delta;        // [B, H, S] workspace (written by dQ kernel, read by dKV kernel; slot 0 = the CLS row's delta,
-                       //  precomputed by egv_attn_cls_delta in MODE_SPACE)
-  float* dcls;         // MODE_SPACE: [B, H, 3, 64] fp32 accumulators of the CLS token's raw dq / dk / dv (zeroed first)
-  int o_fmt;           // MODE_SPACE: format of the forward's output planes (attn_common.h ATT_OUT_*)
-  int g_fmt;           // MODE_SPACE: format of the gradient planes: 0 = split-bf16 (hi[, lo]), ATT_GRAD_F16 = ONE plane of un-clamped fp16
-};
-
-__device__ __forceinline__ void store_planes4(bf16_t* hi, bf16_t* lo, long off, f32x4_t v, int fmt = 0) {
-  uint32_t h0, h1, l0, l1;
-  att_out2(v[0], v[1], fmt, h0, l0);
-  att_out2(v[2], v[3], fmt, h1, l1);
-  egv_store<EGV_NT_SPACE_ATTN>(hi + off, (u32x2_t){h0, h1});
-  if (lo) egv_store<EGV_NT_SPACE_ATTN>(lo + off, (u32x2_t){l0, l1});
-}
-
 // ------------------------------------------------------------------------------------------------ dQ
 // MODE_SPACE: operands are planes; the clip's CLS query rides as query row n (see attn_mfma_fwd.hip): its L and delta
 // are the GLOBAL ones (lse[b,h,0], delta[b,h,0]); its dq partial over this frame's keys is accumulated atomically.
@@ -191,27 +162,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const AttGeom g, const
 // query's dO row with the forward's output row -- so here it is computed up front from the O planes and the keys are walked
 // in 32-key chunks with nothing but the dQ accumulators live: under 128 VGPRs, i.e. two 8-wave workgroups per CU in
 // single-pass mode (the staging of one hides under the tiles of the other) and 16 waves per workgroup in three-pass mode.
-// a = dO (split-bf16), b = O in the format the forward wrote it (b_fmt: ATT_OUT_*)
-template <bool F16 = false>
-__device__ __forceinline__ float frag_dot8(bf16x8_t ah, bf16x8_t al, bool a_lo, bf16x8_t bh, bf16x8_t bl, bool b_lo, int b_fmt) {
-  const u32x4_t a0 = __builtin_bit_cast(u32x4_t, ah), a1 = __builtin_bit_cast(u32x4_t, al);
-  const u32x4_t b0 = __builtin_bit_cast(u32x4_t, bh), b1 = __builtin_bit_cast(u32x4_t, bl);
-  float acc = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float ax, ay, bx, by;
-    if constexpr (F16) {
-      f16x2_unpack(a0[e], ax, ay);           // dO as an fp16 plane (the fp16 attention backward)
-    } else {
-      ax = __uint_as_float(a0[e] << 16), ay = __uint_as_float(a0[e] & 0xffff0000u);
-      if (a_lo) { ax += __uint_as_float(a1[e] << 16); ay += __uint_as_float(a1[e] & 0xffff0000u); }
-    }
-    att_o_unpack(b0[e], b1[e], b_lo, b_fmt, bx, by);
-    acc += ax * bx + ay * by;
-  }
-  return acc;
-}
-
 template <int NKF, int PASSES, bool F16 = false>
 __global__ __launch_bounds__(PASSES == 3 ? 1024 : 512) void attn_bwd_dq_stream_kernel(const AttGeom g, const AttGrad gr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -715,7 +665,7 @@ int dispatch_bwd(const AttGeom& g, const AttGrad& gr, int ngroups, int passes, h
   if (m <= 64) return launch_bwd<MODE, 4>(g, gr, ngroups, passes, s);
   if (m <= 224) return launch_bwd<MODE, 14>(g, gr, ngroups, passes, s);
   if (m <= 288) return launch_bwd<MODE, 18>(g, gr, ngroups, passes, s);
-  return EGV_ERR_ARG;
+  return egv_attn_long_bwd(MODE, g, gr, ngroups, passes, s);      // key- and query-tiled kernels (attn_long.hip): no upper bound
 }
 
 }  // namespace

@@ -534,7 +534,8 @@ int launch_fwd(const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol
 }  // namespace
 
 // dispatch on the padded key count (NKF 16-key fragments, even): 2 (<=32 keys: DistilBERT L<=32 and the
-// tiny test configs), 4, 14 (ViT-B/16: 197 keys), 18 (ViT-L/14: 257 keys)
+// tiny test configs), 4, 14 (ViT-B/16: 197 keys), 18 (ViT-L/14: 257 keys); more than 288 keys (higher input resolutions, long captions)
+// go to the key-tiled online-softmax kernel of attn_long.hip
 template <int MODE>
 static int dispatch_fwd(const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
                         float* cls_ws, hipStream_t s) {
@@ -542,7 +543,7 @@ static int dispatch_fwd(const AttGeom& g, int ngroups, int passes, bf16_t* oh, b
   if (g.nk <= 64) return launch_fwd<MODE, 4>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
   if (g.nk <= 224) return launch_fwd<MODE, 14>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
   if (g.nk <= 288) return launch_fwd<MODE, 18>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
-  return EGV_ERR_ARG;
+  return egv_attn_long_fwd(MODE, g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);      // key-tiled kernel (attn_long.hip): no upper bound
 }
 
 int egv_attn_space_fwd_impl(const bf16_t* qkv_hi, const bf16_t* qkv_lo, int B, int T, int n, int H, int passes,

@@ -93,11 +93,16 @@ class BaseModel(nn.Module):
 
 class FrozenInTime(BaseModel):
     def __init__(self, video_params, text_params, projection_dim=256, load_checkpoint=None,
-                 projection='minimal', load_temporal_fix='zeros'):
+                 projection='minimal', load_temporal_fix='zeros', load_spatial_fix=None):
         super().__init__()
         self.video_params = video_params
         self.text_params = text_params
         self.load_temporal_fix = load_temporal_fix
+        # extension (the reference raises for a checkpoint of another patch grid): None keeps that behaviour; 'bicubic' / 'bilinear'
+        # resize the checkpoint's pos_embed grid to this model's (_inflate_positional_embeds)
+        if load_spatial_fix not in (None, 'bicubic', 'bilinear'):
+            raise ValueError("load_spatial_fix is None, 'bicubic' or 'bilinear'")
+        self.load_spatial_fix = load_spatial_fix
         if not text_params['pretrained']:
             raise NotImplementedError("Huggingface text models require pretrained init.")       # :27-28
         if self.text_params['model'].startswith('distilbert'):
@@ -116,12 +121,15 @@ class FrozenInTime(BaseModel):
             # extension key (the reference's configs carry none and build rate 0): stochastic depth of the video tower, the usual
             # ViT fine-tuning regulariser (0.1 - 0.2); SpaceTimeTransformer(drop_path_rate=...) as in the reference's class
             drop_path_rate = video_params.get('drop_path_rate', 0.)
+            # extension key (the reference's configs carry none and build 224): the input resolution, an int or (height, width) --
+            # fine-tuning and evaluation at 288 / 336 / 384 / 448; the pos_embed grid is img_size // patch_size per side
+            img_size = video_params.get('img_size', 224)
             if arch_config == 'base_patch16_224':
-                model = SpaceTimeTransformer(num_frames=num_frames, time_init=time_init,
+                model = SpaceTimeTransformer(img_size=img_size, num_frames=num_frames, time_init=time_init,
                                              attention_style=attention_style, drop_path_rate=drop_path_rate)
                 vit_path = "pretrained/jx_vit_base_p16_224-80ecf9dd.pth"
             elif arch_config == 'large_patch14_224':          # extension: BASELINE config 5
-                model = SpaceTimeTransformer(patch_size=14, embed_dim=1024, depth=24, num_heads=16,
+                model = SpaceTimeTransformer(img_size=img_size, patch_size=14, embed_dim=1024, depth=24, num_heads=16,
                                              num_frames=num_frames, time_init=time_init,
                                              attention_style=attention_style, drop_path_rate=drop_path_rate)
                 vit_path = None
@@ -295,10 +303,28 @@ class FrozenInTime(BaseModel):
                         raise NotImplementedError
                 new_state_dict['video_model.temporal_embed'] = new_temporal_embed
         if 'video_model.pos_embed' in new_state_dict and 'video_model.pos_embed' in curr_keys:
-            if new_state_dict['video_model.pos_embed'].shape[1] != self.state_dict()['video_model.pos_embed'].shape[1]:
-                raise NotImplementedError(
-                    'Loading models with different spatial resolution / patch number not yet implemented, sorry.')
+            load_pos_embed = new_state_dict['video_model.pos_embed']
+            if load_pos_embed.shape[1] != self.state_dict()['video_model.pos_embed'].shape[1]:
+                if self.load_spatial_fix is None:
+                    raise NotImplementedError(
+                        'Loading models with different spatial resolution / patch number not yet implemented, sorry.')
+                new_state_dict['video_model.pos_embed'] = self._resize_pos_embed(load_pos_embed)
         return new_state_dict
+
+    def _resize_pos_embed(self, load_pos_embed):
+        """The usual ViT rule for a checkpoint of another patch grid (extension, `load_spatial_fix`): the CLS position is kept as it
+        is; the grid rows, reshaped to (gh_old, gw_old, D), are interpolated to this model's (gh, gw) = img_size // patch_size.  The
+        checkpoint's grid is taken as square (the reference trains square inputs only)."""
+        pe = self.video_model.patch_embed
+        gh, gw = pe.img_size[0] // pe.patch_size[0], pe.img_size[1] // pe.patch_size[1]
+        n_old, D = load_pos_embed.shape[1] - 1, load_pos_embed.shape[2]
+        g_old = int(round(n_old ** 0.5))
+        if g_old * g_old != n_old:
+            raise NotImplementedError(f'load_spatial_fix: the checkpoint\'s pos_embed has {n_old} grid rows, not a square grid')
+        grid = load_pos_embed[:, 1:].reshape(1, g_old, g_old, D).permute(0, 3, 1, 2)
+        grid = F.interpolate(grid.float(), size=(gh, gw), mode=self.load_spatial_fix, align_corners=False)
+        grid = grid.permute(0, 2, 3, 1).reshape(1, gh * gw, D).to(load_pos_embed.dtype)
+        return torch.cat([load_pos_embed[:, :1], grid], dim=1)
 
 
 class _SimMatrixFn(torch.autograd.Function):

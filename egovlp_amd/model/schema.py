@@ -11,7 +11,8 @@ def video_schema(embed_dim=768, depth=12, patch_size=16, in_chans=3, img_size=22
                  mlp_ratio=4.0, prefix="video_model."):
     D = embed_dim
     Hd = int(D * mlp_ratio)
-    n = (img_size // patch_size) ** 2
+    ih, iw = (img_size, img_size) if isinstance(img_size, int) else img_size       # FrozenInTime's video_params['img_size']
+    n = (ih // patch_size) * (iw // patch_size)
     s = OrderedDict()
     s[prefix + "cls_token"] = (1, 1, D)
     s[prefix + "pos_embed"] = (1, n + 1, D)
@@ -49,8 +50,12 @@ def text_schema(vocab=30522, max_pos=512, dim=768, n_layers=6, hidden=3072, pref
     return s
 
 
-def state_dict_schema(projection_dim=256, **video_kw):
-    """Full FrozenInTime schema in the reference's registration order (model/model.py:31-86)."""
+def state_dict_schema(projection_dim=256, load_spatial_fix=None, **video_kw):
+    """Full FrozenInTime schema in the reference's registration order (model/model.py:31-86).  The two extension keys of the
+    high-resolution path are accepted: `img_size` (int or (height, width)) sets the pos_embed grid; `load_spatial_fix` only says how a
+    checkpoint of another grid is resized at load time and changes no shape."""
+    if load_spatial_fix not in (None, 'bicubic', 'bilinear'):
+        raise ValueError("load_spatial_fix is None, 'bicubic' or 'bilinear'")
     s = OrderedDict()
     s.update(text_schema())
     s.update(video_schema(**video_kw))

@@ -317,6 +317,10 @@ int egv_assemble_tokens_bwd(const float* dx, int32_t B, int32_t T, int32_t n, in
  * keys, bf16 MFMA as well).  The CLS query row (attends to all S keys, :112) rides in every group as an extra query; its
  * partials are merged by a small combine kernel.  Output: split planes [B, S, H*64]; lse [B, H, S] (log-sum-exp of each
  * query row, saved for backward).  `work`: egv_divided_attn_fwd_work_floats(...) floats.
+ * Sizes: space groups of up to 288 keys (n <= 287: ViT-B/16 and ViT-L/14 at 224^2) keep K / V of a group in LDS; larger n (288^2 ..
+ * 448^2 inputs) runs key-tiled kernels (64-key tiles, online softmax; the backward tiles keys and queries) with the same arguments,
+ * workspaces, precision combinations and output formats.  No structural upper bound on n (S = 1 + T*n must fit int32); largest
+ * size tested: n = 784 (785 keys).  head dim 64 only.
  * mode bits 1-2 (mode = 2 fmt + (0 space | 1 time); fmt != 0 with passes == 3 only) = the format of the output planes:
  *   0  split-bf16 (out_hi = bf16(v), out_lo = bf16(v - out_hi)): a three-product proj;
  *   1  out_hi = bf16(v) (what a bf16 backward reads), out_lo = fp16(v): the operand of a proj Linear that runs ONE fp16 product;
@@ -350,7 +354,8 @@ int egv_embed_bwd(const int64_t* ids, const float* d_e, int32_t B, int32_t L, in
                   float* d_word, float* d_pos, void* stream);
 /* Masked multi-head attention (modeling_distilbert.py:122-203) on separate q,k,v [B, L, H*64] fp32;
  * mask [B, L] int64 (0 = padded key -> -inf).  Output split planes [B, L, H*64]; probs are recomputed
- * in backward from lse [B,H,L].                                                                     */
+ * in backward from lse [B,H,L].  L <= 288 runs the LDS-resident kernels, longer sequences the key-tiled ones (same
+ * arguments, same dropout mask function); no structural upper bound on L, largest size tested 512 (DistilBERT's positions). */
 int egv_text_attn_fwd(const float* q, const float* k, const float* v, int64_t ldqkv, const int64_t* mask, int32_t B,
                       int32_t L, int32_t H, int32_t passes, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
                       egv_bf16* out_hi, egv_bf16* out_lo, float* lse, void* stream);
