@@ -115,6 +115,8 @@ PROTOTYPES = {
     "egv_drop_path_grad": (i32, [c_p, i64, i32, i32, i32, f32, u64, c_p, i32, c_p, c_p, i64, c_p]),
     "egv_egonce_fwd_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, f32, f32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_egonce_work_floats": (i64, [i32, i32]),
+    "egv_egonce_long_fwd_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, f32, f32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
+    "egv_egonce_long_work_floats": (i64, [i32, i32, i32, i32]),
     "egv_sim_matrix_fwd": (i32, [c_p, c_p, i32, i32, i32, f32, c_p, c_p, c_p, c_p, c_p]),
     "egv_sim_matrix_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, f32, c_p, c_p, c_p]),
     "egv_egonce_from_sim": (i32, [c_p, c_p, c_p, i32, f32, i32, i32, c_p, c_p, c_p, c_p]),

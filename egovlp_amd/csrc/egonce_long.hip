@@ -1,0 +1,517 @@
+// Contrastive head for global batches past the 1 024 rows of egonce.hip: the same loss and the same gradients
+// (egonce.hip:8-11), with nothing of size n x n in memory.  The similarity tile X = A_I . B_J^T is formed on the fp32-input
+// MFMA (v_mfma_f32_16x16x4_f32: bit for bit an fp32 fma chain, so the numerics are those of the fp32 short head), the EgoNCE
+// mask comes from bit-packed noun / verb rows, and the row statistics are kept online while the column tiles stream through
+// LDS.  All arithmetic fp32; every reduction runs in a fixed order (no float atomics), so a call is deterministic.
+//
+//   prep    one workgroup per row: |t|, |v|, the normalised rows tn / vn zero-padded from D to Dp (64 or 256), and the
+//           noun / verb rows packed into bit words (bit = entry > 0; each part padded to a multiple of 4 words).  Rows
+//           n .. np - 1 (np = n rounded up to 64) are written as zeros, so no tile load needs a bound.  A negative or NaN
+//           noun / verb entry sets the row's flag; the loss kernel turns any flag into a NaN loss (no host sync).
+//   stats   workgroup = (64 rows of A, a range of 64-row tiles of B); a wave owns 16 rows and keeps their operand in
+//           registers.  Per tile: X^T fragments, the 64 x 64 mask tile from AND / OR of the packed words, and per lane the
+//           running maximum, Z = sum a and P = sum m a, rescaled online.  Launched twice: (tn, vn) gives the row statistics
+//           of the loss; (vn, tn) gives the column statistics, because the mask is symmetric:
+//             m_ij = (rows i, j share a noun AND share a verb) OR i == j        (use_noun only: share a noun; else verb)
+//           which under the data contract -- noun / verb are non-negative multi-hots -- is sim_v * sim_n + I > 0.
+//   loss    one workgroup: merges the column-range partials of both directions in a fixed order, writes the final statistics
+//           and sums the n loss terms in double.
+//   grad    the stats walk again; G_IJ = -1/(n tau) [m a_r / P_i - a_r / Z_i + m a_c / Q_j - a_c / C_j] is formed in the
+//           registers of the X^T fragment, which IS the operand layout of the next product (lane = row i, lane group = k),
+//           so dA_I += G_IJ . B_J runs on the same MFMA with B_J read from the LDS tile.  Launched twice with the roles
+//           swapped; raw partials per column range go to the workspace.
+//   finish  one workgroup per row: sums the partials in a fixed order and applies the backward of the normalisation
+//           (egonce.hip:281-282).
+//
+// k order.  The 16x16x4 MFMA takes k = lane >> 4 from each lane.  A lane reads FOUR consecutive floats (one 16-byte LDS read)
+// and feeds element t to MFMA t, so MFMA t of chunk c sums k = 16 c + 4 (lane >> 4) + t; both operands use the same map, which
+// only permutes the order of the fma chain.  The second product uses the same trick on the OUTPUT column: MFMA t of a 64-wide
+// chunk produces d = 64 c + 4 (lane & 15) + t, so a lane ends with four consecutive d and stores 16 bytes.
+#include "common.h"
+#include "egovlp_hip.h"
+
+namespace {
+
+constexpr int EGL_TILE = 64;          // rows per tile (A rows per workgroup, B rows per LDS tile)
+constexpr int EGL_STAT_WGS = 512;     // column ranges are chosen so that a launch has about this many workgroups (2 per CU)
+constexpr int EGL_GRAD_WGS = 256;     // the gradient's partials cost memory and a pass: half as many
+constexpr float EGL_NEG = -3e38f;
+
+__device__ __forceinline__ float egl_block_sum(float v, float* sh) {  // 256 threads
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+struct EglLayout {
+  int np, Dp, wn, W, ntiles, tps_s, ns_s, tps_g, ns_g;
+  long tn, vn, words, norms, flags, spart, stat, gpart, total;   // offsets in floats
+};
+
+inline void egl_split(int ntiles, int target, int& tps, int& ns) {
+  int want = (target + ntiles - 1) / ntiles;
+  if (want > ntiles) want = ntiles;
+  tps = (ntiles + want - 1) / want;
+  ns = (ntiles + tps - 1) / tps;       // no empty range
+}
+
+inline EglLayout egl_layout(int n, int D, int dn, int dv) {
+  EglLayout L;
+  L.np = (n + EGL_TILE - 1) / EGL_TILE * EGL_TILE;
+  L.Dp = D <= 64 ? 64 : 256;                         // the two widths the tile kernels are compiled for
+  L.wn = ((dn + 31) / 32 + 3) / 4 * 4;
+  L.W = L.wn + ((dv + 31) / 32 + 3) / 4 * 4;
+  L.ntiles = L.np / EGL_TILE;
+  egl_split(L.ntiles, EGL_STAT_WGS, L.tps_s, L.ns_s);
+  egl_split(L.ntiles, EGL_GRAD_WGS, L.tps_g, L.ns_g);
+  const long np = L.np;
+  long o = 0;
+  L.tn = o;     o += np * L.Dp;
+  L.vn = o;     o += np * L.Dp;
+  L.words = o;  o += np * L.W;
+  L.norms = o;  o += 2 * np;
+  L.flags = o;  o += np;
+  L.spart = o;  o += 2L * L.ns_s * 3 * np;
+  L.stat = o;   o += 6 * np;
+  L.gpart = o;  o += (long)L.ns_g * np * L.Dp;
+  L.total = o;
+  return L;
+}
+
+// ------------------------------------------------------------------------------------------------ prep
+__global__ __launch_bounds__(256) void egl_prep_kernel(const float* __restrict__ text, const float* __restrict__ video,
+                                                       const float* __restrict__ noun, const float* __restrict__ verb, int n,
+                                                       int np, int D, int Dp, int dn, int dv, int wn, int W, float eps,
+                                                       float* __restrict__ tn, float* __restrict__ vn,
+                                                       uint32_t* __restrict__ words, float* __restrict__ norms,
+                                                       float* __restrict__ flags) {
+  __shared__ float sh[4];
+  const int i = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (i >= n) {                                       // the padding rows of the last tile
+    for (int d = threadIdx.x; d < Dp; d += 256) {
+      tn[(long)i * Dp + d] = 0.f;
+      vn[(long)i * Dp + d] = 0.f;
+    }
+    for (int w = threadIdx.x; w < W; w += 256) words[(long)i * W + w] = 0u;
+    if (threadIdx.x == 0) {
+      norms[i] = 0.f;
+      norms[np + i] = 0.f;
+      flags[i] = 0.f;
+    }
+    return;
+  }
+  float st = 0.f, sv = 0.f;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    const float a = text[(long)i * D + d], b = video[(long)i * D + d];
+    st += a * a;
+    sv += b * b;
+  }
+  const float nt = sqrtf(egl_block_sum(st, sh));
+  const float nv = sqrtf(egl_block_sum(sv, sh));
+  const float ct = fmaxf(nt, eps), cv = fmaxf(nv, eps);
+  for (int d = threadIdx.x; d < Dp; d += 256) {
+    tn[(long)i * Dp + d] = d < D ? text[(long)i * D + d] / ct : 0.f;
+    vn[(long)i * Dp + d] = d < D ? video[(long)i * D + d] / cv : 0.f;
+  }
+  int bad = 0;
+  if (noun) {
+    // 64 entries per wave and step: the ballot of (entry > 0) is two of the row's words
+    for (int base = wave * 64; base < wn * 32; base += 256) {
+      const int c = base + lane;
+      const float e = c < dn ? noun[(long)i * dn + c] : 0.f;
+      bad |= !(e >= 0.f);
+      const unsigned long long b = __ballot(e > 0.f);
+      if (lane == 0) {
+        words[(long)i * W + base / 32] = (uint32_t)b;
+        words[(long)i * W + base / 32 + 1] = (uint32_t)(b >> 32);
+      }
+    }
+    for (int base = wave * 64; base < (W - wn) * 32; base += 256) {
+      const int c = base + lane;
+      const float e = c < dv ? verb[(long)i * dv + c] : 0.f;
+      bad |= !(e >= 0.f);
+      const unsigned long long b = __ballot(e > 0.f);
+      if (lane == 0) {
+        words[(long)i * W + wn + base / 32] = (uint32_t)b;
+        words[(long)i * W + wn + base / 32 + 1] = (uint32_t)(b >> 32);
+      }
+    }
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    norms[i] = nt;
+    norms[np + i] = nv;
+    flags[i] = bad ? 1.f : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ tile pieces
+// B rows j0 .. j0 + 63 -> LDS image [64][DP + 4] (the 4 floats of padding spread the rows over the banks)
+template <int DP>
+__device__ __forceinline__ void egl_stage_tile(float* bt, const float* __restrict__ B, int j0) {
+  constexpr int LD = DP + 4, C4 = DP / 4;
+  for (int idx = threadIdx.x; idx < EGL_TILE * C4; idx += 256) {
+    const int r = idx / C4, c4 = idx % C4;
+    *(f32x4_t*)(bt + r * LD + 4 * c4) = *(const f32x4_t*)(B + (long)(j0 + r) * DP + 4 * c4);
+  }
+}
+
+// The 64 x 64 mask tile, 16 bits per thread: thread (row i0 + (tid & 63), wave q) covers columns j0 + 16 q .. + 15; the words of
+// a column row are wave-uniform.  mode 0: diagonal only; 1: noun AND verb; 2: noun; 3: verb.  mb: [64][4] words.
+__device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words, int W, int wn, int mode, int i0, int j0,
+                                              uint32_t* mb) {
+  const int il = threadIdx.x & 63;
+  const int jq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gi = i0 + il, jb = j0 + jq * 16;
+  uint32_t bits = 0u;
+  if (mode != 0) {
+    uint32_t hn[16], hv[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) hn[jj] = hv[jj] = 0u;
+    const u32x4_t* wi = (const u32x4_t*)(words + (long)gi * W);
+    const int qn = wn >> 2, qa = W >> 2;
+    if (mode != 3)
+      for (int q = 0; q < qn; ++q) {
+        const u32x4_t a = wi[q];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) {
+          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];      // wave-uniform: scalar loads
+          hn[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
+        }
+      }
+    if (mode != 2)
+      for (int q = qn; q < qa; ++q) {
+        const u32x4_t a = wi[q];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) {
+          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];
+          hv[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
+        }
+      }
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      const bool m = mode == 1 ? (hn[jj] != 0u && hv[jj] != 0u) : (mode == 2 ? hn[jj] != 0u : hv[jj] != 0u);
+      bits |= (m ? 1u : 0u) << jj;
+    }
+  }
+  const int dj = gi - jb;
+  if (dj >= 0 && dj < 16) bits |= 1u << dj;
+  mb[il * 4 + jq] = bits;
+}
+
+// X^T fragments of the wave's 16 rows against the LDS tile: x[jf][r] = <A row (lane & 15), B row 16 jf + 4 (lane >> 4) + r>
+template <int DP>
+__device__ __forceinline__ void egl_xt(const float* bt, const f32x4_t (&a)[DP / 16], int li, int g, f32x4_t (&x)[4]) {
+  constexpr int LD = DP + 4;
+#pragma unroll
+  for (int jf = 0; jf < 4; ++jf) x[jf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < DP / 16; ++c) {
+    f32x4_t b[4];
+#pragma unroll
+    for (int jf = 0; jf < 4; ++jf) b[jf] = *(const f32x4_t*)(bt + (jf * 16 + li) * LD + 16 * c + 4 * g);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int jf = 0; jf < 4; ++jf) x[jf] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jf][t], a[c][t], x[jf], 0, 0, 0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ statistics
+template <int DP>
+__global__ __launch_bounds__(256, 2) void egl_stats_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                           const uint32_t* __restrict__ words, int n, int np, int W, int wn,
+                                                           int mode, float inv_tau, int tps,
+                                                           float* __restrict__ part /* [ranges][3][np] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LD = DP + 4;
+  float* bt = (float*)smem;
+  uint32_t* mb = (uint32_t*)(bt + EGL_TILE * LD);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, g = lane >> 4;
+  const int i0 = blockIdx.x * EGL_TILE;
+  const int ntiles = np / EGL_TILE;
+  const int t0 = blockIdx.y * tps, t1 = min(ntiles, t0 + tps);
+  const int gi = i0 + wave * 16 + li;
+
+  f32x4_t a[DP / 16];
+#pragma unroll
+  for (int c = 0; c < DP / 16; ++c) a[c] = *(const f32x4_t*)(A + (long)gi * DP + 16 * c + 4 * g);
+
+  float m = EGL_NEG, Z = 0.f, P = 0.f;                // this lane's share of row gi: the columns 16 jf + 4 g + r of every tile
+#pragma unroll 1
+  for (int t = t0; t < t1; ++t) {
+    const int j0 = t * EGL_TILE;
+    __syncthreads();                                  // every wave is done with the previous tile
+    egl_stage_tile<DP>(bt, B, j0);
+    egl_mask_tile(words, W, wn, mode, i0, j0, mb);
+    __syncthreads();
+    f32x4_t x[4];
+    egl_xt<DP>(bt, a, li, g, x);
+    const u32x4_t mbits = *(const u32x4_t*)(mb + (wave * 16 + li) * 4);
+    float cm = EGL_NEG;
+#pragma unroll
+    for (int jf = 0; jf < 4; ++jf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (j0 + jf * 16 + 4 * g + r < n) cm = fmaxf(cm, x[jf][r]);
+    const float mn = fmaxf(m, cm);
+    const float alpha = __expf((m - mn) * inv_tau);   // first tile: exp(-inf) = 0 and Z, P are 0 anyway
+    float zs = 0.f, ps = 0.f;
+#pragma unroll
+    for (int jf = 0; jf < 4; ++jf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = (j0 + jf * 16 + 4 * g + r < n) ? __expf((x[jf][r] - mn) * inv_tau) : 0.f;
+        zs += e;
+        ps += ((mbits[jf] >> (4 * g + r)) & 1u) ? e : 0.f;
+      }
+    Z = Z * alpha + zs;
+    P = P * alpha + ps;
+    m = mn;
+  }
+  // the four lane groups of a row
+#pragma unroll
+  for (int off = 16; off <= 32; off <<= 1) {
+    const float mo = __shfl_xor(m, off, 64), Zo = __shfl_xor(Z, off, 64), Po = __shfl_xor(P, off, 64);
+    const float M = fmaxf(m, mo);
+    const float s1 = __expf((m - M) * inv_tau), s2 = __expf((mo - M) * inv_tau);
+    Z = Z * s1 + Zo * s2;
+    P = P * s1 + Po * s2;
+    m = M;
+  }
+  if (g == 0 && gi < n) {
+    float* p = part + (long)blockIdx.y * 3 * np;
+    p[gi] = m;
+    p[np + gi] = Z;
+    p[2 * np + gi] = P;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ loss
+__global__ __launch_bounds__(1024) void egl_loss_kernel(const float* __restrict__ spart /* [2][ranges][3][np] */, int ns, int n,
+                                                        int np, float inv_tau, const float* __restrict__ flags,
+                                                        float* __restrict__ stat /* [2][3][np] */, float* __restrict__ loss) {
+  __shared__ double red[1024];
+  double s = 0.0;
+  int bad = 0;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    float term = 0.f;
+    for (int dir = 0; dir < 2; ++dir) {
+      const float* p = spart + (long)dir * ns * 3 * np;
+      float M = EGL_NEG;
+      for (int r = 0; r < ns; ++r) M = fmaxf(M, p[(long)r * 3 * np + i]);
+      float Z = 0.f, P = 0.f;
+      for (int r = 0; r < ns; ++r) {
+        const float w = __expf((p[(long)r * 3 * np + i] - M) * inv_tau);
+        Z += p[((long)r * 3 + 1) * np + i] * w;
+        P += p[((long)r * 3 + 2) * np + i] * w;
+      }
+      float* o = stat + (long)dir * 3 * np;
+      o[i] = M;
+      o[np + i] = Z;
+      o[2 * np + i] = P;
+      term += __logf(P) - __logf(Z);
+    }
+    s += (double)term;
+    bad |= flags[i] != 0.f;
+  }
+  red[threadIdx.x] = s;
+  bad = __syncthreads_or(bad);
+  for (int h = 512; h >= 1; h >>= 1) {                // pairwise, fixed order
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = bad ? __builtin_nanf("") : (float)(-red[0] / (double)n);
+}
+
+// ------------------------------------------------------------------------------------------------ gradient
+template <int DP>
+__global__ __launch_bounds__(256, 2) void egl_grad_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                          const uint32_t* __restrict__ words,
+                                                          const float* __restrict__ own /* [3][np]: statistics of A's rows */,
+                                                          const float* __restrict__ oth /* [3][np]: of B's rows */, int n,
+                                                          int np, int W, int wn, int mode, float inv_tau, float sc, int tps,
+                                                          float* __restrict__ gpart /* [ranges][np][DP] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LD = DP + 4;
+  float* bt = (float*)smem;
+  uint32_t* mb = (uint32_t*)(bt + EGL_TILE * LD);
+  float* cs = (float*)(mb + EGL_TILE * 4);            // [3][64]: max, 1 / Z, 1 / P of the tile's B rows
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, g = lane >> 4;
+  const int i0 = blockIdx.x * EGL_TILE;
+  const int ntiles = np / EGL_TILE;
+  const int t0 = blockIdx.y * tps, t1 = min(ntiles, t0 + tps);
+  const int gi = i0 + wave * 16 + li;
+
+  f32x4_t a[DP / 16];
+#pragma unroll
+  for (int c = 0; c < DP / 16; ++c) a[c] = *(const f32x4_t*)(A + (long)gi * DP + 16 * c + 4 * g);
+  const bool live = gi < n;
+  const float mo = live ? own[gi] : 0.f;
+  const float izo = live ? 1.0f / own[np + gi] : 0.f;
+  const float ipo = live ? 1.0f / own[2 * np + gi] : 0.f;
+
+  f32x4_t acc[DP / 64][4];
+#pragma unroll
+  for (int c = 0; c < DP / 64; ++c)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[c][t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll 1
+  for (int t = t0; t < t1; ++t) {
+    const int j0 = t * EGL_TILE;
+    __syncthreads();
+    egl_stage_tile<DP>(bt, B, j0);
+    egl_mask_tile(words, W, wn, mode, i0, j0, mb);
+    if (threadIdx.x < EGL_TILE) {
+      const int gj = j0 + threadIdx.x;
+      const bool ok = gj < n;
+      cs[threadIdx.x] = ok ? oth[gj] : 0.f;
+      cs[64 + threadIdx.x] = ok ? 1.0f / oth[np + gj] : 0.f;
+      cs[128 + threadIdx.x] = ok ? 1.0f / oth[2 * np + gj] : 0.f;
+    }
+    __syncthreads();
+    f32x4_t x[4];
+    egl_xt<DP>(bt, a, li, g, x);
+    const u32x4_t mbits = *(const u32x4_t*)(mb + (wave * 16 + li) * 4);
+#pragma unroll
+    for (int jf = 0; jf < 4; ++jf) {
+      const f32x4_t cm4 = *(const f32x4_t*)(cs + jf * 16 + 4 * g);
+      const f32x4_t iz4 = *(const f32x4_t*)(cs + 64 + jf * 16 + 4 * g);
+      const f32x4_t ip4 = *(const f32x4_t*)(cs + 128 + jf * 16 + 4 * g);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float xv = x[jf][r];
+        const float eo = __expf((xv - mo) * inv_tau);         // under the maximum of A's row
+        const float ec = __expf((xv - cm4[r]) * inv_tau);     // under the maximum of B's row
+        const float mm = ((mbits[jf] >> (4 * g + r)) & 1u) ? 1.f : 0.f;
+        const float gv = sc * (eo * (mm * ipo - izo) + ec * (mm * ip4[r] - iz4[r]));
+        x[jf][r] = (live && j0 + jf * 16 + 4 * g + r < n) ? gv : 0.f;
+      }
+    }
+    // dA[i][d] += sum_j G[i][j] B[j][d]: x[jf][r] is the A operand of k-step (jf, r) as it stands (k = j = 16 jf + 4 g + r)
+#pragma unroll
+    for (int jf = 0; jf < 4; ++jf)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < DP / 64; ++c) {
+          const f32x4_t bv = *(const f32x4_t*)(bt + (jf * 16 + 4 * g + r) * LD + 64 * c + 4 * li);
+#pragma unroll
+          for (int tt = 0; tt < 4; ++tt) acc[c][tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[jf][r], bv[tt], acc[c][tt], 0, 0, 0);
+        }
+  }
+  // acc[c][tt][rr]: row i0 + 16 wave + 4 g + rr, column 64 c + 4 li + tt
+  float* out = gpart + ((long)blockIdx.y * np + i0 + wave * 16 + 4 * g) * DP + 4 * li;
+#pragma unroll
+  for (int c = 0; c < DP / 64; ++c)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      *(f32x4_t*)(out + (long)rr * DP + 64 * c) = (f32x4_t){acc[c][0][rr], acc[c][1][rr], acc[c][2][rr], acc[c][3][rr]};
+}
+
+// sum of the column-range partials in a fixed order + the backward of the row normalisation (egonce.hip:281-282)
+__global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict__ gpart, int ns, const float* __restrict__ an,
+                                                         const float* __restrict__ norms, int np, int D, int Dp, float eps,
+                                                         float* __restrict__ out) {
+  __shared__ float sh[4];
+  const int i = blockIdx.x, d = threadIdx.x;
+  float gsum = 0.f, th = 0.f;
+  if (d < Dp) {
+    for (int r = 0; r < ns; ++r) gsum += gpart[((long)r * np + i) * Dp + d];
+    th = an[(long)i * Dp + d];
+  }
+  const float proj = egl_block_sum(th * gsum, sh);
+  const float nrm = norms[i];
+  if (d < D) out[(long)i * D + d] = nrm > eps ? (gsum - th * proj) / nrm : gsum / eps;
+}
+
+template <int DP>
+int egl_launch_stats(const EglLayout& L, const float* A, const float* B, const uint32_t* words, int n, int mode, float inv_tau,
+                     float* part, hipStream_t s) {
+  constexpr int lds = EGL_TILE * (DP + 4) * 4 + EGL_TILE * 4 * 4;
+  auto k = egl_stats_kernel<DP>;
+  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  EGV_LAUNCH(k, dim3(L.ntiles, L.ns_s), dim3(256), lds, s, A, B, words, n, L.np, L.W, L.wn, mode, inv_tau, L.tps_s, part);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+template <int DP>
+int egl_launch_grad(const EglLayout& L, const float* A, const float* B, const uint32_t* words, const float* own,
+                    const float* oth, int n, int mode, float inv_tau, float* gpart, hipStream_t s) {
+  constexpr int lds = EGL_TILE * (DP + 4) * 4 + EGL_TILE * 4 * 4 + 3 * EGL_TILE * 4;
+  auto k = egl_grad_kernel<DP>;
+  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  EGV_LAUNCH(k, dim3(L.ntiles, L.ns_g), dim3(256), lds, s, A, B, words, own, oth, n, L.np, L.W, L.wn, mode, inv_tau,
+             -inv_tau / (float)n, L.tps_g, gpart);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+#define EGL_BY_DP(fn, ...) (L.Dp == 64 ? fn<64>(__VA_ARGS__) : fn<256>(__VA_ARGS__))
+
+inline bool egl_args_ok(int n, int D, int dn, int dv) {
+  return n >= 1 && n <= 65536 && D >= 4 && D <= 256 && D % 4 == 0 && dn >= 0 && dv >= 0 && dn <= 65536 && dv <= 65536;
+}
+
+}  // namespace
+
+extern "C" int64_t egv_egonce_long_work_floats(int32_t n, int32_t D, int32_t dn, int32_t dv) {
+  if (!egl_args_ok(n, D, dn, dv)) return 0;
+  return egl_layout(n, D, dn, dv).total;
+}
+
+extern "C" int egv_egonce_long_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb, int32_t n,
+                                       int32_t D, int32_t dn, int32_t dv, float temperature, float eps, int32_t use_noun,
+                                       int32_t use_verb, float* loss, float* d_text, float* d_video, float* work,
+                                       void* stream) {
+  if (!text || !video || !loss || !work) return EGV_ERR_ARG;
+  if ((noun != nullptr) != (verb != nullptr)) return EGV_ERR_ARG;
+  if (!noun) dn = dv = 0;
+  if (!egl_args_ok(n, D, dn, dv) || !(temperature > 0.f)) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const EglLayout L = egl_layout(n, D, dn, dv);
+  float* tn = work + L.tn;
+  float* vn = work + L.vn;
+  uint32_t* words = (uint32_t*)(work + L.words);
+  float* norms = work + L.norms;
+  float* flags = work + L.flags;
+  float* spart = work + L.spart;
+  float* stat = work + L.stat;
+  float* gpart = work + L.gpart;
+  // the mode of egonce_rows_kernel: noun and verb, noun only, else verb (the reference's else-branch)
+  const int mode = !noun ? 0 : (use_noun && use_verb) ? 1 : use_noun ? 2 : 3;
+  const float inv_tau = 1.0f / temperature;
+  const long np = L.np;
+
+  EGV_LAUNCH(egl_prep_kernel, dim3(L.np), dim3(256), 0, s, text, video, noun, verb, n, L.np, D, L.Dp, dn, dv, L.wn, L.W, eps, tn,
+             vn, words, norms, flags);
+  EGV_CHECK_LAUNCH();
+  int rc = EGL_BY_DP(egl_launch_stats, L, tn, vn, words, n, mode, inv_tau, spart, s);
+  if (rc != EGV_OK) return rc;
+  rc = EGL_BY_DP(egl_launch_stats, L, vn, tn, words, n, mode, inv_tau, spart + (long)L.ns_s * 3 * np, s);
+  if (rc != EGV_OK) return rc;
+  EGV_LAUNCH(egl_loss_kernel, dim3(1), dim3(1024), 0, s, spart, L.ns_s, n, L.np, inv_tau, flags, stat, loss);
+  EGV_CHECK_LAUNCH();
+  if (d_text) {
+    rc = EGL_BY_DP(egl_launch_grad, L, tn, vn, words, stat, stat + 3 * np, n, mode, inv_tau, gpart, s);
+    if (rc != EGV_OK) return rc;
+    EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns_g, tn, norms, L.np, D, L.Dp, eps, d_text);
+    EGV_CHECK_LAUNCH();
+  }
+  if (d_video) {
+    rc = EGL_BY_DP(egl_launch_grad, L, vn, tn, words, stat + 3 * np, stat, n, mode, inv_tau, gpart, s);
+    if (rc != EGV_OK) return rc;
+    EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns_g, vn, norms + np, L.np, D, L.Dp, eps, d_video);
+    EGV_CHECK_LAUNCH();
+  }
+  return EGV_OK;
+}

@@ -4,7 +4,8 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip):
   * the reference's own call shape  `loss(sim_matrix(text, video), sim_v, sim_n)`  (model/loss.py:34,
     trainer/trainer_egoclip.py:130-137): `forward` below, an autograd node over egv_egonce_from_sim;
   * the fused hot path  `loss.fused(text, video, noun, verb)`: ONE call computes the three similarity
-    matrices, the mask, the loss and the gradients w.r.t. both embeddings (egv_egonce_fwd_bwd).
+    matrices, the mask, the loss and the gradients w.r.t. both embeddings (egv_egonce_fwd_bwd; past 1 024 rows the tiled
+    egv_egonce_long_fwd_bwd of csrc/egonce_long.hip, which forms no n x n matrix).
 MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EPIC-MIR / Charades fine-tuning heads over the
 same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
 of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR

@@ -1198,8 +1198,17 @@ def embed_bwd(ids, d_e, word_shape, pos_shape, pad_id=-1):
 # ------------------------------------------------------------------------------------------- loss / optim
 def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
                    want_sim=False):
+    """The contrastive head in one call -> (loss[1], sim or None, d_text, d_video).  Up to EGONCE_SHORT_MAX rows: the latency-bound
+    kernels of csrc/egonce.hip; beyond: egonce_long_fwd_bwd (no n x n matrix exists there, so `want_sim` is refused)."""
     _need_cuda(text, video, noun, verb)
     n, D = text.shape
+    if n > EGONCE_SHORT_MAX:
+        if want_sim:
+            raise ValueError("egonce_fwd_bwd: want_sim needs n <= %d (the long head materialises no n x n matrix), got n = %d"
+                             % (EGONCE_SHORT_MAX, n))
+        loss, dt, dvv = egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=eps, use_noun=use_noun, use_verb=use_verb,
+                                            want_grads=want_grads)
+        return loss, None, dt, dvv
     dev = text.device
     dn = noun.shape[1] if noun is not None else 0
     dv = verb.shape[1] if verb is not None else 0
@@ -1213,6 +1222,29 @@ def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True
                                         float(eps), int(use_noun), int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv),
                                         _p(work), _stream(text)), "egv_egonce_fwd_bwd")
     return loss, sim, dt, dvv
+
+
+EGONCE_SHORT_MAX = 1024      # rows of egv_egonce_fwd_bwd; egonce_fwd_bwd switches to the long head past it
+EGONCE_LONG_MAX = 65536      # rows of egv_egonce_long_fwd_bwd
+
+
+def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True):
+    """egv_egonce_long_fwd_bwd for ANY n in [1, 65536] -> (loss[1], d_text, d_video): the tiled fp32-MFMA head with a workspace
+    linear in n.  noun / verb: non-negative multi-hots (only entry > 0 is used); a negative or NaN entry makes the loss NaN."""
+    _need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    dev = text.device
+    dn = noun.shape[1] if noun is not None else 0
+    dv = verb.shape[1] if verb is not None else 0
+    wf = _lib.lib().egv_egonce_long_work_floats(n, D, dn, dv)
+    work = torch.empty(wf, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dt = torch.empty_like(text) if want_grads else None
+    dvv = torch.empty_like(video) if want_grads else None
+    check(_lib.lib().egv_egonce_long_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, float(temperature),
+                                             float(eps), int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(work),
+                                             _stream(text)), "egv_egonce_long_fwd_bwd")
+    return loss, dt, dvv
 
 
 def grad_nonfinite_multi(grads, state):

@@ -43,9 +43,10 @@ def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fu
     from ..model.model import sim_matrix
     is_ego = type(loss_fn).__name__ == 'EgoNCE'
     n, D = text_embeds.shape
-    # the one-launch head covers global batches up to 1024 rows of <= 256 features (8 x 128 per GPU); beyond that the
-    # API-compatible sim_matrix + loss.forward path takes over (n <= 4096)
-    if fused_head and hasattr(loss_fn, 'fused') and n <= 1024 and D <= 256 and D % 4 == 0:
+    # the one-call head covers global batches up to 65 536 rows of <= 256 features: the latency-bound kernels up to 1 024 rows, the
+    # tiled fp32-MFMA ones beyond (ops.egonce_fwd_bwd switches); anything else, or fused_head=False, takes the API-compatible
+    # sim_matrix + loss.forward path (n <= 4096)
+    if fused_head and hasattr(loss_fn, 'fused') and n <= 65536 and D <= 256 and D % 4 == 0:
         return loss_fn.fused(text_embeds, video_embeds, n_embeds, v_embeds) if is_ego \
             else loss_fn.fused(text_embeds, video_embeds)
     output = sim_matrix(text_embeds, video_embeds)                          # :130

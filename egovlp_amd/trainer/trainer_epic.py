@@ -40,8 +40,8 @@ def retrieval_step(model, loss_fn, optimizer, data, world_size=1, rank=0, fused_
     else:
         video_embeds, text_embeds = AllGatherRows.apply(world_size, rank, video_embeds, text_embeds)        # :123-124
     n, D = text_embeds.shape
-    # the one-call head covers what the EgoNCE head covers (n <= 1024, D <= 256, D % 4 == 0); beyond that the reference's own
-    # decomposition takes over (n <= 4096)
+    # the one-call ranking head covers n <= 1024, D <= 256, D % 4 == 0 (the fine-tunes run small batches; only the EgoNCE head goes
+    # further); beyond that the reference's own decomposition takes over (n <= 4096)
     if fused_head and hasattr(loss_fn, 'fused') and maxmargin_head_ok(n, D):
         loss = loss_fn.fused(text_embeds, video_embeds, weight) if adaptive else loss_fn.fused(text_embeds, video_embeds)
     else:

@@ -399,12 +399,22 @@ int egv_drop_path_grad(const float* g, int64_t ldg, int32_t rows, int32_t cols, 
  * (model/model.py:189-197; model/loss.py:13-25,34-53; trainer/trainer_egoclip.py:130-137).
  * text, video [n, D] fp32 (the all-gathered global batch); noun [n, dn], verb [n, dv] multi-hot fp32
  * (NULL for NormSoftmaxLoss: mask = I).  Writes loss[1], sim [n,n] (optional), and the gradients of
- * the loss w.r.t. text and video [n, D] (optional).  n <= 1024.  `use_noun/use_verb` mirror EgoNCE's ctor. */
+ * the loss w.r.t. text and video [n, D] (optional).  n <= 1024 (beyond: egv_egonce_long_fwd_bwd).  `use_noun/use_verb` mirror EgoNCE's ctor. */
 int egv_egonce_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
                        int32_t n, int32_t D, int32_t dn, int32_t dv, float temperature, float eps,
                        int32_t use_noun, int32_t use_verb,
                        float* loss, float* sim, float* d_text, float* d_video, float* work, void* stream);
 int64_t egv_egonce_work_floats(int32_t n, int32_t D);
+/* The same head for ANY n in [1, 65536] (D <= 256, D % 4 == 0; noun and verb both given or both NULL), with no n x n buffer: the
+ * similarity tiles are recomputed on the fp32-input MFMA and streamed (csrc/egonce_long.hip), so there is no `sim` output.  The
+ * workspace (egv_egonce_long_work_floats floats) is linear in n plus a bounded number of partial tiles.  Same loss and gradients as
+ * egv_egonce_fwd_bwd; deterministic.  Data contract: noun / verb are non-negative multi-hots -- only (entry > 0) is used, as bits;
+ * a negative or NaN entry makes the loss NaN (a device-side flag, no host sync).  d_text / d_video may each be NULL. */
+int egv_egonce_long_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
+                            int32_t n, int32_t D, int32_t dn, int32_t dv, float temperature, float eps,
+                            int32_t use_noun, int32_t use_verb,
+                            float* loss, float* d_text, float* d_video, float* work, void* stream);
+int64_t egv_egonce_long_work_floats(int32_t n, int32_t D, int32_t dn, int32_t dv);
 /* The same head in the reference's own decomposition (kept for API compatibility with code that calls
  * model.model.sim_matrix and model.loss.EgoNCE(x, mask_v, mask_n) separately):
  *  sim_matrix forward (any n, m, D): an/bn = normalised rows (saved for backward), norms [n+m], out [n,m];
