@@ -100,6 +100,12 @@ PROTOTYPES = {
     "egv_patch_gather_u8_eval": (i32, [c_p, i32, c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, i64, c_p]),
     "egv_assemble_tokens": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p]),
     "egv_assemble_tokens_bwd": (i32, [c_p, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
+    "egv_patch_keep_draw": (i32, [i32, i32, i32, u64, c_p, c_p, c_p]),
+    "egv_patch_gather_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, c_p, i32, c_p, c_p, i64, c_p]),
+    "egv_patch_gather_u8_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
+    "egv_patch_gather_u8_aug_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
+    "egv_assemble_tokens_sel": (i32, [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, c_p, c_p]),
+    "egv_assemble_tokens_bwd_sel": (i32, [c_p, c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_divided_attn_fwd": (i32, [c_p, c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_divided_attn_fwd_work_floats": (i64, [i32, i32, i32, i32, i32]),
     "egv_divided_attn_bwd": (i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p]),

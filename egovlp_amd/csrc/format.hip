@@ -1,5 +1,6 @@
 // Format kernels: fp32 <-> split-bf16 planes, transposes (+ column sums = bias gradients),
-// patch gather, token assembly.  All HBM-bound: 16-byte global accesses, LDS only for transposes.
+// patch gather, token assembly, and both over the kept patches of patch dropout (the egv_*_sel entry points and the draw of their
+// table, at the end of the file).  All HBM-bound: 16-byte global accesses, LDS only for transposes and the draw's keys.
 #include "common.h"
 #include "f16x2.h"
 #include "egovlp_hip.h"
@@ -614,6 +615,48 @@ __device__ __forceinline__ void store_patch4(const float (&v)[4], int bt, int c,
     }
   }
 }
+// One output row of the resized crop of frame bt, channel c: the clamped box, the two source rows behind output row y and the
+// Normalize constants.  pixel(ox) is output pixel ox of that row, normalised.
+struct AugRow {
+  const unsigned char *r0, *r1;
+  float ly, sx, mu, sd;
+  int bw, flip, R;
+  __device__ __forceinline__ AugRow(const unsigned char* __restrict__ video, const int* __restrict__ boxes, int bt, int T, int C, int c,
+                                    int Hs, int Ws, int R_, int y, const PatchNorm& nrm) {
+    const int* bx = boxes + (long)(bt / T) * 5;
+    // a box that leaves the frame is CLAMPED into it (the host validates boxes it can see, model/video_transformer.py
+    // set_input_augmentation; a device-resident box cannot be checked without a sync): no read below can leave the clip
+    const int top = min(max(bx[0], 0), Hs - 1), left = min(max(bx[1], 0), Ws - 1);
+    const int bh = min(max(bx[2], 1), Hs - top);
+    bw = min(max(bx[3], 1), Ws - left);
+    flip = bx[4];
+    R = R_;
+    const unsigned char* src = video + ((long)bt * C + c) * Hs * Ws;
+    const float sy = (float)bh / (float)R;
+    sx = (float)bw / (float)R;
+    float fy = ((float)y + 0.5f) * sy - 0.5f;
+    fy = fy < 0.f ? 0.f : fy;
+    const int y0 = (int)fy;
+    const int y1 = y0 + (y0 < bh - 1 ? 1 : 0);
+    ly = fy - (float)y0;
+    r0 = src + (long)(top + y0) * Ws + left;
+    r1 = src + (long)(top + y1) * Ws + left;
+    mu = nrm.mean[c];
+    sd = nrm.std[c];
+  }
+  __device__ __forceinline__ float pixel(int ox) const {
+    const int sxi = flip ? R - 1 - ox : ox;               // RandomHorizontalFlip acts on the resized crop
+    float fx = ((float)sxi + 0.5f) * sx - 0.5f;
+    fx = fx < 0.f ? 0.f : fx;
+    const int x0 = (int)fx;
+    const int x1 = x0 + (x0 < bw - 1 ? 1 : 0);
+    const float lx = fx - (float)x0;
+    const float p00 = (float)r0[x0] / 255.0f, p01 = (float)r0[x1] / 255.0f;
+    const float p10 = (float)r1[x0] / 255.0f, p11 = (float)r1[x1] / 255.0f;
+    const float val = (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
+    return (val - mu) / sd;
+  }
+};
 __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned char* __restrict__ video, int BT, int T, int C,
                                                                int Hs, int Ws, int R, int P, const int* __restrict__ boxes,
                                                                bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda,
@@ -629,36 +672,10 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned ch
   t /= R;
   const int c = (int)(t % C);
   const int bt = (int)(t / C);
-  const int* bx = boxes + (long)(bt / T) * 5;
-  // a box that leaves the frame is CLAMPED into it (the host validates boxes it can see, model/video_transformer.py
-  // set_input_augmentation; a device-resident box cannot be checked without a sync): no read below can leave the clip
-  const int top = min(max(bx[0], 0), Hs - 1), left = min(max(bx[1], 0), Ws - 1);
-  const int bh = min(max(bx[2], 1), Hs - top), bw = min(max(bx[3], 1), Ws - left), flip = bx[4];
-  const unsigned char* src = video + ((long)bt * C + c) * Hs * Ws;
-  const float sy = (float)bh / (float)R, sx = (float)bw / (float)R;
-  float fy = ((float)y + 0.5f) * sy - 0.5f;
-  fy = fy < 0.f ? 0.f : fy;
-  const int y0 = (int)fy;
-  const int y1 = y0 + (y0 < bh - 1 ? 1 : 0);
-  const float ly = fy - (float)y0;
-  const unsigned char* r0 = src + (long)(top + y0) * Ws + left;
-  const unsigned char* r1 = src + (long)(top + y1) * Ws + left;
-  const float mu = nrm.mean[c], sd = nrm.std[c];
+  const AugRow row(video, boxes, bt, T, C, c, Hs, Ws, R, y, nrm);
   float v[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int ox = xg * 4 + e;
-    const int sxi = flip ? R - 1 - ox : ox;               // RandomHorizontalFlip acts on the resized crop
-    float fx = ((float)sxi + 0.5f) * sx - 0.5f;
-    fx = fx < 0.f ? 0.f : fx;
-    const int x0 = (int)fx;
-    const int x1 = x0 + (x0 < bw - 1 ? 1 : 0);
-    const float lx = fx - (float)x0;
-    const float p00 = (float)r0[x0] / 255.0f, p01 = (float)r0[x1] / 255.0f;
-    const float p10 = (float)r1[x0] / 255.0f, p11 = (float)r1[x1] / 255.0f;
-    const float val = (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
-    v[e] = (val - mu) / sd;
-  }
+  for (int e = 0; e < 4; ++e) v[e] = row.pixel(xg * 4 + e);
   store_patch4(v, bt, c, y, xg * 4, R, P, ahi, alo, lda);
 }
 }  // namespace
@@ -809,5 +826,321 @@ extern "C" int egv_patch_gather_u8_eval(const uint8_t* frames, int32_t F, const 
                (long)lda, nrm);
   }
   EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+// ---- patch dropout (timm patch_drop_rate / FLIP masking, as tubes): train on K of the n patch positions of every clip -------------
+// egv_patch_keep_draw draws the table keep[B, K] on the device; the *_sel gathers and the *_sel token assembly are the kernels above
+// restricted to the kept positions, so the planes, the patch-embed GEMM, its wgrad and every block run over B*T*K rows and a
+// dropped patch is never read.  A table entry outside [0, n) is clamped into it wherever it is read: a bad table cannot make a
+// kernel leave its buffers.
+namespace {
+constexpr int KEEP_MAX_N = 1024;    // 448^2 / 14^2
+
+__device__ __forceinline__ int keep_at(const int* __restrict__ keep, long i, int n) { return min(max(keep[i], 0), n - 1); }
+
+// One workgroup per clip.  key(b, j) = the hash egv_drop_scale uses at element index b * n + j; j is kept <=> fewer than K positions
+// of the clip have a smaller (key, j) pair.  Keys in LDS, rank by counting (all lanes read the same LDS word: a broadcast), output
+// slot = number of kept positions in front of j.  No atomics: the table is a pure function of (seed, b, n, K).
+__global__ __launch_bounds__(256) void patch_keep_draw_kernel(int n, int K, EgvDrop d0, int* __restrict__ keep) {
+  __shared__ uint32_t key[KEEP_MAX_N];
+  __shared__ unsigned char kept[KEEP_MAX_N];
+  const EgvDrop d = egv_drop_resolve(d0);
+  const int b = blockIdx.x;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const uint64_t idx = (uint64_t)b * (uint64_t)n + (uint64_t)j;
+    key[j] = egv_mix32(egv_mix32((uint32_t)idx ^ d.s0) ^ (uint32_t)(idx >> 32) ^ d.s1);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const uint32_t h = key[j];
+    int rank = 0;
+    for (int i = 0; i < n; ++i) {
+      const uint32_t hi = key[i];
+      rank += (hi < h || (hi == h && i < j)) ? 1 : 0;
+    }
+    kept[j] = rank < K ? 1 : 0;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += 256) {
+    if (!kept[j]) continue;
+    int slot = 0;
+    for (int i = 0; i < j; ++i) slot += kept[i];
+    keep[(long)b * K + slot] = j;      // exactly K positions have rank < K: slot < K
+  }
+}
+
+// The fp32 / uint8 gather over the kept patches: thread -> (output row r = bt * K + j, channel c, patch row iy, G-pixel group xg), xg
+// fastest, so a row's K_cols columns are written contiguously and one patch-row segment (P pixels) is read by P / G neighbours.
+// Arithmetic and split as patch_gather_kernel: the same bits in row bt * K + j as that kernel leaves in row bt * n + keep[bt / T][j].
+template <int G, bool U8>
+__global__ __launch_bounds__(256) void patch_gather_sel_kernel(const void* __restrict__ video_, int BT, int T, int C, int H, int W,
+                                                               int P, const int* __restrict__ keep, int K,
+                                                               bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda,
+                                                               const PatchNorm nrm) {
+  const int PG = P / G;
+  const long total = (long)BT * K * C * P * PG;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int xg = (int)(i % PG);
+  long t = i / PG;
+  const int iy = (int)(t % P);
+  t /= P;
+  const int c = (int)(t % C);
+  const long row = t / C;                       // bt * K + j
+  const int bt = (int)(row / K);
+  const int gw = W / P, gh = H / P;
+  const int pos = keep_at(keep, (long)(bt / T) * K + (row - (long)bt * K), gw * gh);
+  const int py = pos / gw, px = pos - py * gw;
+  const int ix = xg * G;
+  const long soff = (((long)bt * C + c) * H + (py * P + iy)) * W + px * P + ix;
+  float v[G];
+  if (U8) {
+    const unsigned char* src = (const unsigned char*)video_ + soff;
+    const float mu = nrm.mean[c], sd = nrm.std[c];
+    unsigned bits;
+    if (G == 4) bits = *(const unsigned*)src;
+    else bits = *(const unsigned short*)src;
+#pragma unroll
+    for (int e = 0; e < G; ++e) v[e] = ((float)((bits >> (8 * e)) & 0xffu) / 255.0f - mu) / sd;
+  } else {
+    const float* src = (const float*)video_ + soff;
+    if (G == 4) {
+      const f32x4_t q = *(const f32x4_t*)src;
+      v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+      v[0] = src[0]; v[1] = src[1];
+    }
+  }
+  const int col = (c * P + iy) * P + ix;
+  bf16_t h[G], l[G];
+#pragma unroll
+  for (int e = 0; e < G; ++e) split_bf16(v[e], h[e], l[e]);
+  if (G == 4) {
+    *(u32x2_t*)(ahi + row * lda + col) = (u32x2_t){pack2(h[0], h[1]), pack2(h[2], h[3])};
+    if (alo) *(u32x2_t*)(alo + row * lda + col) = (u32x2_t){pack2(l[0], l[1]), pack2(l[2], l[3])};
+  } else {
+    *(uint32_t*)(ahi + row * lda + col) = pack2(h[0], h[1]);
+    if (alo) *(uint32_t*)(alo + row * lda + col) = pack2(l[0], l[1]);
+  }
+}
+
+// The train-transform gather over the kept patches.  The bilinear arithmetic is contraction-sensitive (which product of a sum the compiler
+// fuses into an FMA depends on how it packs the four pixels of a group), so a thread computes the SAME aligned 4-pixel group x4 .. x4 + 3
+// of output row y with the SAME code as patch_gather_aug_kernel and stores the pixels of it that lie in its patch: NG = P / 4 groups
+// per patch row when P % 4 == 0, (P + 2) / 4 when a patch can start in the middle of a group (P = 14).
+__global__ __launch_bounds__(256) void patch_gather_aug_sel_kernel(const unsigned char* __restrict__ video, int BT, int T, int C,
+                                                                   int Hs, int Ws, int R, int P, int NG, const int* __restrict__ boxes,
+                                                                   const int* __restrict__ keep, int K, bf16_t* __restrict__ ahi,
+                                                                   bf16_t* __restrict__ alo, long lda, const PatchNorm nrm) {
+  const long total = (long)BT * K * C * P * NG;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int g = (int)(i % NG);
+  long t = i / NG;
+  const int iy = (int)(t % P);
+  t /= P;
+  const int c = (int)(t % C);
+  const long orow = t / C;                      // bt * K + j
+  const int bt = (int)(orow / K);
+  const int gw = R / P;
+  const int pos = keep_at(keep, (long)(bt / T) * K + (orow - (long)bt * K), gw * gw);
+  const int py = pos / gw, px = pos - py * gw;
+  const int xq = (px * P) / 4 + g;              // the 4-pixel group of the whole output row
+  if (xq * 4 >= (px + 1) * P) return;
+  const AugRow row(video, boxes, bt, T, C, c, Hs, Ws, R, py * P + iy, nrm);
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = row.pixel(xq * 4 + e);
+  const int ix = xq * 4 - px * P;               // column of the group's first pixel inside the patch row: -2 .. P - 2
+  bf16_t* const dhi = ahi + orow * lda + (c * P + iy) * P;
+  bf16_t* const dlo = alo ? alo + orow * lda + (c * P + iy) * P : nullptr;
+  if (ix >= 0 && ix + 3 < P && (((orow * lda + (c * P + iy) * P + ix) & 3) == 0)) {
+    uint32_t h0, h1, l0, l1;
+    split_bf16x2(v[0], v[1], h0, l0);
+    split_bf16x2(v[2], v[3], h1, l1);
+    *(u32x2_t*)(dhi + ix) = (u32x2_t){h0, h1};
+    if (dlo) *(u32x2_t*)(dlo + ix) = (u32x2_t){l0, l1};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (ix + e < 0 || ix + e >= P) continue;
+      bf16_t h, l;
+      split_bf16(v[e], h, l);
+      dhi[ix + e] = h;
+      if (dlo) dlo[ix + e] = l;
+    }
+  }
+}
+
+// x[b, 0, :] = cls + pos[0]; x[b, 1 + f*K + j, :] = (pe[(b*T + f)*K + j] + pos[1 + keep[b][j]]) + temporal[f]: the sum order of
+// assemble_tokens_kernel
+__global__ __launch_bounds__(256) void assemble_tokens_sel_kernel(const float* __restrict__ pe, const float* __restrict__ cls,
+                                                                  const float* __restrict__ pos, const float* __restrict__ temporal,
+                                                                  const int* __restrict__ keep, int B, int T, int n, int K, int D,
+                                                                  float* __restrict__ x) {
+  const int D4 = D / 4;
+  const long S = 1 + (long)T * K;
+  const long total = (long)B * S * D4;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int d = (int)(i % D4) * 4;
+  const long tok = i / D4;
+  const int s = (int)(tok % S);
+  const int b = (int)(tok / S);
+  f32x4_t v;
+  if (s == 0) {
+    v = *(const f32x4_t*)(cls + d) + *(const f32x4_t*)(pos + d);
+  } else {
+    const int f = (s - 1) / K, j = (s - 1) % K;
+    const int ii = keep_at(keep, (long)b * K + j, n);
+    v = *(const f32x4_t*)(pe + (((long)b * T + f) * K + j) * D + d) + *(const f32x4_t*)(pos + (long)(1 + ii) * D + d) +
+        *(const f32x4_t*)(temporal + (long)f * D + d);
+  }
+  *(f32x4_t*)(x + tok * D + d) = v;
+}
+
+// d_pos[1 + p] = sum of dx over the frames of the clips that kept p; d_pos[0] = d_cls = sum_b dx[b, 0].  Grid (n + 1 position rows,
+// slices of the clips), as assemble_bwd_pos_kernel; a block walks its clips' table rows for its position (K ints, the same for every
+// lane) and adds the T rows of a hit.  A position no clip kept is never added to: it stays the launcher's zero.
+__global__ __launch_bounds__(256) void assemble_bwd_pos_sel_kernel(const float* __restrict__ dx, const int* __restrict__ keep, int B,
+                                                                   int T, int n, int K, int D, float* __restrict__ d_pos,
+                                                                   float* __restrict__ d_cls) {
+  const int p = blockIdx.x;
+  const long S = 1 + (long)T * K;
+  for (int d4 = threadIdx.x; d4 < D / 4; d4 += blockDim.x) {
+    f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+    bool any = false;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+      if (p == 0) {
+        s0 += *(const f32x4_t*)(dx + (long)b * S * D + d4 * 4);
+        any = true;
+        continue;
+      }
+      for (int j = 0; j < K; ++j) {
+        if (keep_at(keep, (long)b * K + j, n) != p - 1) continue;
+        any = true;
+        const float* src = dx + ((long)b * S + 1 + j) * D + d4 * 4;
+        int f = 0;
+        for (; f + 1 < T; f += 2) {
+          s0 += *(const f32x4_t*)(src + (long)f * K * D);
+          s1 += *(const f32x4_t*)(src + (long)(f + 1) * K * D);
+        }
+        if (f < T) s0 += *(const f32x4_t*)(src + (long)f * K * D);
+      }
+    }
+    if (!any) continue;
+    const f32x4_t s = s0 + s1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      atomicAdd(d_pos + (long)p * D + d4 * 4 + e, s[e]);
+      if (p == 0) atomicAdd(d_cls + d4 * 4 + e, s[e]);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int egv_patch_keep_draw(int32_t B, int32_t n, int32_t K, uint64_t seed, const uint64_t* seed_dev, int32_t* keep,
+                                   void* stream) {
+  if (!keep || B <= 0 || K < 1 || K > n || n > KEEP_MAX_N) return EGV_ERR_ARG;
+  EGV_LAUNCH(patch_keep_draw_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, n, K, egv_make_drop(0.f, seed, seed_dev), keep);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+template <bool U8>
+static int patch_gather_sel_launch(const void* video, int BT, int T, int C, int H, int W, int P, const int32_t* keep, int K,
+                                   egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, const PatchNorm& nrm, void* stream) {
+  if (!video || !a_hi || !keep || BT <= 0 || T <= 0 || BT % T != 0 || C <= 0 || H <= 0 || W <= 0 || P <= 0) return EGV_ERR_ARG;
+  if (P % 2 != 0 || W % P != 0 || H % P != 0 || lda % 4 != 0 || lda < (int64_t)C * P * P) return EGV_ERR_ARG;
+  if (K < 1 || K > (H / P) * (W / P)) return EGV_ERR_ARG;
+  const int G = P % 4 == 0 ? 4 : 2;
+  const long blocks = ((long)BT * K * C * P * (P / G) + 255) / 256;
+  if (blocks > 0x7fffffffL) return EGV_ERR_ARG;
+  if (G == 4) {
+    EGV_LAUNCH((patch_gather_sel_kernel<4, U8>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, video, BT, T, C, H, W, P,
+               keep, K, a_hi, a_lo, (long)lda, nrm);
+  } else {
+    EGV_LAUNCH((patch_gather_sel_kernel<2, U8>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, video, BT, T, C, H, W, P,
+               keep, K, a_hi, a_lo, (long)lda, nrm);
+  }
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+extern "C" int egv_patch_gather_sel(const float* video, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                                    const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  return patch_gather_sel_launch<false>(video, BT, T, C, H, W, P, keep, K, a_hi, a_lo, lda, PatchNorm{}, stream);
+}
+
+extern "C" int egv_patch_gather_u8_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                                       const float* mean, const float* std, const int32_t* keep, int32_t K, egv_bf16* a_hi,
+                                       egv_bf16* a_lo, int64_t lda, void* stream) {
+  if (!mean || !std || C < 1 || C > 4) return EGV_ERR_ARG;
+  PatchNorm nrm{};
+  for (int c = 0; c < C; ++c) {
+    if (!(std[c] > 0.f)) return EGV_ERR_ARG;
+    nrm.mean[c] = mean[c];
+    nrm.std[c] = std[c];
+  }
+  return patch_gather_sel_launch<true>(video, BT, T, C, H, W, P, keep, K, a_hi, a_lo, lda, nrm, stream);
+}
+
+extern "C" int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws,
+                                           int32_t R, int32_t P, const int32_t* boxes, const float* mean, const float* std,
+                                           const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda,
+                                           void* stream) {
+  if (!video || !boxes || !keep || !a_hi || !mean || !std || BT <= 0 || T <= 0 || BT % T != 0 || C <= 0 || C > 4) return EGV_ERR_ARG;
+  if (Hs <= 0 || Ws <= 0 || R <= 0 || P <= 0 || R % P != 0 || R % 4 != 0 || P % 2 != 0) return EGV_ERR_ARG;
+  if (lda % 4 != 0 || lda < (int64_t)C * P * P || K < 1 || K > (R / P) * (R / P)) return EGV_ERR_ARG;
+  PatchNorm nrm{};
+  for (int c = 0; c < C; ++c) {
+    nrm.mean[c] = mean[c];
+    nrm.std[c] = std[c];
+  }
+  const int NG = P % 4 == 0 ? P / 4 : (P + 2) / 4;           // 4-pixel groups of the output row that can touch one patch row
+  const long blocks = ((long)BT * K * C * P * NG + 255) / 256;
+  if (blocks > 0x7fffffffL) return EGV_ERR_ARG;
+  EGV_LAUNCH(patch_gather_aug_sel_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, video, BT, T, C, Hs, Ws, R, P, NG,
+             boxes, keep, K, a_hi, a_lo, (long)lda, nrm);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+extern "C" int egv_assemble_tokens_sel(const float* pe, const float* cls, const float* pos, const float* temporal,
+                                       const int32_t* keep, int32_t B, int32_t T, int32_t n, int32_t K, int32_t D, float* x,
+                                       void* stream) {
+  if (!pe || !cls || !pos || !temporal || !keep || !x || D <= 0 || D % 4 != 0) return EGV_ERR_ARG;
+  if (B <= 0 || T <= 0 || K < 1 || K > n) return EGV_ERR_ARG;
+  const long blocks = ((long)B * (1 + (long)T * K) * (D / 4) + 255) / 256;
+  if (blocks > 0x7fffffffL) return EGV_ERR_ARG;
+  EGV_LAUNCH(assemble_tokens_sel_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pe, cls, pos, temporal, keep, B, T,
+             n, K, D, x);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+extern "C" int egv_assemble_tokens_bwd_sel(const float* dx, const int32_t* keep, int32_t B, int32_t T, int32_t n, int32_t K,
+                                           int32_t D, int32_t T_model, float* d_pe, float* d_cls, float* d_pos, float* d_temporal,
+                                           void* stream) {
+  if (!dx || !keep || D <= 0 || D % 4 != 0 || B <= 0 || T <= 0 || T > T_model || K < 1 || K > n) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (d_pos && d_cls) {
+    if (hipMemsetAsync(d_pos, 0, sizeof(float) * (size_t)(n + 1) * D, s) != hipSuccess) return EGV_ERR_LAUNCH;
+    if (hipMemsetAsync(d_cls, 0, sizeof(float) * (size_t)D, s) != hipSuccess) return EGV_ERR_LAUNCH;
+    EGV_LAUNCH(assemble_bwd_pos_sel_kernel, dim3(n + 1, 4), dim3(256), 0, s, dx, keep, B, T, n, K, D, d_pos, d_cls);
+    EGV_CHECK_LAUNCH();
+  }
+  // with K patches per frame the tokens ARE a [B, 1 + T*K, D] sequence: d_temporal and d_pe are those of egv_assemble_tokens_bwd at n = K
+  if (d_temporal) {
+    if (hipMemsetAsync(d_temporal, 0, sizeof(float) * (size_t)T_model * D, s) != hipSuccess) return EGV_ERR_LAUNCH;
+    EGV_LAUNCH(assemble_bwd_temporal_kernel, dim3(T, (D + 63) / 64, 32), dim3(256), 0, s, dx, B, T, K, D, T_model, d_temporal);
+    EGV_CHECK_LAUNCH();
+  }
+  if (d_pe) {
+    const long total = (long)B * T * K * (D / 4);
+    EGV_LAUNCH(assemble_bwd_pe_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dx, B, T, K, D, d_pe);
+    EGV_CHECK_LAUNCH();
+  }
   return EGV_OK;
 }

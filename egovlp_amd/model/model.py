@@ -121,21 +121,27 @@ class FrozenInTime(BaseModel):
             # extension key (the reference's configs carry none and build rate 0): stochastic depth of the video tower, the usual
             # ViT fine-tuning regulariser (0.1 - 0.2); SpaceTimeTransformer(drop_path_rate=...) as in the reference's class
             drop_path_rate = video_params.get('drop_path_rate', 0.)
+            # extension key (absent = 0 = the reference): patch dropout, timm's patch_drop_rate / FLIP's masking -- a train-mode forward
+            # runs the video tower on a random subset of the patch positions of every clip (SpaceTimeTransformer(patch_drop_rate=...))
+            patch_drop_rate = video_params.get('patch_drop_rate', 0.)
             # extension key (the reference's configs carry none and build 224): the input resolution, an int or (height, width) --
             # fine-tuning and evaluation at 288 / 336 / 384 / 448; the pos_embed grid is img_size // patch_size per side
             img_size = video_params.get('img_size', 224)
             if arch_config == 'base_patch16_224':
                 model = SpaceTimeTransformer(img_size=img_size, num_frames=num_frames, time_init=time_init,
-                                             attention_style=attention_style, drop_path_rate=drop_path_rate)
+                                             attention_style=attention_style, drop_path_rate=drop_path_rate,
+                                             patch_drop_rate=patch_drop_rate)
                 vit_path = "pretrained/jx_vit_base_p16_224-80ecf9dd.pth"
             elif arch_config == 'large_patch14_224':          # extension: BASELINE config 5
                 model = SpaceTimeTransformer(img_size=img_size, patch_size=14, embed_dim=1024, depth=24, num_heads=16,
                                              num_frames=num_frames, time_init=time_init,
-                                             attention_style=attention_style, drop_path_rate=drop_path_rate)
+                                             attention_style=attention_style, drop_path_rate=drop_path_rate,
+                                             patch_drop_rate=patch_drop_rate)
                 vit_path = None
             elif arch_config == 'custom':                     # extension (tests): SpaceTimeTransformer(**video_params['arch_kwargs'])
                 model = SpaceTimeTransformer(num_frames=num_frames, time_init=time_init, attention_style=attention_style,
-                                             **{'drop_path_rate': drop_path_rate, **video_params['arch_kwargs']})
+                                             **{'drop_path_rate': drop_path_rate, 'patch_drop_rate': patch_drop_rate,
+                                                **video_params['arch_kwargs']})
                 vit_path = None
             else:
                 raise NotImplementedError                                                        # :53

@@ -331,7 +331,8 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
 
 class _PatchTokensFn(torch.autograd.Function):
     """VideoPatchEmbed (:72-77) + flatten/CLS/pos/temporal (:305-320): patch gather -> MFMA GEMM (+bias)
-    -> token assembly.  No gradient flows to the input frames."""
+    -> token assembly.  No gradient flows to the input frames.  With patch dropout (geom[9] = keep, int32 [B, K] on the device) all of it
+    runs over the K kept positions of every frame: B*T*K rows in the gather, the GEMM, its saved operand and its weight gradient."""
 
     @staticmethod
     def forward(ctx, video, geom, ec, proj_w, proj_b, cls_token, pos_embed, temporal_embed):
@@ -341,12 +342,13 @@ class _PatchTokensFn(torch.autograd.Function):
         mean, std = geom[6] if len(geom) > 6 else (ops.IMAGENET_MEAN, ops.IMAGENET_STD)
         aug = geom[7] if len(geom) > 7 else None
         ev = geom[8] if len(geom) > 8 else None
+        keep = geom[9] if len(geom) > 9 else None
         if ev is not None:
             # the val / test transform inside the gather: `video` is the uint8 frame bank, ev = (center_crop, out_res, frame table)
             a = ops.patch_gather_eval(video.contiguous(), ev[2], T, P_, Pp, ev[0], ev[1], mean, std)
         else:
             # uint8 frames: /255 + Normalize (and, with `aug`, the train transform's crop / resize / flip) inside the gather
-            a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug)
+            a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug, keep=keep)
         K = proj_w[0].numel()
         if a.cols == K:
             w_pl = wc.get(proj_w, need_t=False)[0]
@@ -354,8 +356,9 @@ class _PatchTokensFn(torch.autograd.Function):
             w_pl = ops.split_f32(torch.nn.functional.pad(proj_w.detach().reshape(D, K), (0, a.cols - K)), Pp)[0]
         pe = torch.empty((a.rows, D), dtype=torch.float32, device=video.device)
         ops.gemm_nt(a, w_pl, passes=Pp, bias=proj_b, out_f32=pe, ec=ec)
-        x = ops.assemble_tokens(pe, cls_token, pos_embed, temporal_embed, B, T, n, D)
-        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom, a, Pp, ec
+        x = ops.assemble_tokens(pe, cls_token, pos_embed, temporal_embed, B, T, n, D, keep=keep)
+        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom[:9], a, Pp, ec
+        ctx.save_for_backward(*(() if keep is None else (keep,)))
         ctx.wshape, ctx.proj_w = proj_w.shape, proj_w
         return x
 
@@ -367,7 +370,8 @@ class _PatchTokensFn(torch.autograd.Function):
         # its dY carries the blocks' 2.5e-3 already, and three products would cost 0.12 ms on the tail for 3.5e-3 -> 2.5e-3 on this one tensor
         Pb = 1 if ec.bwd_passes == 4 else ec.bwd_passes
         ec.poll_backward()              # every block's gradients are final here
-        d_pe, d_cls, d_pos, d_tmp = ops.assemble_tokens_bwd(dx.contiguous(), B, T, n, D, T_model)
+        keep = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        d_pe, d_cls, d_pos, d_tmp = ops.assemble_tokens_bwd(dx.contiguous(), B, T, n, D, T_model, keep=keep)
         K = ctx.wshape[1] * ctx.wshape[2] * ctx.wshape[3]
         # a zero-padded K (ViT-L/14: 588 -> 640) is cut off dW right here, on THIS stream: that wgrad must not run on a side stream
         # (bench.py's grad_rel_err had this gradient 100 % off in config 5 with the wgrad side streams on, rounds 3 - 4)
@@ -505,7 +509,7 @@ class SpaceTimeTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, qk_scale=None, representation_size=None,
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., hybrid_backbone=None, norm_layer=None,
-                 num_frames=8, time_init='rand', attention_style='frozen-in-time'):
+                 num_frames=8, time_init='rand', attention_style='frozen-in-time', patch_drop_rate=0.):
         super().__init__()
         if hybrid_backbone is not None:
             raise NotImplementedError('hybrid backbone not implemented')       # :231
@@ -542,10 +546,16 @@ class SpaceTimeTransformer(nn.Module):
         nn.init.trunc_normal_(self.cls_token, std=.02, a=-2., b=2.)
         if num_frames == 1:                                                    # :272-273
             self.apply(self._init_weights)
+        # patch dropout (extension; timm's patch_drop_rate, FLIP's masking): a train-mode forward runs the tower on K = max(1, int(n * (1 -
+        # rate))) of the n patch positions of every clip, the same positions in all its frames (a tube: the time attention attends over one
+        # position across frames, :114); eval() sees all patches.  `last_patch_keep`: the int32 [B, K] device table of the last train-mode
+        # forward that dropped (tests, debugging), else None.
+        self.set_patch_drop_rate(patch_drop_rate)
+        self.last_patch_keep = None
         self.exec_ctx = ops.new_context()     # FrozenInTime replaces it with the dual encoder's shared context
         # stochastic-depth seeds, as the text tower's dropout seeds (text_transformer.DistilBertModel): a call counter advanced by every
-        # train-mode forward that drops paths, the data-parallel rank, an optional capture-safe device word XOR-ed in by the kernels
-        # (the counter stops while it is set), and a site id per block and branch
+        # train-mode forward that drops paths or patches, the data-parallel rank, an optional capture-safe device word XOR-ed in by the kernels
+        # (the counter stops while it is set), and a site id per block and branch (and one for the patch-dropout table)
         self._drop_calls = 0
         self.seed_rank = 0
         self.seed_device = None
@@ -561,6 +571,20 @@ class SpaceTimeTransformer(nn.Module):
         """(seed_space, seed_mlp, seed_dev) of block `layer` at the CURRENT call counter: what its last train-mode forward drew from."""
         # sites 4096 + ...: apart from the text tower's dropout sites, which share the formula
         return self._seed(4096 + 2 * layer), self._seed(4097 + 2 * layer), self.seed_device
+
+    PATCH_DROP_SITE = 2048      # apart from the text tower's sites (0 ..) and the drop-path sites (4096 + ..)
+
+    def set_patch_drop_rate(self, rate):
+        """Change the patch-dropout rate between epochs (FLIP's last, unmasked epochs: set_patch_drop_rate(0.))."""
+        rate = float(rate)
+        if not 0. <= rate < 1.:
+            raise ValueError("patch_drop_rate is a probability in [0, 1)")
+        self.patch_drop_rate = rate
+
+    def patch_keep_count(self, n=None):
+        """K, the patch positions a train-mode forward keeps of n per frame (timm's rule)."""
+        n = self.patches_per_frame if n is None else n
+        return max(1, int(n * (1. - self.patch_drop_rate)))
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -646,13 +670,24 @@ class SpaceTimeTransformer(nn.Module):
         geom = (b, curr_frames, n, P_, self.embed_dim, self.num_frames,
                 getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev)
         ec = self.exec_ctx
+        drops = self.training and any(blk.drop_path > 0. for blk in self.blocks)
+        patch_drop = self.training and self.patch_drop_rate > 0.
+        if patch_drop and ev is not None:
+            raise ValueError("patch dropout (patch_drop_rate > 0 in train mode) does not combine with set_input_eval_transform: "
+                             "that gather is the extraction path; call eval() or set_patch_drop_rate(0.)")
+        if (drops or patch_drop) and self.seed_device is None:
+            self._drop_calls += 1                                              # fresh draws in every train-mode forward: once
+        kept = n                                                               # patch positions per frame the blocks see
+        self.last_patch_keep = None
+        if patch_drop:
+            kept = self.patch_keep_count(n)
+            self.last_patch_keep = ops.patch_keep_draw(b, n, kept, self._seed(self.PATCH_DROP_SITE), self.seed_device,
+                                                       device=self.cls_token.device)
+            geom = geom + (self.last_patch_keep,)
         x = _PatchTokensFn.apply(x, geom, ec, self.patch_embed.proj.weight, self.patch_embed.proj.bias,
                                  self.cls_token, self.pos_embed, self.temporal_embed)
-        drops = self.training and any(blk.drop_path > 0. for blk in self.blocks)
-        if drops and self.seed_device is None:
-            self._drop_calls += 1                                              # fresh draws in every train-mode forward
         for li, blk in enumerate(self.blocks):                                 # :325-328
-            x = blk(x, b, curr_frames, n, ec, self.drop_path_seeds(li) if drops and blk.drop_path > 0. else None)
+            x = blk(x, b, curr_frames, kept, ec, self.drop_path_seeds(li) if drops and blk.drop_path > 0. else None)
         x = _ClsNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, ec)   # :330
         return self.pre_logits(x)
 

@@ -961,12 +961,37 @@ def layernorm_bwd(dy2d, x2d, gamma, mean, rstd, *, add1=None, add2=None, rows=No
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)    # data_loader/transforms.py:34-35 defaults
 
 
-def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None) -> Planes:
+def _check_keep(keep, B, n, what):
+    """The patch-dropout table of a call: contiguous int32 [B, K] in HBM, 1 <= K <= n.  -> K"""
+    if not torch.is_tensor(keep) or keep.dtype != torch.int32 or keep.dim() != 2 or not keep.is_contiguous():
+        raise ValueError(f"{what}: keep is a contiguous int32 [B, K] table of kept patch positions")
+    if keep.shape[0] != B or not 1 <= keep.shape[1] <= n:
+        raise ValueError(f"{what}: keep is [{B}, K] with 1 <= K <= {n}, got {tuple(keep.shape)}")
+    _need_cuda(keep)
+    return int(keep.shape[1])
+
+
+def patch_keep_draw(B, n, K, seed, seed_dev=None, device="cuda"):
+    """-> int32 [B, K]: per clip, K of the n patch positions, uniform without replacement, ascending (egv_patch_keep_draw: the K smallest
+    (hash, position) pairs of the counter-based hash of (seed ^ *seed_dev, b * n + j)).  Drawn on the device, no synchronisation."""
+    B, n, K = int(B), int(n), int(K)
+    if B < 1 or not 1 <= K <= n <= 1024:
+        raise ValueError(f"patch_keep_draw: B >= 1 and 1 <= K <= n <= 1024, got B = {B}, n = {n}, K = {K}")
+    _need_cuda(seed_dev)
+    keep = torch.empty((B, K), dtype=torch.int32, device=device)
+    _need_cuda(keep)
+    check(_lib.lib().egv_patch_keep_draw(B, n, K, int(seed), _p(seed_dev), _p(keep), _stream(keep)), "egv_patch_keep_draw")
+    return keep
+
+
+def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None, keep=None) -> Planes:
     """im2col planes [B*T*patches, K = C*P*P]; K is padded with zero columns to a multiple of 64 (the GEMM k-tile;
     588 -> 640 for ViT-L/14), `cols` of the returned planes is the PADDED width.  A uint8 `video5d` (decoded frames) is
     scaled and normalised in the kernel (x / 255, then (x - mean) / std per channel) -- the loader's host transform.
     aug = (boxes int32 [B, 5] on the device: top, left, h, w, flip; out_res): the train transform (RandomResizedCrop +
-    RandomHorizontalFlip, data_loader/transforms.py:14-19) runs inside the gather on the decoded uint8 clip."""
+    RandomHorizontalFlip, data_loader/transforms.py:14-19) runs inside the gather on the decoded uint8 clip.
+    keep (patch dropout): int32 [B, Kp] on the device -- only those patch positions of every frame of clip b are gathered, row
+    bt * Kp + j = patch keep[bt // T][j] of frame bt, the bits of that row of the full gather (the egv_patch_gather*_sel kernels)."""
     B, T, Cc, H, W = video5d.shape
     if aug is not None:
         boxes, R = aug
@@ -975,24 +1000,36 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
         if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, 5) or not boxes.is_cuda or not boxes.is_contiguous():
             raise ValueError("aug boxes: contiguous int32 [B, 5] on the device (top, left, h, w, flip)")
         H = W = int(R)
-    rows = B * T * (H // P) * (W // P)
+    n = (H // P) * (W // P)
+    per_frame = n if keep is None else _check_keep(keep, B, n, "patch_gather")
+    rows = B * T * per_frame
     K = Cc * P * P
     Kp = (K + 63) // 64 * 64
+    u8 = video5d.dtype == torch.uint8
+    if u8 and (len(norm_mean) != Cc or len(norm_std) != Cc):
+        raise ValueError("patch_gather: one mean / std per channel")
     pl = empty_planes(rows, Kp, passes, video5d.device, zero=(Kp != K))
-    if video5d.dtype == torch.uint8:
-        if len(norm_mean) != Cc or len(norm_std) != Cc:
-            raise ValueError("patch_gather: one mean / std per channel")
+    sel = () if keep is None else (_p(keep), per_frame)
+    if u8:
         mean, std = (C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)
         if aug is not None:
-            check(_lib.lib().egv_patch_gather_u8_aug(_p(video5d), B * T, T, Cc, video5d.shape[3], video5d.shape[4], H, P,
-                                                     _p(aug[0]), mean, std, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
-                  "egv_patch_gather_u8_aug")
+            name = "egv_patch_gather_u8_aug" if keep is None else "egv_patch_gather_u8_aug_sel"
+            check(getattr(_lib.lib(), name)(_p(video5d), B * T, T, Cc, video5d.shape[3], video5d.shape[4], H, P, _p(aug[0]), mean, std,
+                                            *sel, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)), name)
             return pl
-        check(_lib.lib().egv_patch_gather_u8(_p(video5d), B * T, Cc, H, W, P, mean, std, _p(pl.hi), _p(pl.lo), pl.ld,
-                                             _stream(video5d)), "egv_patch_gather_u8")
+        if keep is None:
+            check(_lib.lib().egv_patch_gather_u8(_p(video5d), B * T, Cc, H, W, P, mean, std, _p(pl.hi), _p(pl.lo), pl.ld,
+                                                 _stream(video5d)), "egv_patch_gather_u8")
+        else:
+            check(_lib.lib().egv_patch_gather_u8_sel(_p(video5d), B * T, T, Cc, H, W, P, mean, std, *sel, _p(pl.hi), _p(pl.lo), pl.ld,
+                                                     _stream(video5d)), "egv_patch_gather_u8_sel")
         return pl
-    check(_lib.lib().egv_patch_gather(_p(video5d), B * T, Cc, H, W, P, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
-          "egv_patch_gather")
+    if keep is None:
+        check(_lib.lib().egv_patch_gather(_p(video5d), B * T, Cc, H, W, P, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
+              "egv_patch_gather")
+    else:
+        check(_lib.lib().egv_patch_gather_sel(_p(video5d), B * T, T, Cc, H, W, P, *sel, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
+              "egv_patch_gather_sel")
     return pl
 
 
@@ -1034,21 +1071,39 @@ def patch_gather_eval(frames, index, T, P, passes, center_crop=256, out_res=224,
     return pl
 
 
-def assemble_tokens(pe, cls, pos, temporal, B, T, n, D):
-    x = torch.empty((B, 1 + T * n, D), dtype=torch.float32, device=pe.device)
-    check(_lib.lib().egv_assemble_tokens(_p(pe), _p(cls), _p(pos), _p(temporal), B, T, n, D, _p(x), _stream(pe)),
-          "egv_assemble_tokens")
+def assemble_tokens(pe, cls, pos, temporal, B, T, n, D, keep=None):
+    """-> x [B, 1 + T*n, D]; with `keep` (patch dropout, int32 [B, K]): pe is [B*T*K, D] and x [B, 1 + T*K, D], token 1 + f*K + j of clip b
+    carrying pos[1 + keep[b][j]]."""
+    K = n if keep is None else _check_keep(keep, B, n, "assemble_tokens")
+    if keep is not None and (pe.dim() != 2 or pe.shape[0] != B * T * K or pe.shape[1] != D or pe.dtype != torch.float32 or not pe.is_contiguous()):
+        raise ValueError(f"assemble_tokens: with keep, pe is contiguous fp32 [B*T*K, D] = [{B * T * K}, {D}]")
+    x = torch.empty((B, 1 + T * K, D), dtype=torch.float32, device=pe.device)
+    if keep is None:
+        check(_lib.lib().egv_assemble_tokens(_p(pe), _p(cls), _p(pos), _p(temporal), B, T, n, D, _p(x), _stream(pe)),
+              "egv_assemble_tokens")
+    else:
+        check(_lib.lib().egv_assemble_tokens_sel(_p(pe), _p(cls), _p(pos), _p(temporal), _p(keep), B, T, n, K, D, _p(x), _stream(pe)),
+              "egv_assemble_tokens_sel")
     return x
 
 
-def assemble_tokens_bwd(dx, B, T, n, D, T_model):
+def assemble_tokens_bwd(dx, B, T, n, D, T_model, keep=None):
+    """-> (d_pe, d_cls, d_pos, d_temporal); with `keep`: dx is [B, 1 + T*K, D], d_pe [B*T*K, D], and d_pos rows of positions no clip kept
+    are exactly zero."""
     dev = dx.device
-    d_pe = torch.empty((B * T * n, D), dtype=torch.float32, device=dev)
+    K = n if keep is None else _check_keep(keep, B, n, "assemble_tokens_bwd")
+    if keep is not None and (tuple(dx.shape) != (B, 1 + T * K, D) or dx.dtype != torch.float32 or not dx.is_contiguous()):
+        raise ValueError(f"assemble_tokens_bwd: with keep, dx is contiguous fp32 [B, 1 + T*K, D] = [{B}, {1 + T * K}, {D}]")
+    d_pe = torch.empty((B * T * K, D), dtype=torch.float32, device=dev)
     d_cls = torch.empty((1, 1, D), dtype=torch.float32, device=dev)
     d_pos = torch.empty((1, n + 1, D), dtype=torch.float32, device=dev)
     d_tmp = zeros((1, T_model, D), device=dev)
-    check(_lib.lib().egv_assemble_tokens_bwd(_p(dx), B, T, n, D, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp),
-                                             _stream(dx)), "egv_assemble_tokens_bwd")
+    if keep is None:
+        check(_lib.lib().egv_assemble_tokens_bwd(_p(dx), B, T, n, D, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp),
+                                                 _stream(dx)), "egv_assemble_tokens_bwd")
+    else:
+        check(_lib.lib().egv_assemble_tokens_bwd_sel(_p(dx), _p(keep), B, T, n, K, D, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp),
+                                                     _stream(dx)), "egv_assemble_tokens_bwd_sel")
     return d_pe, d_cls, d_pos, d_tmp
 
 

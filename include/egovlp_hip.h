@@ -309,6 +309,39 @@ int egv_assemble_tokens(const float* pe, const float* cls, const float* pos, con
 int egv_assemble_tokens_bwd(const float* dx, int32_t B, int32_t T, int32_t n, int32_t D, int32_t T_model,
                             float* d_pe, float* d_cls, float* d_pos, float* d_temporal, void* stream);
 
+/* ---- patch dropout (extension; timm's VisionTransformer(patch_drop_rate), FLIP's masking; the reference's tower,
+ * model/video_transformer.py:302-328, always runs all n = patches_per_frame positions) ---------------------------------------------
+ * A train-mode forward keeps K of the n patch positions of every clip -- a TUBE: the same positions in all T frames, which the time
+ * attention (:114, one position across frames) needs -- and the tower runs over S = 1 + T*K tokens, [CLS, frame 0's kept patches in
+ * ascending position order, frame 1's ...].  keep: int32 [B, K] on the DEVICE.  Every kernel that reads the table clamps an entry
+ * outside [0, n) into it, so a bad table cannot make a kernel leave its buffers.
+ *
+ * egv_patch_keep_draw: the key of (clip b, position j) is h = egv_mix32(egv_mix32((uint32)idx ^ s0) ^ (uint32)(idx >> 32) ^ s1),
+ * idx = b*n + j, (s0, s1) = the words of `seed` XOR-ed with seed_dev[0..1] when seed_dev is given (the hash of egv_dropout /
+ * egv_drop_path_*).  j is kept <=> fewer than K positions of the clip have a smaller (h, j) pair (lexicographic: ties break by
+ * index); keep[b] lists the kept positions in ascending order.  One workgroup per clip, no atomics: deterministic.
+ * 1 <= K <= n <= 1024, keep != NULL; EGV_ERR_ARG (nothing launched) otherwise.  K == n gives 0 .. n-1.                            */
+int egv_patch_keep_draw(int32_t B, int32_t n, int32_t K, uint64_t seed, const uint64_t* seed_dev, int32_t* keep, void* stream);
+/* The three gathers over the kept patches only (VideoPatchEmbed :72-77 on a subset): output row bt*K + j is patch keep[bt / T][j]
+ * of frame bt, bit-identical to row bt*n + keep[bt / T][j] of egv_patch_gather / _u8 / _u8_aug (same x / 255, Normalize and bilinear
+ * arithmetic, same split); columns C*P*P .. lda-1 are left untouched.  lda % 4 == 0, 1 <= K <= patches per frame.                 */
+int egv_patch_gather_sel(const float* video, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                         const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
+int egv_patch_gather_u8_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                            const float* mean, const float* std, const int32_t* keep, int32_t K, egv_bf16* a_hi,
+                            egv_bf16* a_lo, int64_t lda, void* stream);
+int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
+                                int32_t P, const int32_t* boxes, const float* mean, const float* std, const int32_t* keep,
+                                int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
+/* x[b,0,:] = cls + pos[0]; x[b,1+f*K+j,:] = (pe[(b*T+f)*K+j,:] + pos[1+keep[b][j]]) + temporal[f] (:305-320 on the kept tokens):
+ * the sum order of egv_assemble_tokens, so the rows are bit-identical to the matching rows of the full assembly.                  */
+int egv_assemble_tokens_sel(const float* pe, const float* cls, const float* pos, const float* temporal, const int32_t* keep,
+                            int32_t B, int32_t T, int32_t n, int32_t K, int32_t D, float* x, void* stream);
+/* backward of the above: d_pe [B*T*K, D], d_cls, d_pos [n+1, D] (row 1+j sums dx over the frames of the clips that kept j and is
+ * exactly zero where no clip did), d_temporal [T_model, D] (rows >= T zeroed).                                                     */
+int egv_assemble_tokens_bwd_sel(const float* dx, const int32_t* keep, int32_t B, int32_t T, int32_t n, int32_t K, int32_t D,
+                                int32_t T_model, float* d_pe, float* d_cls, float* d_pos, float* d_temporal, void* stream);
+
 /* ---- divided space-time attention ------------------------------------------------------------------
  * VarAttention core (model/video_transformer.py:104-133) on the fused qkv buffer [B, S, 3, H, 64] given as split-bf16
  * planes (exactly what the qkv GEMM epilogue writes; qkv_lo is ignored / may be NULL when passes == 1).
