@@ -1,6 +1,6 @@
 // The CLS-row helpers of divided space-time attention (model/video_transformer.py:109-112: the clip's CLS query attends to all S
 // keys per (b, head)).  The CLS query has no attention kernel of its own: each group of the space kernel (attn_mfma_*.hip) and
-// each unit of the time kernel (attn_time_mfma.hip) carries it as one more query against ITS keys -- forward as an un-normalised
+// each unit of the time kernels (attn_time_mfma.hip: T <= 16, attn_time_long.hip: 16 < T <= 64) carries it as one more query against ITS keys -- forward as an un-normalised
 // softmax partial (o[64], m, l) merged here by egv_attn_cls_combine, backward with the global log-sum-exp and delta
 // (egv_attn_cls_delta), so every dK / dV row leaves those kernels complete (patch queries + CLS query) and is written ONCE, as bf16
 // planes.  Only the CLS token's own gradients (shared by all groups of a clip) go through fp32 atomics + egv_attn_cls_finish.
@@ -122,17 +122,24 @@ int egv_attn_time_mfma_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T
                                 float* ws, int out_fmt, int f16, hipStream_t s);
 int egv_attn_time_mfma_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
                                 const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s);
+// 16 < T <= 64: attn_time_long.hip
+int egv_attn_time_long_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse,
+                                float* ws, int out_fmt, int f16, hipStream_t s);
+int egv_attn_time_long_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
+                                const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s);
 
 int egv_attn_time_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol,
                            float* lse, float* ws, int out_fmt, int f16, hipStream_t s) {
-  if (T > 16) return EGV_ERR_ARG;
+  if (T > 64) return EGV_ERR_ARG;
+  if (T > 16) return egv_attn_time_long_fwd_impl(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
   return egv_attn_time_mfma_fwd_impl(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
 }
 
 int egv_attn_time_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
                            const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16,
                            hipStream_t s) {
-  if (T > 16) return EGV_ERR_ARG;
+  if (T > 64) return EGV_ERR_ARG;
+  if (T > 16) return egv_attn_time_long_bwd_impl(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
   return egv_attn_time_mfma_bwd_impl(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
 }
 

@@ -25,7 +25,9 @@
 // forced to probability 0.  What bounds it: HBM -- at T = 16, B = 16 the three-pass forward reads 462 MB and writes 154 MB in 141 us
 // (4.4 TB/s = 0.55 of peak; the loads alone, diagnostic build: 82 us = 5.6 TB/s), the single-pass backward moves 539 MB in 138 us;
 // fetching the tiles cooperatively per workgroup (adjacent tokens per instruction) changed nothing (profiles/r04q_*).
+// 16 < T <= 64: attn_time_long.hip (2 - 4 tiles per location); the tile helpers both share are in attn_time_tile.h.
 #include "attn_common.h"
+#include "attn_time_tile.h"
 #include "egovlp_hip.h"
 
 namespace {
@@ -34,8 +36,6 @@ constexpr int HD64 = 64;
 constexpr int IMG17 = 18 * ATT_ROW_BYTES;      // image read by column fragments only: 16 frame rows + the CLS row (+ 1 pad)
 constexpr int IMG20 = 21 * ATT_ROW_BYTES;      // image read by the transpose read as well: rows 16..19 = CLS copies / zeros, row 20 = zero
 
-// ---- one operand tile (16 frame rows of one plane, 128 B each) as two coalesced loads: lane -> (row 8 it + (l >> 3), chunk l & 7)
-struct Tile { u32x4_t r[2]; };
 // tile row -> (location i0 + row / TP, frame row % TP); rows whose frame >= T or location >= n repeat a valid token (masked by
 // the callers)
 template <int TP>
@@ -52,13 +52,6 @@ __device__ __forceinline__ Tile load_tile(const bf16_t* __restrict__ plane, long
   for (int it = 0; it < 2; ++it)
     t.r[it] = *(const u32x4_t*)(plane + part_base + row_token<TP>(8 * it + (lane >> 3), T, n, i0) * ts + (lane & 7) * 8);
   return t;
-}
-__device__ __forceinline__ void put_tile(char* img, const Tile& t, int lane) {
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int row = 8 * it + (lane >> 3), chunk = lane & 7;
-    *(u32x4_t*)(img + row * ATT_ROW_BYTES + ((chunk ^ (row & 7)) << 4)) = t.r[it];
-  }
 }
 // rows 16 .. 16 + copies - 1 = the CLS row (from the lanes [8 slot, 8 slot + 8) of `v`); `fill` (images the transpose read walks):
 // the rest up to row 19 and row 20 zero.  Rows 16..20: row & 7 = 0..4.
@@ -90,42 +83,6 @@ __device__ __forceinline__ bf16x8_t frag_rows20(const char* img, int col0, int l
   return __builtin_bit_cast(bf16x8_t, z);
 }
 
-__device__ __forceinline__ float allg_max(float v) {   // over the four lane groups that share a column
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float allg_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-__device__ __forceinline__ float row16_sum(float v) {   // over the 16 lanes of a lane group (DPP row)
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));
-  return v;
-}
-
-// row-contraction B operand from a tile pair's accumulator-layout values: elements 0..3 = rows 4g + j of the 16-row tile,
-// elements 4..7 = rows 16..19 (the CLS tile: its rows live in lane group 0 only -- the callers pass zeros elsewhere)
-template <bool F16 = false>
-__device__ __forceinline__ void pack_b(const float (&a)[4], const float (&x)[4], bf16x8_t& hi, bf16x8_t& lo) {
-  const float v[8] = {a[0], a[1], a[2], a[3], x[0], x[1], x[2], x[3]};
-  att_split8<F16>(v, hi, lo);
-}
-template <bool F16 = false>
-__device__ __forceinline__ void pack_b(const float (&a)[4], float one, bf16x8_t& hi, bf16x8_t& lo) {
-  const float x[4] = {one, 0.f, 0.f, 0.f};
-  pack_b<F16>(a, x, hi, lo);
-}
-
-template <int PASSES, bool F16 = false>
-__device__ __forceinline__ f32x4_t mma2(const bf16x8_t (&ah)[2], const bf16x8_t (&al)[2], const bf16x8_t (&bh)[2], const bf16x8_t (&bl)[2]) {
-  f32x4_t c = {0.f, 0.f, 0.f, 0.f};
-  c = att_mma<PASSES, F16>(ah[0], al[0], bh[0], bl[0], c);
-  return att_mma<PASSES, F16>(ah[1], al[1], bh[1], bl[1], c);
-}
-
 __device__ __forceinline__ void store4(bf16_t* __restrict__ ph, bf16_t* __restrict__ pl, long off, const f32x4_t& v, float scale, int fmt = 0) {
   uint32_t h0, h1, l0, l1;
   att_out2(v[0] * scale, v[1] * scale, fmt, h0, l0);
@@ -141,19 +98,6 @@ __device__ __forceinline__ void store4(bf16_t* __restrict__ ph, bf16_t* __restri
 #endif
 }
 
-// ---- output rows through LDS (round 5).  A lane of an output tile owns 4 channels of ONE token row (8 bytes of each plane): stored
-// directly, a wave instruction wrote 16 x 32-byte segments of 16 different 128-byte rows, four instructions per row and plane.  The
-// 16 x 64 tile of a plane is staged in the wave's own LDS instead (the image layout: 128-B rows, 16-B chunk XOR (row & 7); LDS
-// operations of a wave execute in order, so no barrier) and leaves as whole rows: lane -> (row 8 it + (l >> 3), chunk l & 7), one
-// 16-byte store per lane, 8 lanes per 128-byte row.  -DEGV_TMF_OLD_STORES: the direct 8-byte stores (A/B builds).
-__device__ __forceinline__ void stage4(char* sh, char* sl, int p, int col, const f32x4_t& v, float scale, int fmt = 0) {
-  uint32_t h0, h1, l0, l1;
-  att_out2(v[0] * scale, v[1] * scale, fmt, h0, l0);
-  att_out2(v[2] * scale, v[3] * scale, fmt, h1, l1);
-  const int off = att_off(p, col);
-  *(u32x2_t*)(sh + off) = (u32x2_t){h0, h1};
-  if (sl) *(u32x2_t*)(sl + off) = (u32x2_t){l0, l1};
-}
 // rows of the staged tile -> plane rows: element offset of row r = (tok0 + row_token(r)) * ts + col0
 template <int TP, int SITE>
 __device__ __forceinline__ void flush_rows(const char* sh, const char* sl, bf16_t* __restrict__ ph, bf16_t* __restrict__ pl, long tok0, long ts,

@@ -1,7 +1,7 @@
 // C-ABI entry points of divided space-time attention (VarAttention core, model/video_transformer.py:104-133).
 // Patch queries run in the space kernels (attn_mfma_fwd / _bwd.hip: groups of up to 288 keys, K / V of a group in LDS; attn_long.hip:
 // more than 288 keys -- input resolutions above 224^2 --, keys and queries walked in 64-row tiles) or the time kernels
-// (attn_time_mfma.hip) -- all on the matrix cores --; the clip's CLS query row (:109-112) rides along in every
+// (attn_time_mfma.hip: T <= 16 frames; attn_time_long.hip: 16 < T <= 64) -- all on the matrix cores --; the clip's CLS query row (:109-112) rides along in every
 // group of those kernels (see attn_small.hip) and is finished by tiny combine / delta / finish kernels.
 #include "common.h"
 #include "egovlp_hip.h"

@@ -301,10 +301,12 @@ class FrozenInTime(BaseModel):
                         new_temporal_embed = torch.zeros([load_temporal_embed.shape[0], curr_num_frames, embed_dim])
                         new_temporal_embed[:, :load_num_frames] = load_temporal_embed
                     elif self.load_temporal_fix in ['interp', 'bilinear']:
+                        # 'interp' is nearest: F.interpolate takes align_corners with the interpolating modes only (the reference
+                        # passes True to both, which current PyTorch refuses for 'nearest')
                         mode = 'bilinear' if self.load_temporal_fix == 'bilinear' else 'nearest'
                         new_temporal_embed = F.interpolate(load_temporal_embed.unsqueeze(0),
                                                            (curr_num_frames, embed_dim), mode=mode,
-                                                           align_corners=True).squeeze(0)
+                                                           align_corners=True if mode == 'bilinear' else None).squeeze(0)
                     else:
                         raise NotImplementedError
                 new_state_dict['video_model.temporal_embed'] = new_temporal_embed

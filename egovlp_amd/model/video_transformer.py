@@ -519,6 +519,8 @@ class SpaceTimeTransformer(nn.Module):
             raise ValueError("drop_path_rate is a probability in [0, 1)")
         if representation_size:
             raise NotImplementedError("representation_size (pre_logits) is not on the EgoClip hot path")
+        if num_frames > ops.TIME_ATTN_MAX_FRAMES:
+            raise ValueError("num_frames = %d: the time attention takes at most %d frames" % (num_frames, ops.TIME_ATTN_MAX_FRAMES))
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
         self.num_frames = num_frames

@@ -1109,6 +1109,12 @@ def assemble_tokens_bwd(dx, B, T, n, D, T_model, keep=None):
 
 # ---------------------------------------------------------------------------------------------- attention
 ATT_OUT_FMTS = {"bf16": 0, "bf16+f16": 1, "f16x2": 2, "f16": 3}      # csrc/attn_common.h ATT_OUT_*
+TIME_ATTN_MAX_FRAMES = 64    # frames of a time-attention group (mode & 1): csrc/attn_time_mfma.hip up to 16, attn_time_long.hip up to 64
+
+
+def _check_time_frames(who, T, mode):
+    if mode & 1 and T > TIME_ATTN_MAX_FRAMES:
+        raise ValueError("%s: time attention takes at most TIME_ATTN_MAX_FRAMES = %d frames, got T = %d" % (who, TIME_ATTN_MAX_FRAMES, T))
 
 
 def divided_attn_fwd(qkv: Planes, B, T, n, H, mode, passes, out_f16=False, out_fmt=None):
@@ -1117,6 +1123,7 @@ def divided_attn_fwd(qkv: Planes, B, T, n, H, mode, passes, out_f16=False, out_f
     'bf16' split planes; 'bf16+f16' hi = bf16(value) for a bf16 backward, lo = fp16(value), the operand of a one-product proj;
     'f16x2' the f16x2 first-operand planes of a TWO-product proj (fp16 backward); 'f16' ONE plane of fp16(value) (one-product proj, fp16
     backward)."""
+    _check_time_frames("divided_attn_fwd", T, mode)
     S = 1 + T * n
     dev = qkv.hi.device
     if qkv.fmt == "f16s":
@@ -1143,6 +1150,7 @@ def divided_attn_fwd(qkv: Planes, B, T, n, H, mode, passes, out_f16=False, out_f
 def divided_attn_bwd(qkv: Planes, out: Planes, d_out: Planes, lse, B, T, n, H, mode, passes, grad_f16=False) -> Planes:
     """-> dqkv planes [B*S, 3*H*64], ready to be the dY operand of the qkv dgrad / wgrad GEMMs.  grad_f16 (passes == 1): dqkv as ONE plane of
     un-clamped fp16 (the fp16 backward; q / k / v / dO are read as bf16 planes all the same)."""
+    _check_time_frames("divided_attn_bwd", T, mode)
     S = 1 + T * n
     dev = qkv.hi.device
     if grad_f16:

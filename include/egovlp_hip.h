@@ -353,7 +353,9 @@ int egv_assemble_tokens_bwd_sel(const float* dx, const int32_t* keep, int32_t B,
  * Sizes: space groups of up to 288 keys (n <= 287: ViT-B/16 and ViT-L/14 at 224^2) keep K / V of a group in LDS; larger n (288^2 ..
  * 448^2 inputs) runs key-tiled kernels (64-key tiles, online softmax; the backward tiles keys and queries) with the same arguments,
  * workspaces, precision combinations and output formats.  No structural upper bound on n (S = 1 + T*n must fit int32); largest
- * size tested: n = 784 (785 keys).  head dim 64 only.
+ * size tested: n = 784 (785 keys).  Time groups: T <= 16 frames are ONE 16-row tile per location (csrc/attn_time_mfma.hip),
+ * 16 < T <= 64 are 2 - 4 tiles held by one workgroup (csrc/attn_time_long.hip) with the same arguments, workspaces, precision
+ * combinations and output formats; mode 1 with T > 64 returns EGV_ERR_ARG (space mode has no bound on T).  head dim 64 only.
  * mode bits 1-2 (mode = 2 fmt + (0 space | 1 time); fmt != 0 with passes == 3 only) = the format of the output planes:
  *   0  split-bf16 (out_hi = bf16(v), out_lo = bf16(v - out_hi)): a three-product proj;
  *   1  out_hi = bf16(v) (what a bf16 backward reads), out_lo = fp16(v): the operand of a proj Linear that runs ONE fp16 product;
