@@ -169,6 +169,13 @@ PROTOTYPES = {
     "egv_text_layer_bwd_arena_bytes": (i64, [C.POINTER(TextGeom)]),
     "egv_text_layer_grad_layout": (i32, [C.POINTER(TextGeom), c_p, c_p]),
     "egv_text_layer_bwd": (i32, [C.POINTER(TextGeom), C.POINTER(TextParams), c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "egv_cls_linear_fwd": (i32, [c_p, i64, c_p, i64, c_p, i32, i32, i32, i32, c_p, c_p, i64, c_p, i64, c_p]),
+    "egv_cls_linear_work_floats": (i64, [i32, i32, i32]),
+    "egv_cls_linear_dgrad": (i32, [c_p, i64, c_p, i64, i32, i32, i32, c_p, c_p, i64, i32, c_p, c_p]),
+    "egv_cls_linear_wgrad": (i32, [c_p, i64, c_p, i64, i32, i32, i32, c_p, i64, c_p, c_p]),
+    "egv_cls_rows_add": (i32, [c_p, i64, c_p, i64, i32, i32, c_p]),
+    "egv_cls_attn_fwd": (i32, [c_p, i64, c_p, c_p, c_p, c_p, i64, i32, i32, i32, i32, c_p, i64, c_p, c_p]),
+    "egv_cls_attn_bwd": (i32, [c_p, i64, c_p, c_p, c_p, c_p, i64, i32, c_p, c_p, c_p, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, i64, i32, c_p]),
     "egv_diag_mfma_peak": (i32, [i32, i32, c_p, c_p]),
     "egv_diag_traffic_calib": (i32, [i32, c_p, c_p, i64, c_p]),
 }

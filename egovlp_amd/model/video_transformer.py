@@ -211,11 +211,36 @@ def block_calls_ok(ec: ExecContext, M, D, Hd, drop_path=False):
     return all(ops.auto_ksplit_nt(*sh) == 1 for sh in ((M, 3 * D, D), (M, D, D), (M, Hd, D), (M, D, Hd), (M, D, 3 * D)))
 
 
-def _block_geom(B, T, n, H, D, Hd, P, Pb, train, z_bf16, single, eps, grid):
-    return BlockGeom(B, T, n, H, D, Hd, P, Pb, int(train), int(z_bf16), float(eps), int(grid), int(single))
+def _block_geom(B, T, n, H, D, Hd, P, Pb, train, z_bf16, single, eps, grid, tail=False):
+    # egv_block_geom.train: bit 0 = keep what the backward needs, bit 1 = CLS tail (only the B CLS rows of the output are wanted)
+    return BlockGeom(B, T, n, H, D, Hd, P, Pb, int(train) | (2 if tail else 0), int(z_bf16), float(eps), int(grid), int(single))
+
+
+def cls_tail_ok(ec: ExecContext, M, D):
+    """May the LAST block of a tower that runs through the C block calls compute the CLS rows of its output only?  (the setting, and
+    the space qkv GEMMs restricted to the k / v rows -- N = 2 D forward, K = 2 D in the dgrad -- un-split like the block's other GEMMs)"""
+    if not ec.cls_tail:
+        return False
+    if ec.fwd_passes == 2 and not ops.f16x2_gemm_ok(M, 2 * D, D):
+        return False
+    return all(ops.auto_ksplit_nt(*sh) == 1 for sh in ((M, 2 * D, D), (M, D, 2 * D)))
 
 
 _X2_FMTS = ("f16x2", "bf16", "f16x2", "bf16", "f16x2", "f16x2")     # f16x2 mode: qkv / fc1 / fc2 weights in the f16x2 format, proj split-bf16
+
+
+def _tail_params(prm, weights, need_t):
+    """egv_block_params of a CLS-tail call: a copy of `prm` in which the fp32 master weights of attn.qkv, attn.proj, fc1, fc2 (read by the
+    B-row Linears, csrc/cls_tail.hip) travel in the plane slots of the OTHER direction, which that call does not read -- wt_hi[2..5]
+    in the forward, w_hi[2..5] in the backward (contiguous [N, K] fp32)."""
+    out = BlockParams.from_buffer_copy(prm)
+    slot = out.w_hi if need_t else out.wt_hi
+    for i in range(2, 6):
+        w = weights[i]
+        if w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError("the CLS tail reads the fp32 master weights: contiguous float32 parameters")
+        slot[i] = w.data_ptr()
+    return out
 
 
 def _block_params(wc, ln, biases, weights, need_t, x2=False, proj_x2=False, t16=False):
@@ -248,21 +273,24 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         x2 = x.contiguous().view(M, D)
         save = any(ctx.needs_input_grad)
         train = ec.forward_is_train(ctx)
+        tail = len(geom) > 7 and bool(geom[7])      # CLS tail (the tower's last block): the output is the [B, D] CLS rows
         key = (B, T, n, H, D, Hd, P, Pb, train, gelu_grad_16bit(ec, M, Hd, D, P), single)
-        g = _block_geom(*key, eps, ec.gemm_grid)
-        ent = layer_sizes("egv_block", key, g, 18)
+        g = _block_geom(*key, eps, ec.gemm_grid, tail)
+        ent = layer_sizes("egv_block", key + (tail,), g, 18)
         arena = torch.empty(ent[0], dtype=torch.uint8, device=dev)
-        out = torch.empty((M, D), dtype=torch.float32, device=dev)
+        out = torch.empty((B if tail else M, D), dtype=torch.float32, device=dev)
         ln = (n3w, n3b, n1w, n1b, n2w, n2b)
         biases = (tqkv_b, tproj_b, sqkv_b, sproj_b, fc1_b, fc2_b)
         weights = (tqkv_w, tproj_w, sqkv_w, sproj_w, fc1_w, fc2_w)
         prm = _block_params(ec.wc, ln, biases, weights, need_t=False, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4)
+        if tail:
+            prm = _tail_params(prm, weights, need_t=False)
         _lib.check(_lib.lib().egv_block_fwd(C.byref(g), C.byref(prm), x2.data_ptr(), out.data_ptr(), arena.data_ptr(), ops._stream(x2)),
                    "egv_block_fwd")
         if save:
-            ctx.key, ctx.eps, ctx.ec, ctx.arena, ctx.sizes = key, eps, ec, arena, ent
+            ctx.key, ctx.eps, ctx.ec, ctx.arena, ctx.sizes, ctx.tail = key, eps, ec, arena, ent, tail
             ctx.save_for_backward(x2, *ln, *biases, *weights)
-        return out.view(B, S, D)
+        return out if tail else out.view(B, S, D)
 
     @staticmethod
     def backward(ctx, g_out):
@@ -278,9 +306,11 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         S = 1 + T * n
         M = B * S
         dev = x2.device
-        G = g_out.contiguous().view(M, D)
+        tail = ctx.tail
+        G = g_out.contiguous().view(B if tail else M, D)
         # the gradient-plane hand-over of the block behind this one (layer_common._attach_grad_planes); without it the C side formats G
-        g_pl = _take_grad_planes(g_out, M, D, Pb)
+        # (the CLS tail takes its [B, D] gradient as fp32)
+        g_pl = None if tail else _take_grad_planes(g_out, M, D, Pb)
         g_hi, g_lo = (g_pl.hi.data_ptr(), ops._p(g_pl.lo)) if g_pl is not None else (None, None)
         # weight gradients in the order the C side enqueues them (fc2, fc1, attn.proj, attn.qkv, timeattn.proj, timeattn.qkv): stream,
         # event and k-slices of each -- the policy of _lin_bwd / ops.gemm_tn
@@ -294,10 +324,12 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         for i in order:
             if use[i]:
                 streams[i], events[i] = next(it)
-        ks = [ops.wgrad_ksplit(shapes[i][0], shapes[i][1], M, ec, use[i]) for i in range(6)]
-        g = _block_geom(*ctx.key, ctx.eps, ec.gemm_grid)
+        if tail:        # the big space qkv weight gradient covers the k / v rows; attn.proj / fc1 / fc2 are rank-B updates (no k-slices)
+            shapes[2] = (2 * D, D)
+        ks = [1 if tail and i > 2 else ops.wgrad_ksplit(shapes[i][0], shapes[i][1], M, ec, use[i]) for i in range(6)]
+        g = _block_geom(*ctx.key, ctx.eps, ec.gemm_grid, tail)
         ks6 = (C.c_int32 * 6)(*ks)
-        barena = torch.empty(bwd_arena_bytes("egv_block", (ctx.key, tuple(ks)), g, ks6), dtype=torch.uint8, device=dev)
+        barena = torch.empty(bwd_arena_bytes("egv_block", (ctx.key, tail, tuple(ks)), g, ks6), dtype=torch.uint8, device=dev)
         _, goff, gtot = ctx.sizes
         grads = torch.empty(gtot, dtype=torch.float32, device=dev)
         d_x = torch.empty((M, D), dtype=torch.float32, device=dev)
@@ -311,6 +343,8 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
             # that runs two steps ahead that was ~10 ms of host time per ViT-L/14 step (host_enqueue 26 ms against 16 from idle).
             ec.hold_until_join(ctx.arena, barena, grads, *((g_pl.hi, g_pl.lo) if g_pl is not None else ()))
         prm = _block_params(ec.wc, ln, biases, weights, need_t=True, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4, t16=Pb == 4)
+        if tail:
+            prm = _tail_params(prm, weights, need_t=True)
         P6 = C.c_void_p * 6
         io = BlockBwdIO(G.data_ptr(), g_hi, g_lo, x2.data_ptr(), ctx.arena.data_ptr(), barena.data_ptr(),
                         d_x.data_ptr(), dx_pl.hi.data_ptr(), ops._p(dx_pl.lo), grads.data_ptr(),
@@ -386,10 +420,13 @@ class _ClsNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, eps, ec):
-        B, S, D = x.shape
         xc = x.contiguous()
-        _, y, mean, rstd, _ = ops.layernorm_fwd(xc.view(B * S, D), w, b, eps, 1, want_f32=True, want_planes=False,
-                                                rows=B, ldx=S * D)
+        if x.dim() == 2:                # the last block ran its CLS tail: x IS the [B, D] CLS rows
+            _, y, mean, rstd, _ = ops.layernorm_fwd(xc, w, b, eps, 1, want_f32=True, want_planes=False)
+        else:
+            B, S, D = x.shape
+            _, y, mean, rstd, _ = ops.layernorm_fwd(xc.view(B * S, D), w, b, eps, 1, want_f32=True, want_planes=False,
+                                                    rows=B, ldx=S * D)
         ctx.save_for_backward(xc, w, mean, rstd)
         ctx.ec = ec
         return y
@@ -397,8 +434,11 @@ class _ClsNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xc, w, mean, rstd = ctx.saved_tensors
-        B, S, D = xc.shape
         ctx.ec.poll_backward()          # first node of the video tower's backward: what ran before it (the text tower) is final
+        if xc.dim() == 2:               # a [B, D] gradient for the CLS tail: no zero fill of [B, S, D]
+            dx, dg, db = ops.layernorm_bwd(dy.contiguous(), xc, w, mean, rstd)
+            return dx, dg, db, None, None
+        B, S, D = xc.shape
         dx = ops.zeros(tuple(xc.shape), device=xc.device)     # only the B CLS rows receive a gradient
         _, dg, db = ops.layernorm_bwd(dy.contiguous(), xc.view(B * S, D), w, mean, rstd, rows=B, ldx=S * D,
                                       dx=dx.view(B * S, D), lddx=S * D)
@@ -481,9 +521,11 @@ class SpaceTimeBlock(nn.Module):
         self.num_heads = num_heads
         self.attention_style = attention_style
 
-    def forward(self, x, B, T, n, ec, drop_seeds=None):
+    def forward(self, x, B, T, n, ec, drop_seeds=None, cls_only=False):
         """`drop_seeds` = (seed_space, seed_mlp, seed_dev): this forward's stochastic-depth seeds (SpaceTimeTransformer._seed); without
-        them, in eval() and at drop_path == 0 the block is the deterministic one."""
+        them, in eval() and at drop_path == 0 the block is the deterministic one.  `cls_only` (the tower's last block): the caller
+        reads the CLS rows only -- the block MAY then return them as [B, D] (the CLS tail: C block calls, no dropped paths,
+        `ec.cls_tail`) instead of [B, S, D]."""
         # which Linears of THIS block run one fp16 product in the f16x2 mode: the model's precision policy (ops.single_product_policy)
         single = ec.f16_single_mask(getattr(self, "layer_index", None), getattr(self, "depth", None)) if ec.fwd_passes == 2 else 0
         geom = (B, T, n, self.num_heads, self.norm1.eps, single)
@@ -493,6 +535,8 @@ class SpaceTimeBlock(nn.Module):
             geom = geom + ((self.drop_path,) + tuple(drop_seeds),)
         fn = _SpaceTimeBlockCFn if block_calls_ok(ec, B * (1 + T * n), x.shape[-1], self.mlp.fc1.weight.shape[0], drop_path=len(geom) > 6) \
             else _SpaceTimeBlockFn
+        if cls_only and fn is _SpaceTimeBlockCFn and cls_tail_ok(ec, B * (1 + T * n), x.shape[-1]):
+            geom = geom + (None, True)
         return fn.apply(
             x, geom, ec,
             self.norm3.weight, self.norm3.bias, self.timeattn.qkv.weight, self.timeattn.qkv.bias,
@@ -688,8 +732,10 @@ class SpaceTimeTransformer(nn.Module):
             geom = geom + (self.last_patch_keep,)
         x = _PatchTokensFn.apply(x, geom, ec, self.patch_embed.proj.weight, self.patch_embed.proj.bias,
                                  self.cls_token, self.pos_embed, self.temporal_embed)
+        last = len(self.blocks) - 1
         for li, blk in enumerate(self.blocks):                                 # :325-328
-            x = blk(x, b, curr_frames, kept, ec, self.drop_path_seeds(li) if drops and blk.drop_path > 0. else None)
+            # only the CLS rows of the last block's output are read below (:330): it may return just those, [b, D]
+            x = blk(x, b, curr_frames, kept, ec, self.drop_path_seeds(li) if drops and blk.drop_path > 0. else None, cls_only=li == last)
         x = _ClsNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, ec)   # :330
         return self.pre_logits(x)
 

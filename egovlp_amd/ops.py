@@ -77,6 +77,9 @@ _HARD_DEFAULTS = {
     # one C-ABI call per SpaceTimeBlock forward / backward (egv_block_fwd / egv_block_bwd, one workspace arena per direction)
     # instead of the per-kernel calls: the same launches, ~10x less host work.  Off: the per-kernel reference path.
     "block_calls": os.environ.get("EGV_BLOCK_CALLS", "1") == "1",
+    # the last video block computes only the B CLS rows of its output (forward_features reads nothing else: norm(x)[:, 0]) when it runs
+    # through the C block calls and drops no paths: egv_block_geom.train bit 1, csrc/cls_tail.hip.  EGV_CLS_TAIL=0 overrides (A/B runs).
+    "cls_tail": True,
     # how many steps the host may have enqueued beyond the one the GPU is executing.  Workspaces that side streams touch go back to
     # the caching allocator only when the GPU has passed them, so the memory a training loop holds grows with the host's lead: at
     # B = 16, T = 16 (66 GB of such workspaces per step) a lead of four steps reserved 273 of the 288 GB and one slower box went into
@@ -221,6 +224,7 @@ class ExecContext:
     backward_poll = property(lambda self: self.get("backward_poll"))
     kernel_timer = property(lambda self: self.get("kernel_timer"))
     block_calls = property(lambda self: self.get("block_calls"))
+    cls_tail = property(lambda self: bool(self.get("cls_tail")) and os.environ.get("EGV_CLS_TAIL", "1") != "0")
     f16_single = property(lambda self: self.get("f16_single"))
     max_steps_in_flight = property(lambda self: self.get("max_steps_in_flight"))
 
@@ -1407,6 +1411,86 @@ def adamw_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step
     check(_lib.lib().egv_adamw_multi(n, P, G, M_, V, None, None, N, float(lr), float(beta1), float(beta2),
                                      float(eps), float(weight_decay), int(step), int(correct_bias),
                                      float(grad_scale), _p(hyper_dev), _stream(params[0])), "egv_adamw_multi")
+
+
+# ------------------------------------------------------------------------------------------ the CLS tail's pieces (csrc/cls_tail.hip)
+# egv_block_fwd / _bwd launch these from C for the tower's last block (egv_block_geom.train bit 1); the wrappers serve tests and tools.
+def cls_linear_fwd(x, W, bias=None, *, rows=None, ldx=None, gelu=False, want_z=False, residual=None, ldr=None):
+    """y[R,N] = x[R,K] . W[N,K]^T + bias (+ exact-erf GELU; `want_z`: also the fp32 pre-activation) (+ residual), fp32 from the master
+    weight.  `rows` / `ldx` (`ldr`): strided input (residual) rows, e.g. the CLS rows of [B, S, D].  -> y or (y, z)"""
+    _need_cuda(x, W)
+    N, K = W.shape
+    R = x.shape[0] if rows is None else rows
+    y = torch.empty((R, N), dtype=torch.float32, device=x.device)
+    z = torch.empty((R, N), dtype=torch.float32, device=x.device) if want_z else None
+    check(_lib.lib().egv_cls_linear_fwd(_p(x), x.stride(0) if ldx is None else ldx, _p(W), W.stride(0), _p(bias), R, N, K,
+                                        ACT_GELU if gelu else 0, _p(z), _p(residual),
+                                        0 if residual is None else (residual.stride(0) if ldr is None else ldr), _p(y), N, _stream(x)),
+          "egv_cls_linear_fwd")
+    return (y, z) if want_z else y
+
+
+def cls_linear_dgrad(dy, W, *, z=None, out=None, ldo=None, add=False):
+    """dX[R,K] = dY[R,N] . W[N,K] (x gelu'(z)); `out`: store into (or, `add`, add to) R rows of an existing fp32 / fp16 tensor, row
+    stride `ldo`."""
+    _need_cuda(dy, W)
+    N, K = W.shape
+    R = dy.shape[0]
+    if out is None:
+        out = torch.empty((R, K), dtype=torch.float32, device=dy.device)
+        add = False
+    mode = (2 if out.dtype == torch.float16 else 1) if add else 0
+    if out.dtype == torch.float16 and not add:
+        raise ValueError("cls_linear_dgrad: an fp16 destination is accumulated into (add=True)")
+    lib = _lib.lib()
+    work = torch.empty(int(lib.egv_cls_linear_work_floats(R, N, K)), dtype=torch.float32, device=dy.device)
+    check(lib.egv_cls_linear_dgrad(_p(dy), dy.stride(0), _p(W), W.stride(0), R, N, K, _p(z), _p(out), out.stride(0) if ldo is None else ldo,
+                                   mode, _p(work), _stream(dy)), "egv_cls_linear_dgrad")
+    return out
+
+
+def cls_linear_wgrad(dy, x, *, ldx=None):
+    """-> (dW[N,K] = dY[R,N]^T . X[R,K], db[N] = column sums of dY); `ldx`: the row stride of x."""
+    _need_cuda(dy, x)
+    R, N = dy.shape
+    K = x.shape[-1]
+    dW = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+    db = torch.empty(N, dtype=torch.float32, device=dy.device)
+    check(_lib.lib().egv_cls_linear_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0) if ldx is None else ldx, R, N, K, _p(dW), K, _p(db),
+                                          _stream(dy)), "egv_cls_linear_wgrad")
+    return dW, db
+
+
+def _kv_planes(kv: Planes, D):
+    if kv.fmt not in ("bf16", "f16s", "f16"):
+        raise ValueError(f"cls_attn: k | v planes are split-bf16 or an fp16 split, got {kv.fmt!r}")
+    es = kv.hi.element_size()
+    lo = kv.lo
+    return (_p(kv.hi), _p(lo), _p(kv.hi) + D * es, None if lo is None else _p(lo) + D * es, kv.ld, 0 if kv.fmt == "bf16" else 1)
+
+
+def cls_attn_fwd(q, kv: Planes, B, S, H):
+    """The CLS query's attention: q fp32 [B, H 64]; kv = planes [B S, 2 H 64] (k | v of every token).  -> (out [B, H 64], lse [B, H])"""
+    _need_cuda(q, kv.hi)
+    D = H * 64
+    out = torch.empty((B, D), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
+    kh, kl, vh, vl, ld, fmt = _kv_planes(kv, D)
+    check(_lib.lib().egv_cls_attn_fwd(_p(q), q.stride(0), kh, kl, vh, vl, ld, fmt, B, S, H, _p(out), D, _p(lse), _stream(q)), "egv_cls_attn_fwd")
+    return out, lse
+
+
+def cls_attn_bwd(q, kv: Planes, out, d_out, lse, B, S, H, passes):
+    """-> (dq fp32 [B, H 64], dkv Planes [B S, 2 H 64]: split-bf16 (`passes` 3 / 1) or ONE plane of un-clamped fp16 (`passes` 4))"""
+    _need_cuda(q, kv.hi, out, d_out, lse)
+    D = H * 64
+    dq = torch.empty((B, D), dtype=torch.float32, device=q.device)
+    dkv = empty_planes_f16x2(B * S, 2 * D, q.device, single=True) if passes == 4 else empty_planes(B * S, 2 * D, passes, q.device)
+    kh, kl, vh, vl, ld, fmt = _kv_planes(kv, D)
+    dh, dl, dvh, dvl, ldd, dfmt = _kv_planes(dkv, D)
+    check(_lib.lib().egv_cls_attn_bwd(_p(q), q.stride(0), kh, kl, vh, vl, ld, fmt, _p(out.contiguous()), _p(d_out.contiguous()), _p(lse), B, S, H,
+                                      _p(dq), dh, dl, dvh, dvl, ldd, dfmt, _stream(q)), "egv_cls_attn_bwd")
+    return dq, dkv
 
 
 # ---- module-level views of DEFAULT's settings (earlier rounds' names; scripts, tools and tests assign to them) -----------------

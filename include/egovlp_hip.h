@@ -159,10 +159,19 @@ int egv_layernorm_fwd_f16x2(const float* x, int64_t ldx, const float* gamma, con
  * otherwise.  Token-major [M = B (1 + T n), D] fp32 residual stream; D = 64 H.
  * fwd_passes / bwd_passes: 3 = split-bf16 three-product, 1 = single-pass bf16 (bwd_passes <= fwd_passes); train != 0 keeps what
  * the backward needs (z_bf16 != 0: fc1 saves gelu'(z) as bf16 -- single-pass backward -- instead of the fp32 pre-activation).
- * The forward arena must stay untouched until egv_block_bwd has run on it.                                                     */
+ * The forward arena must stay untouched until egv_block_bwd has run on it.
+ * CLS tail (train bit 1; the tower's LAST block, whose output is read on the B CLS rows only -- norm(x)[:, 0], :330): `out` of
+ * egv_block_fwd is the dense [B, D] fp32 CLS rows and io.g_out of egv_block_bwd their [B, D] gradient (io.g_hi NULL); d_x stays
+ * [M, D].  The time branch, norm1 and the k / v rows of the space qkv Linear run over all rows as before; the space attention's CLS
+ * query, the space proj, norm2, fc1 / GELU and fc2 run on B rows in fp32 from the fp32 MASTER weights (the egv_cls_* entry points
+ * below).  Those masters -- contiguous W[N,K] of weights 2 .. 5 -- travel in the plane slots of the other direction, which the call
+ * does not read: wt_hi[2 .. 5] for egv_block_fwd, w_hi[2 .. 5] for egv_block_bwd (cast to const float*); w_hi / w_lo[3 .. 5] (fwd) and
+ * wt_hi / wt_lo[3 .. 5] (bwd) are unused.  wgrad_ksplit[2] is that of the k / v rows' gradient [2 D, D]; [3 .. 5] are ignored.  Arena
+ * sizes, egv_block_fwd_offsets (-1 for planes the tail does not write; `sr` and `z` hold B rows) follow the bit; the gradient layout
+ * does not.                                                                                                                     */
 typedef struct egv_block_geom {
   int32_t B, T, n, H, D, Hd;
-  int32_t fwd_passes, bwd_passes, train, z_bf16;
+  int32_t fwd_passes, bwd_passes, train /* bit 0: keep what the backward needs; bit 1: CLS tail */, z_bf16;
   float eps;
   int32_t grid_cap;     /* as egv_gemm_desc.grid_cap */
   int32_t f16_single;   /* fwd_passes == 2 only: which Linears of THIS block run ONE fp16 product (egv_gemm_nt passes == 4) instead of
@@ -378,6 +387,43 @@ int egv_divided_attn_bwd(const egv_bf16* qkv_hi, const egv_bf16* qkv_lo, const e
                          int32_t n, int32_t H, int32_t mode, int32_t passes, egv_bf16* dqkv_hi, egv_bf16* dqkv_lo,
                          float* work, void* stream);
 int64_t egv_divided_attn_bwd_work_floats(int32_t B, int32_t T, int32_t n, int32_t H);
+
+/* ---- the CLS tail of the last video block (csrc/cls_tail.hip) ------------------------------------------------------------
+ * forward_features ends with norm(x)[:, 0] (model/video_transformer.py:330): of the last SpaceTimeBlock's output only the B CLS rows
+ * are read, so its space-attention output, space proj, norm2, fc1 / GELU, fc2 run on R = B rows (egv_block_fwd / _bwd with bit 1 of
+ * egv_block_geom.train).  These are the R-row pieces: Linears in plain fp32 straight from the fp32 master weights W[N,K] (latency-
+ * sized: W is streamed once; no operand planes), and the attention of ONE query row per (clip, head).  Every sum runs in a fixed
+ * order (no float atomics).  R >= 1; N % 4 == 0, K % 4 == 0, every leading dimension % 4 == 0, 16-byte aligned base pointers.
+ *
+ * y[R,N] = x[R,K] . W[N,K]^T + bias, then act (EGV_ACT_NONE / EGV_ACT_GELU, exact erf; z_out != NULL: the fp32 pre-activation is
+ * stored there, [R, N] contiguous), then + residual[r, n].  x rows may be strided (ldx = S D picks the CLS rows of [B, S, D]).      */
+int egv_cls_linear_fwd(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias /* or NULL */, int32_t R, int32_t N,
+                       int32_t K, int32_t act, float* z_out, const float* residual /* or NULL */, int64_t ldr, float* y, int64_t ldy,
+                       void* stream);
+/* dX[R,K] = dY[R,N] . W[N,K]  (x gelu'(z[r,k]) when z != NULL: z = the [R, K] pre-activation egv_cls_linear_fwd saved).  dx_mode:
+ * 0 = dX fp32 [R, lddx] is overwritten; 1 = added to the fp32 there; 2 = added to a plane of UN-CLAMPED fp16 (dx is uint16 [R, lddx]):
+ * the B CLS rows of a gradient the big dgrad GEMM wrote for all rows.  `work`: egv_cls_linear_work_floats(R, N, K) floats.           */
+int64_t egv_cls_linear_work_floats(int32_t R, int32_t N, int32_t K);
+int egv_cls_linear_dgrad(const float* dy, int64_t lddy, const float* W, int64_t ldw, int32_t R, int32_t N, int32_t K, const float* z,
+                         void* dx, int64_t lddx, int32_t dx_mode, float* work, void* stream);
+/* the rank-R weight gradient dW[N,K] = dY[R,N]^T . X[R,K] (overwritten, row stride lddw) and db[n] = sum_r dY[r,n] (or NULL)        */
+int egv_cls_linear_wgrad(const float* dy, int64_t lddy, const float* x, int64_t ldx, int32_t R, int32_t N, int32_t K, float* dW,
+                         int64_t lddw, float* db, void* stream);
+/* dst[r, 0 .. cols) += src[r, 0 .. cols): R strided fp32 rows                                                                      */
+int egv_cls_rows_add(float* dst, int64_t lddst, const float* src, int64_t ldsrc, int32_t R, int32_t cols, void* stream);
+/* Attention of the CLS query (model/video_transformer.py:112: cls_out = attn(cls_q, k, v) over all S = 1 + T n keys of its clip, the
+ * CLS key / value row an ordinary key): q fp32 [B, H 64] (scaled by 64^-0.5 inside), k / v = operand planes with rows b S + j and the
+ * head's 64 columns at h 64 (row stride ldkv elements; value = hi + lo, lo may be NULL); kv_fmt 0 = bf16 planes, 1 = fp16 planes.
+ * The keys are streamed (online softmax): no bound on S.  out fp32 [B, H 64]; lse [B, H] = log sum_j exp(q . k_j / 8).               */
+int egv_cls_attn_fwd(const float* q, int64_t ldq, const uint16_t* k_hi, const uint16_t* k_lo, const uint16_t* v_hi, const uint16_t* v_lo,
+                     int64_t ldkv, int32_t kv_fmt, int32_t B, int32_t S, int32_t H, float* out, int64_t ldo, float* lse, void* stream);
+/* Backward: dq fp32 [B, H 64] (contiguous) and dK / dV of EVERY key row, written once as gradient planes of row stride lddkv --
+ * d_fmt 0: split-bf16 (dk_lo / dv_lo may be NULL), 1: ONE plane of un-clamped fp16 in dk_hi / dv_hi -- the operand format of the qkv
+ * dgrad / wgrad GEMMs.  out / d_out fp32 [B, H 64] contiguous.                                                                      */
+int egv_cls_attn_bwd(const float* q, int64_t ldq, const uint16_t* k_hi, const uint16_t* k_lo, const uint16_t* v_hi, const uint16_t* v_lo,
+                     int64_t ldkv, int32_t kv_fmt, const float* out, const float* d_out, const float* lse, int32_t B, int32_t S,
+                     int32_t H, float* dq, uint16_t* dk_hi, uint16_t* dk_lo, uint16_t* dv_hi, uint16_t* dv_lo, int64_t lddkv,
+                     int32_t d_fmt, void* stream);
 
 /* ---- DistilBERT pieces ----------------------------------------------------------------------------
  * Embeddings (modeling_distilbert.py:82-118): e[b,l,:] = word[ids[b,l]] + pos[l] (fp32 sum; LN is a
