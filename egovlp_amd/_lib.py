@@ -135,6 +135,10 @@ PROTOTYPES = {
     "egv_dual_softmax": (i32, [c_p, i32, i32, f32, c_p, c_p, c_p]),
     "egv_rank_scores": (i32, [c_p, i64, i32, c_p, i32, i64, i32, i32, i32, c_p, c_p, c_p, c_p]),
     "egv_rank_scores_work_bytes": (i64, [i32, i32]),
+    "egv_gt_ranks": (i32, [c_p, i64, i32, i32, i32, i64, i32, i32, c_p, i32, c_p, c_p, c_p]),
+    "egv_gt_ranks_work_bytes": (i64, [i32, i32]),
+    "egv_topk_rows": (i32, [c_p, i64, i32, i32, c_p, i32, c_p, c_p, c_p]),
+    "egv_row_normalize": (i32, [c_p, i64, i32, i32, f32, c_p, i64, c_p]),
     "egv_cross_entropy_fwd_bwd": (i32, [c_p, i64, c_p, i32, i32, i64, c_p, c_p, i64, c_p]),
     "egv_adamw_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, f32, f32, f32, f32, f32, i32, i32, f32, c_p, c_p]),
     "egv_grad_accumulate_multi": (i32, [i32, c_p, c_p, c_p, c_p]),

@@ -15,17 +15,13 @@
 // c(p) is the running SUM of the relevancies as in calculate_mAP's cumsum (= the count of positives when R is binary).
 // All sums, the discount and the division are fp64.  No atomics: results do not depend on scheduling.
 #include "common.h"
+#include "rank_keys.h"                                           // ordered_desc32, launch_transpose
 #include "egovlp_hip.h"
 
 namespace {
 
 constexpr int RANK_MAX_THREADS = 1024;
 
-__device__ __forceinline__ uint32_t ordered_desc32(float s) {
-  s += 0.0f;                                                     // -0.0 -> +0.0: they are equal similarities
-  const uint32_t u = __float_as_uint(s);
-  return ~(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u));
-}
 __device__ __forceinline__ uint64_t ordered_desc64(double r) {
   r += 0.0;
   const uint64_t u = (uint64_t)__double_as_longlong(r);
@@ -138,28 +134,6 @@ __global__ __launch_bounds__(RANK_MAX_THREADS) void rank_scores_kernel(const flo
     if (dcg_out) dcg_out[row] = d;
     if (ap_out) ap_out[row] = a / (double)n_pos;
   }
-}
-
-// out [cols, rows] = in [rows, cols]^T, 32 x 32 tiles through LDS, 256 threads
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ in, long ldi, int rows, int cols, T* __restrict__ out) {
-  __shared__ T tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-  for (int y = ty; y < 32; y += 8)
-    if (r0 + y < rows && c0 + tx < cols) tile[y][tx] = in[(long)(r0 + y) * ldi + c0 + tx];
-  __syncthreads();
-  for (int y = ty; y < 32; y += 8)
-    if (c0 + y < cols && r0 + tx < rows) out[(long)(c0 + y) * rows + r0 + tx] = tile[tx][y];
-}
-
-template <typename T>
-int launch_transpose(const T* in, long ldi, int rows, int cols, T* out, hipStream_t s) {
-  const int gy = (rows + 31) / 32;
-  if (gy > 65535) return EGV_ERR_ARG;
-  EGV_LAUNCH((transpose_kernel<T>), dim3((cols + 31) / 32, gy), dim3(256), 0, s, in, ldi, rows, cols, out);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
 }
 
 template <typename RT>

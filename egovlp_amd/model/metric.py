@@ -11,7 +11,14 @@ configs/ft/epic.json, configs/eval/epic.json), `map` / `charades_metrics` (:301-
 configs/eval/charades.json) and `oscc_metrics` (:342-353).  The per-query nDCG / average precision of both directions run on
 the device (retrieval_ops.rank_scores -> egv_rank_scores): the similarity matrix is never copied to the host, only the final
 scalars are.  Equal similarities are ranked by ascending index (the reference's order among ties is whatever numpy's unstable
-sort leaves); similarities are ranked as fp32."""
+sort leaves); similarities are ranked as fp32.
+
+Recall@K -- drop-ins for `t2v_metrics` / `v2t_metrics` (reference model/metric.py:20-216, named by configs/eval/nlq.json and
+configs/eval/mq.json, resolved by run/test_nlq.py:37 and run/test_mq.py:36) and for the `cols2metrics` they call (:124, :216).
+The reference defines no `cols2metrics`: the EgoVLP copy of the file dropped the function.  The definition here is the one of
+the public code those two functions were written for (frozen-in-time / collaborative-experts model/metric.py): R1, R5, R10, R50,
+MedR, MeanR and the geometric mean of R1, R5, R10.  The ranks are counts (retrieval_ops.gt_ranks -> egv_gt_ranks), equal to the
+positions the reference's sort-and-subtract finds; their summary is torch on the device, read by the host once."""
 import csv
 import os
 import pickle
@@ -153,6 +160,94 @@ def mir_scores(similarity_matrix, annotations, per_query=False):
     dcg_v, ap_v = retrieval_ops.rank_scores(sims, c["rel_t"], transposed=True)
     dcg_t, ap_t = retrieval_ops.rank_scores(sims, c["rel_t"])
     return _mir_results(dcg_v, ap_v, dcg_t, ap_t, idcg_v, idcg_t, per_query)
+
+
+# ------------------------------------------------------------------------------------------------ Recall@K
+RECALL_KEYS = ("R1", "R5", "R10", "R50", "MedR", "MeanR", "geometric_mean_R1-R5-R10")
+
+
+def _recall_summary(cols, num_queries, keep=None):
+    """The seven numbers of cols2metrics from a rank vector on its device.  keep (bool, same length): only these entries count
+    (t2v's query mask, model/metric.py:109-115), without compacting the vector.  num_queries: a number or a 0-dim tensor."""
+    cols = cols.reshape(-1).double()
+    dev = cols.device
+    if keep is None:
+        n = torch.tensor(cols.numel(), dtype=torch.int64, device=dev)
+        live, srt = cols, torch.sort(cols).values
+        total = cols.sum()
+    else:
+        n = keep.sum()
+        live = torch.where(keep, cols, torch.full_like(cols, float("inf")))     # dropped entries count for no recall ...
+        srt = torch.sort(live).values                                           # ... and sort behind the n kept ones
+        total = torch.where(keep, cols, torch.zeros_like(cols)).sum()
+    if cols.numel() == 0:
+        med = mean = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    else:
+        lo, hi = ((n - 1) // 2).clamp(min=0), (n // 2).clamp(max=cols.numel() - 1)
+        med = torch.where(n > 0, (srt[lo] + srt[hi]) / 2, torch.full_like(total, float("nan")))   # numpy's median
+        mean = total / n
+    nq = torch.as_tensor(num_queries).to(device=dev, dtype=torch.float64).reshape(())
+    hits = [(live == 0).sum()] + [(live < k).sum() for k in (5, 10, 50)]
+    vals = torch.stack([h.double() for h in hits] + [med, mean, nq]).tolist()           # the one host copy
+    nq = vals[6]
+    metrics = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name, hit in zip(("R1", "R5", "R10", "R50"), vals[:4]):
+            metrics[name] = float(100 * np.float64(hit) / np.float64(nq))
+        metrics["MedR"] = vals[4] + 1
+        metrics["MeanR"] = vals[5] + 1
+        stats = np.array([metrics[x] for x in ("R1", "R5", "R10")])
+        metrics["geometric_mean_R1-R5-R10"] = float(np.exp(np.mean(np.log(stats))))      # 0 when one of them is 0
+    return metrics
+
+
+def cols2metrics(cols, num_queries):
+    """Recall summary of a vector of ranks (0 = the ground truth came first): R1 = 100 * #{cols == 0} / n, R5 / R10 / R50 =
+    100 * #{cols < k} / n, MedR = median + 1, MeanR = mean + 1 and the geometric mean of R1, R5, R10 -- the function the
+    reference calls at model/metric.py:124 and :216 and does not define (see the module docstring for its origin)."""
+    return _recall_summary(_to_device(cols, torch.float64), num_queries)
+
+
+def _recall_inputs(name, sims, query_masks):
+    s = _to_device(sims, torch.float32)
+    if s.dim() != 2:
+        raise ValueError(f"{name}: expected a [texts, videos] matrix")
+    nq, nv = s.shape
+    if nq < 1 or nv < 1:
+        raise ValueError(f"{name}: empty matrix {tuple(s.shape)}")
+    if nq % nv != 0:
+        raise ValueError(f"{name}: {nq} texts for {nv} videos: Nq must be a multiple of Nv (caption i belongs to video i // (Nq // Nv))")
+    mask = None
+    if query_masks is not None:
+        mask = _to_device(query_masks).to(s.device).reshape(-1)
+        if mask.numel() != nq:
+            raise ValueError(f"{name}: invalid query mask shape: {mask.numel()} elements for {nq} texts")
+        mask = mask != 0
+    return s, nq // nv, mask
+
+
+def t2v_metrics(sims, query_masks=None, per_query=False):
+    """Text-to-video recall from sims [texts, videos], sims[i, j] = <text i, video j> (model/metric.py:20-124): rank_i =
+    #{j : sims[i, j] > sims[i, i // qpv]}, ties "optimistically"; the queries query_masks marks as missing are dropped afterwards
+    and num_queries = query_masks.sum().  per_query=True additionally returns the kept ranks (device tensor)."""
+    s, qpv, mask = _recall_inputs("t2v_metrics", sims, query_masks)
+    ranks = retrieval_ops.gt_ranks(s, qpv, "t2v", query_masks=mask)
+    metrics = _recall_summary(ranks, ranks.numel() if mask is None else mask.sum(), keep=mask)
+    if per_query:
+        return metrics, (ranks if mask is None else ranks[mask])
+    return metrics
+
+
+def v2t_metrics(sims, query_masks=None, per_query=False):
+    """Video-to-text recall from the same [texts, videos] matrix (model/metric.py:127-216): per video the rank of its closest
+    existing caption among the existing captions, ties "averaging"; a video without a caption ranks +inf; num_queries = videos.
+    per_query=True additionally returns the ranks (device tensor)."""
+    s, qpv, mask = _recall_inputs("v2t_metrics", sims, query_masks)
+    ranks = retrieval_ops.gt_ranks(s, qpv, "v2t", query_masks=mask)
+    metrics = _recall_summary(ranks, ranks.numel())
+    if per_query:
+        return metrics, ranks
+    return metrics
 
 
 # ------------------------------------------------------------------------------------------------ Charades

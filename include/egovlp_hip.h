@@ -602,6 +602,37 @@ int egv_rank_scores(const float* S, int64_t lds, int32_t transposed, const void*
                     int32_t n1, int32_t n2, int32_t affine_half, double* dcg_out, double* ap_out, void* work, void* stream);
 int64_t egv_rank_scores_work_bytes(int32_t n1, int32_t n2);
 
+/* ---- Recall@K: ground-truth ranks, top-k lists, row normalisation (csrc/recall.hip) -----------------------------------
+ * Replaces the sort-and-subtract ranking of model/metric.py t2v_metrics (:20-124) and v2t_metrics (:127-216): the position
+ * of the ground-truth distance in the sorted row is a count.  S is fp32 [n1, n2] row-major, leading dimension lds (elements).
+ *   transposed == 0: the queries are the n1 rows, a row has n2 columns.
+ *   transposed == 1: the queries are the n2 columns of S (v2t_metrics receives [texts, videos], :143); S is transposed on the
+ *     device into `work` (egv_gt_ranks_work_bytes(n1, n2) bytes, 4-byte aligned; may be NULL otherwise) and a "row" below is a
+ *     column of S with n1 entries.  n1 <= 65535 * 32 in this form.
+ * Query r is row row0 + r of a larger problem (row0 >= 0: a chunk of rows can be ranked on its own).  Its ground truth is
+ *   seg_wide == 0: the single column (row0 + r) / qpv                  (t2v: caption i belongs to video i / qpv, :39-43)
+ *   seg_wide != 0: the qpv columns from (row0 + r) * qpv               (v2t: the captions of video i, :176)
+ * col_valid (NULL = all valid): one uint8 per column of the row, nonzero = the column exists (query_masks, :167).
+ *   g    = max of S over the valid columns of the segment                            (the closest ground-truth caption, :188-189)
+ *   rank = #{valid j : s_j > g}                                   tie_avg == 0 ("optimistically", :66, :71-73)
+ *   rank = #{valid j : s_j > g} + (#{valid j : s_j == g} - 1) / 2  tie_avg != 0 ("averaging", :157, :187)
+ *   rank = +inf when the segment has no valid column (:175).
+ * rank_out holds one double per query.  Comparisons are IEEE fp32 (-0 == +0); NaN is not supported.  A row may have up to
+ * 2^31 - 1 columns; the counters are integers, so two calls give the same bits.  A segment that leaves the row returns 1 and
+ * launches nothing, as every invalid argument does.                                                                          */
+int egv_gt_ranks(const float* S, int64_t lds, int32_t transposed, int32_t n1, int32_t n2, int64_t row0, int32_t qpv,
+                 int32_t seg_wide, const uint8_t* col_valid, int32_t tie_avg, double* rank_out, void* work, void* stream);
+int64_t egv_gt_ranks_work_bytes(int32_t n1, int32_t n2);
+/* Per row of S [rows, cols] the k <= EGV_TOPK_MAX largest (value, column) pairs among the valid columns, descending value, ties
+ * by ascending column (-0 == +0; the TIE RULE of egv_rank_scores): vals fp32 [rows, k] (the entries themselves), idx int64
+ * [rows, k].  With fewer than k valid columns the tail is -inf / -1.  Any row length up to 2^31 - 1.                          */
+#define EGV_TOPK_MAX 64
+int egv_topk_rows(const float* S, int64_t lds, int32_t rows, int32_t cols, const uint8_t* col_valid, int32_t k, float* vals,
+                  int64_t* idx, void* stream);
+/* out[r, :] = x[r, :] / max(|x[r, :]|_2, eps): the normalisation of sim_matrix (model/model.py:189-197) as an op of its own.
+ * x [rows, D] with leading dimension ldx, out with ldo; out may be x.                                                         */
+int egv_row_normalize(const float* x, int64_t ldx, int32_t rows, int32_t D, float eps, float* out, int64_t ldo, void* stream);
+
 /* ---- gradient exchange (data parallel) ------------------------------------------------------------------
  * Replaces the fp32 bucket copies of DistributedDataParallel (base/base_trainer.py:258): `count` fp32 gradient tensors
  * (HOST arrays of device pointers / sizes) are scaled by `scale` (= 1 / world size), rounded to bf16 (RNE) and written to
