@@ -1013,27 +1013,15 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
     if u8 and (len(norm_mean) != Cc or len(norm_std) != Cc):
         raise ValueError("patch_gather: one mean / std per channel")
     pl = empty_planes(rows, Kp, passes, video5d.device, zero=(Kp != K))
+    # egv_patch_gather[_u8[_aug]][_sel](video, B*T, [T,] C, geometry, [mean, std,] [keep, K,] planes, lda, stream); "_aug" only ever
+    # follows "_u8" (aug with fp32 frames was refused above), so the six names this can form are the six entry points
+    name = "egv_patch_gather" + ("_u8" if u8 else "") + ("_aug" if aug is not None else "") + ("" if keep is None else "_sel")
+    clip = (T,) if aug is not None or keep is not None else ()
+    geom = (H, W, P) if aug is None else (video5d.shape[3], video5d.shape[4], H, P, _p(aug[0]))
+    norm = ((C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)) if u8 else ()
     sel = () if keep is None else (_p(keep), per_frame)
-    if u8:
-        mean, std = (C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)
-        if aug is not None:
-            name = "egv_patch_gather_u8_aug" if keep is None else "egv_patch_gather_u8_aug_sel"
-            check(getattr(_lib.lib(), name)(_p(video5d), B * T, T, Cc, video5d.shape[3], video5d.shape[4], H, P, _p(aug[0]), mean, std,
-                                            *sel, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)), name)
-            return pl
-        if keep is None:
-            check(_lib.lib().egv_patch_gather_u8(_p(video5d), B * T, Cc, H, W, P, mean, std, _p(pl.hi), _p(pl.lo), pl.ld,
-                                                 _stream(video5d)), "egv_patch_gather_u8")
-        else:
-            check(_lib.lib().egv_patch_gather_u8_sel(_p(video5d), B * T, T, Cc, H, W, P, mean, std, *sel, _p(pl.hi), _p(pl.lo), pl.ld,
-                                                     _stream(video5d)), "egv_patch_gather_u8_sel")
-        return pl
-    if keep is None:
-        check(_lib.lib().egv_patch_gather(_p(video5d), B * T, Cc, H, W, P, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
-              "egv_patch_gather")
-    else:
-        check(_lib.lib().egv_patch_gather_sel(_p(video5d), B * T, T, Cc, H, W, P, *sel, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d)),
-              "egv_patch_gather_sel")
+    check(getattr(_lib.lib(), name)(_p(video5d), B * T, *clip, Cc, *geom, *norm, *sel, _p(pl.hi), _p(pl.lo), pl.ld,
+                                    _stream(video5d)), name)
     return pl
 
 
@@ -1083,11 +1071,10 @@ def assemble_tokens(pe, cls, pos, temporal, B, T, n, D, keep=None):
         raise ValueError(f"assemble_tokens: with keep, pe is contiguous fp32 [B*T*K, D] = [{B * T * K}, {D}]")
     x = torch.empty((B, 1 + T * K, D), dtype=torch.float32, device=pe.device)
     if keep is None:
-        check(_lib.lib().egv_assemble_tokens(_p(pe), _p(cls), _p(pos), _p(temporal), B, T, n, D, _p(x), _stream(pe)),
-              "egv_assemble_tokens")
+        name, table, dims = "egv_assemble_tokens", (), (B, T, n, D)
     else:
-        check(_lib.lib().egv_assemble_tokens_sel(_p(pe), _p(cls), _p(pos), _p(temporal), _p(keep), B, T, n, K, D, _p(x), _stream(pe)),
-              "egv_assemble_tokens_sel")
+        name, table, dims = "egv_assemble_tokens_sel", (_p(keep),), (B, T, n, K, D)
+    check(getattr(_lib.lib(), name)(_p(pe), _p(cls), _p(pos), _p(temporal), *table, *dims, _p(x), _stream(pe)), name)
     return x
 
 
@@ -1103,11 +1090,10 @@ def assemble_tokens_bwd(dx, B, T, n, D, T_model, keep=None):
     d_pos = torch.empty((1, n + 1, D), dtype=torch.float32, device=dev)
     d_tmp = zeros((1, T_model, D), device=dev)
     if keep is None:
-        check(_lib.lib().egv_assemble_tokens_bwd(_p(dx), B, T, n, D, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp),
-                                                 _stream(dx)), "egv_assemble_tokens_bwd")
+        name, table, dims = "egv_assemble_tokens_bwd", (), (B, T, n, D)
     else:
-        check(_lib.lib().egv_assemble_tokens_bwd_sel(_p(dx), _p(keep), B, T, n, K, D, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp),
-                                                     _stream(dx)), "egv_assemble_tokens_bwd_sel")
+        name, table, dims = "egv_assemble_tokens_bwd_sel", (_p(keep),), (B, T, n, K, D)
+    check(getattr(_lib.lib(), name)(_p(dx), *table, *dims, T_model, _p(d_pe), _p(d_cls), _p(d_pos), _p(d_tmp), _stream(dx)), name)
     return d_pe, d_cls, d_pos, d_tmp
 
 

@@ -12,7 +12,8 @@ Measured on MI355X (rel-L2): tower (depth 3, B = 6, T = 2, K = 8 of 16, 'bf16x3'
 blocks.0.timeattn.qkv.weight 1.6e-5; with drop_path 0.3 on top: 1.1e-5 / 1.7e-5.  Assembly backward against fp64 autograd: d_pe 0,
 d_cls 3.0e-8, d_pos 3.9e-8, d_temporal 4.8e-8.  ViT-B width at K = 98 (M = 786), 'f16mix' / 'f16' against 'bf16x3' / 'bf16x3': embedding
 0 (786 rows are too few for the fp16 big-tile format, f16x2_block_ok: the forward of both runs is split-bf16), worst gradient
-patch_embed.proj.weight 2.3e-3.  Draw, gathers and assembly forward: bit-equal.  Cached step: max |pass 3 - cache| = 0.
+patch_embed.proj.weight 2.3e-3.  Draw, gathers and assembly forward: bit-equal.  Cached step: max |pass 3 - cache| = 0.  Identity table
+(K = n) against the full kernels: gathers and assembly forward bit-equal, assembly backward d_pe 0, d_cls 0, d_pos 6.3e-8, d_temporal 5.6e-8.
 """
 import numpy as np
 import pytest
@@ -179,6 +180,117 @@ def test_assembly_forward_rows_and_backward_against_fp64_autograd():
         assert float(d_pos[0, [1 + j for j in unkept]].abs().max()) == 0.0
         assert float(d_pos[0, [1 + j for j in range(n) if j not in unkept]].abs().max(dim=1).values.min()) > 0.0
         assert float(d_tmp[0, T:].abs().max()) == 0.0
+
+
+def _identity(B, n):
+    return torch.arange(n, dtype=torch.int32, device="cuda").expand(B, n).contiguous()
+
+
+def test_identity_table_is_the_full_kernels():
+    """keep[b] = 0 .. n-1 (K = n, the boundary the draw's "exactly K have rank < K" rests on): the *_sel entry points are their full twins.
+    Gathers and assembly forward in every bit (both planes, passes 1 and 3); the assembly backward within the 1e-6 of this file -- its two
+    position kernels sum in different orders."""
+    from egovlp_amd import ops
+    g = torch.Generator().manual_seed(15)
+    n = 12
+    for B, T, H, W, P in ((2, 3, 64, 48, 16), (2, 2, 56, 42, 14)):
+        for u8 in (False, True):
+            video = torch.randint(0, 256, (B, T, 3, H, W), generator=g, dtype=torch.uint8) if u8 else torch.randn(B, T, 3, H, W, generator=g)
+            sel = _check_gather(video.cuda(), P, n, T, _identity(B, n))
+            if P == 14:
+                assert sel.cols == 640 and float(sel.hi[:, 588:].float().abs().max()) == 0.0 and float(sel.lo[:, 588:].float().abs().max()) == 0.0
+    Bq, Tq, Hs, Ws = 3, 2, 80, 100
+    src = torch.randint(0, 256, (Bq, Tq, 3, Hs, Ws), generator=g, dtype=torch.uint8).cuda()
+    boxes = torch.tensor([[0, 0, Hs, Ws, 0], [7, 11, 50, 61, 1], [20, 3, 33, 90, 0]], dtype=torch.int32, device="cuda")
+    for R_, P in ((64, 16), (56, 14)):
+        _check_gather(src, P, (R_ // P) ** 2, Tq, _identity(Bq, (R_ // P) ** 2), aug=(boxes, R_))
+    B, T, D, T_model = 2, 3, 64, 5
+    pe = torch.randn(B * T * n, D, generator=g).cuda()
+    cls, pos, tmp = torch.randn(1, 1, D, generator=g).cuda(), torch.randn(1, n + 1, D, generator=g).cuda(), torch.randn(1, T_model, D, generator=g).cuda()
+    dx = torch.randn(B, 1 + T * n, D, generator=g).cuda()
+    keep = _identity(B, n)
+    assert torch.equal(bits(ops.assemble_tokens(pe, cls, pos, tmp, B, T, n, D, keep=keep)), bits(ops.assemble_tokens(pe, cls, pos, tmp, B, T, n, D)))
+    full, sel = ops.assemble_tokens_bwd(dx, B, T, n, D, T_model), ops.assemble_tokens_bwd(dx, B, T, n, D, T_model, keep=keep)
+    torch.cuda.synchronize()
+    errs = [rel(s_, f_) for s_, f_ in zip(sel, full)]
+    print("assembly backward, identity table against the full backward: d_pe %.1e d_cls %.1e d_pos %.1e d_temporal %.1e" % tuple(errs))
+    assert all(tuple(s_.shape) == tuple(f_.shape) for s_, f_ in zip(sel, full)) and all(e < 1e-6 for e in errs), errs
+
+
+def test_input_path_with_bad_arguments_launches_nothing():
+    """Every refusal of the eleven entry points of csrc/video_input.hip but the draw's (above): a valid argument list per entry point
+    (names and order of include/egovlp_hip.h), the named arguments of ONE case replaced, EGV_ERR_ARG expected and no output buffer
+    touched.  The valid lists themselves are never sent."""
+    import ctypes as C
+    from egovlp_amd import _lib
+    h = _lib.lib()
+    BT, T, Cc, H, P, n, K, D, TM = 2, 2, 3, 32, 16, 4, 2, 8, 2                 # one clip of two 32 x 32 frames, 768 columns
+    lda = Cc * P * P
+    dev = "cuda"
+    f32 = torch.zeros(BT, Cc, H, H, device=dev)
+    u8 = torch.zeros(BT, Cc, 40, 40, dtype=torch.uint8, device=dev)             # the direct gathers read its first 32 x 32 x 3 x 2 bytes
+    hi, lo = (torch.full((BT * n, lda), -7, dtype=torch.int16, device=dev) for _ in range(2))
+    keep = torch.tensor([[0, 3]], dtype=torch.int32, device=dev)
+    boxes = torch.tensor([[0, 0, 40, 40, 0]], dtype=torch.int32, device=dev)
+    pe, cls, pos, tmp = (torch.zeros(r, D, device=dev) for r in (BT * n, 1, n + 1, TM))
+    x, dxs = torch.full((1, 1 + T * n, D), -7.0, device=dev), torch.zeros(1, 1 + T * n, D, device=dev)
+    d_pe, d_cls, d_pos, d_tmp = (torch.full((r, D), -7.0, device=dev) for r in (BT * n, 1, n + 1, TM))
+    mean, std = (C.c_float * 3)(0.5, 0.5, 0.5), (C.c_float * 3)(0.25, 0.25, 0.25)
+    std0, stdn = (C.c_float * 3)(0.25, 0.0, 0.25), (C.c_float * 3)(0.25, 0.25, -1.0)
+    p = lambda t: t.data_ptr()
+    planes = dict(a_hi=p(hi), a_lo=p(lo), lda=lda, stream=None)
+    norm, table = dict(mean=mean, std=std), dict(keep=p(keep), K=K)
+    aug = dict(video=p(u8), BT=BT, T=T, C=Cc, Hs=40, Ws=40, R=H, P=P, boxes=p(boxes))
+    grads = dict(d_pe=p(d_pe), d_cls=p(d_cls), d_pos=p(d_pos), d_temporal=p(d_tmp), stream=None)
+    valid = {
+        "egv_patch_gather": dict(video=p(f32), BT=BT, C=Cc, H=H, W=H, P=P, **planes),
+        "egv_patch_gather_u8": dict(video=p(u8), BT=BT, C=Cc, H=H, W=H, P=P, **norm, **planes),
+        "egv_patch_gather_sel": dict(video=p(f32), BT=BT, T=T, C=Cc, H=H, W=H, P=P, **table, **planes),
+        "egv_patch_gather_u8_sel": dict(video=p(u8), BT=BT, T=T, C=Cc, H=H, W=H, P=P, **norm, **table, **planes),
+        "egv_patch_gather_u8_aug": dict(**aug, **norm, **planes),
+        "egv_patch_gather_u8_aug_sel": dict(**aug, **norm, **table, **planes),
+        "egv_patch_gather_u8_eval": dict(frames=p(u8), F=BT, index=None, BT=BT, C=Cc, Hs=40, Ws=40, S=H, R=H, P=P, **norm, **planes),
+        "egv_assemble_tokens": dict(pe=p(pe), cls=p(cls), pos=p(pos), temporal=p(tmp), B=1, T=T, n=n, D=D, x=p(x), stream=None),
+        "egv_assemble_tokens_sel": dict(pe=p(pe), cls=p(cls), pos=p(pos), temporal=p(tmp), keep=p(keep), B=1, T=T, n=n, K=K, D=D, x=p(x), stream=None),
+        "egv_assemble_tokens_bwd": dict(dx=p(dxs), B=1, T=T, n=n, D=D, T_model=TM, **grads),
+        "egv_assemble_tokens_bwd_sel": dict(dx=p(dxs), keep=p(keep), B=1, T=T, n=n, K=K, D=D, T_model=TM, **grads),
+    }
+    null = lambda *names: [{a: None} for a in names]
+    zero = lambda *names: [{a: 0} for a in names]
+    # GRID: more than 2^31 - 1 blocks.  These cases pass every other check with the small buffers above, so grid_of (csrc/video_input.hip)
+    # alone stands between them and a launch far beyond those buffers.
+    BIG = 1 << 30
+    bad = {
+        "egv_patch_gather": null("video", "a_hi") + zero("BT", "C", "H", "W", "P") + [dict(BT=-BT), dict(H=24), dict(P=15), dict(lda=lda - 2),
+                            dict(lda=lda + 1), dict(BT=BIG, H=4096, W=4096)],
+        "egv_patch_gather_sel": null("video", "a_hi", "keep") + zero("BT", "T", "C", "H", "W", "P", "K") + [dict(K=n + 1), dict(BT=3), dict(H=24),
+                                dict(P=15), dict(lda=lda - 4), dict(lda=lda + 2), dict(BT=BIG, H=4096, W=4096, K=65536)],
+        "egv_patch_gather_u8_aug": null("video", "boxes", "mean", "std", "a_hi") + zero("BT", "T", "C", "Hs", "Ws", "R", "P") + [
+            dict(std=std0), dict(std=stdn), dict(C=5), dict(BT=3), dict(R=24), dict(R=30, P=6), dict(P=15), dict(lda=lda - 4), dict(lda=lda + 1),
+            dict(BT=BIG, R=4096)],
+        "egv_patch_gather_u8_eval": null("frames", "a_hi", "mean", "std") + zero("F", "BT", "C", "Hs", "Ws", "S", "R", "P") + [
+            dict(std=std0), dict(std=stdn), dict(C=5), dict(BT=BT + 1), dict(R=24), dict(R=30, P=6), dict(P=15), dict(lda=lda - 2),
+            dict(lda=lda + 1), dict(S=1 << 20), dict(index=p(keep), BT=BIG, R=4096)],
+        "egv_assemble_tokens": null("pe", "cls", "pos", "temporal", "x") + zero("B", "T", "n", "D") + [dict(D=6), dict(B=BIG, T=64, n=1024, D=1024)],
+        "egv_assemble_tokens_sel": null("pe", "cls", "pos", "temporal", "keep", "x") + zero("B", "T", "K", "D") + [dict(K=n + 1), dict(D=6),
+                                   dict(B=BIG, T=64, n=1024, K=1024, D=1024)],
+        "egv_assemble_tokens_bwd": null("dx") + zero("B", "T", "n", "D") + [dict(D=6), dict(T_model=T - 1), dict(B=BIG, T=64, T_model=64, n=1024, D=1024)],
+        "egv_assemble_tokens_bwd_sel": null("dx", "keep") + zero("B", "T", "K", "D") + [dict(K=n + 1), dict(D=6), dict(T_model=T - 1),
+                                       dict(B=BIG, T=64, T_model=64, n=1024, K=1024, D=1024)],
+    }
+    u8_extra = null("mean", "std") + [dict(std=std0), dict(std=stdn), dict(C=5)]
+    bad["egv_patch_gather_u8"] = bad["egv_patch_gather"] + u8_extra
+    bad["egv_patch_gather_u8_sel"] = bad["egv_patch_gather_sel"] + u8_extra
+    bad["egv_patch_gather_u8_aug_sel"] = bad["egv_patch_gather_u8_aug"][:-1] + null("keep") + [dict(K=0), dict(K=n + 1), dict(lda=lda + 2),
+                                                                                             dict(BT=BIG, R=4096, K=65536)]
+    assert bad.keys() == valid.keys()
+    for name, cases in bad.items():
+        for case in cases:
+            assert case.keys() <= valid[name].keys(), (name, case)
+            assert getattr(h, name)(*{**valid[name], **case}.values()) == 1, (name, case)
+    torch.cuda.synchronize()
+    assert bool((hi == -7).all()) and bool((lo == -7).all())
+    assert all(bool((t == -7.0).all()) for t in (x, d_pe, d_cls, d_pos, d_tmp))
 
 
 # ------------------------------------------------------------------------------------------------ 4. the tower
