@@ -153,7 +153,8 @@ __global__ __launch_bounds__(256) void patch_gather_sel_kernel(const void* __res
 }
 
 // ---- train-time augmentation fused into the patch gather (data_loader/transforms.py:14-19: RandomResizedCrop(
-// input_res, scale) -> RandomHorizontalFlip -> ColorJitter(0, 0, 0) = identity -> Normalize) -----------------------------------
+// input_res, scale) -> RandomHorizontalFlip -> ColorJitter(brightness, saturation, hue) -> Normalize; the jitter is the identity in
+// the pre-training config and lives in the *_color kernels further down) ---------------------------------------------------------
 // The loader hands over the DECODED uint8 clip [B*T, C, Hs, Ws] and five ints per clip -- the crop box (top, left, h, w) and a
 // flip flag, the random draws of the host transform (one box per clip: the reference applies the transform to the [T, C, H, W]
 // tensor as a whole).  Every output pixel of the R x R frame is sampled here: x / 255 first (the reference resizes float frames),
@@ -199,8 +200,31 @@ __device__ __forceinline__ void store_patch4(const float (&v)[4], int bt, int c,
     }
   }
 }
+// The same group into row orow of the planes of a gather over kept patches: the pixels of it that lie in the patch.  ix = column of the
+// group's first pixel inside the patch row, -2 .. P - 2.
+__device__ __forceinline__ void store_patch4_sel(const float (&v)[4], long orow, int c, int iy, int ix, int P, bf16_t* ahi, bf16_t* alo,
+                                                 long lda) {
+  bf16_t* const dhi = ahi + orow * lda + (c * P + iy) * P;
+  bf16_t* const dlo = alo ? alo + orow * lda + (c * P + iy) * P : nullptr;
+  if (ix >= 0 && ix + 3 < P && (((orow * lda + (c * P + iy) * P + ix) & 3) == 0)) {
+    uint32_t h0, h1, l0, l1;
+    split_bf16x2(v[0], v[1], h0, l0);
+    split_bf16x2(v[2], v[3], h1, l1);
+    *(u32x2_t*)(dhi + ix) = (u32x2_t){h0, h1};
+    if (dlo) *(u32x2_t*)(dlo + ix) = (u32x2_t){l0, l1};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (ix + e < 0 || ix + e >= P) continue;
+      bf16_t h, l;
+      split_bf16(v[e], h, l);
+      dhi[ix + e] = h;
+      if (dlo) dlo[ix + e] = l;
+    }
+  }
+}
 // One output row of the resized crop of frame bt, channel c: the clamped box, the two source rows behind output row y and the
-// Normalize constants.  pixel(ox) is output pixel ox of that row, normalised.
+// Normalize constants.  sample(ox) is output pixel ox of that row in [0, 1], pixel(ox) the same normalised.
 struct AugRow {
   const unsigned char *r0, *r1;
   float ly, sx, mu, sd;
@@ -228,7 +252,7 @@ struct AugRow {
     mu = nrm.mean[c];
     sd = nrm.std[c];
   }
-  __device__ __forceinline__ float pixel(int ox) const {
+  __device__ __forceinline__ float sample(int ox) const {
     const int sxi = flip ? R - 1 - ox : ox;               // RandomHorizontalFlip acts on the resized crop
     float fx = ((float)sxi + 0.5f) * sx - 0.5f;
     fx = fx < 0.f ? 0.f : fx;
@@ -237,9 +261,9 @@ struct AugRow {
     const float lx = fx - (float)x0;
     const float p00 = (float)r0[x0] / 255.0f, p01 = (float)r0[x1] / 255.0f;
     const float p10 = (float)r1[x0] / 255.0f, p11 = (float)r1[x1] / 255.0f;
-    const float val = (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
-    return (val - mu) / sd;
+    return (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
   }
+  __device__ __forceinline__ float pixel(int ox) const { return (sample(ox) - mu) / sd; }
 };
 __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned char* __restrict__ video, int BT, int T, int C,
                                                                int Hs, int Ws, int R, int P, const int* __restrict__ boxes,
@@ -290,25 +314,142 @@ __global__ __launch_bounds__(256) void patch_gather_aug_sel_kernel(const unsigne
   float v[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = row.pixel(xq * 4 + e);
-  const int ix = xq * 4 - px * P;               // column of the group's first pixel inside the patch row: -2 .. P - 2
-  bf16_t* const dhi = ahi + orow * lda + (c * P + iy) * P;
-  bf16_t* const dlo = alo ? alo + orow * lda + (c * P + iy) * P : nullptr;
-  if (ix >= 0 && ix + 3 < P && (((orow * lda + (c * P + iy) * P + ix) & 3) == 0)) {
-    uint32_t h0, h1, l0, l1;
-    split_bf16x2(v[0], v[1], h0, l0);
-    split_bf16x2(v[2], v[3], h1, l1);
-    *(u32x2_t*)(dhi + ix) = (u32x2_t){h0, h1};
-    if (dlo) *(u32x2_t*)(dlo + ix) = (u32x2_t){l0, l1};
-  } else {
+  store_patch4_sel(v, orow, c, iy, xq * 4 - px * P, P, ahi, alo, lda);
+}
+
+// ---- ColorJitter(brightness, saturation, hue) of the train transform (torchvision 0.13's tensor path, restated; contrast cannot be
+// set by the reference's configs) ---------------------------------------------------------------------------------------------------
+// The host draws, per clip, color[b] = (brightness factor, saturation factor, hue shift, code): code holds three base-4 digits, the
+// first applied op lowest (0 nothing, 1 brightness, 2 saturation, 3 hue), i.e. which ops run and in torchvision's random order.  The
+// ops act on RGB in [0, 1] after crop / resize / flip and before Normalize, and saturation and hue mix the channels: a thread owns
+// an aligned 4-pixel group of an output row for ALL THREE channels.  The arithmetic follows the fp32 restatement operation for
+// operation with contraction OFF: no product is fused into a neighbouring sum, whichever way the compiler packs the twelve values,
+// so the kept-patch twin computes the bits of the full kernel (and the jitter's own error is that of the fp32 host transform).
+// No table value addresses anything: (int)code & 63 only selects among the three bodies; a non-finite factor gives NaN pixels (the
+// clamps are comparisons, which let a NaN through) in the frames of that clip only.
+__device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
+// blend(x, 0, f)
+__device__ __forceinline__ void jitter_brightness(float& r, float& g, float& b, float f) {
+#pragma clang fp contract(off)
+  r = clamp01(f * r);
+  g = clamp01(f * g);
+  b = clamp01(f * b);
+}
+// blend(x, gray, f)
+__device__ __forceinline__ void jitter_saturation(float& r, float& g, float& b, float f) {
+#pragma clang fp contract(off)
+  const float gray = (1.0f - f) * (0.2989f * r + 0.587f * g + 0.114f * b);
+  r = clamp01(f * r + gray);
+  g = clamp01(f * g + gray);
+  b = clamp01(f * b + gray);
+}
+// rgb -> hsv, h -> (h + d) mod 1, hsv -> rgb.  Selects only: every lane runs the same instructions whatever its pixel's sector.
+__device__ __forceinline__ void jitter_hue(float& r, float& g, float& b, float d) {
+#pragma clang fp contract(off)
+  const float maxc = fmaxf(fmaxf(r, g), b), minc = fminf(fminf(r, g), b);
+  const bool eq = maxc == minc;
+  const float cr = maxc - minc;
+  const float s = cr / (eq ? 1.0f : maxc);
+  const float dv = eq ? 1.0f : cr;
+  const float rc = (maxc - r) / dv, gc = (maxc - g) / dv, bc = (maxc - b) / dv;
+  const float hp = maxc == r ? bc - gc : (maxc == g ? 2.0f + rc - bc : 4.0f + gc - rc);
+  float h = hp / 6.0f + 1.0f;
+  h -= floorf(h);                                 // fmod(., 1) of a positive number: exact
+  h += d;
+  h -= floorf(h);                                 // Python's %: the sign of the divisor
+  const float v = maxc;
+  const float h6 = h * 6.0f;
+  const float fl = floorf(h6);
+  const float f = h6 - fl;
+  int i = (int)fl;                                // 0 .. 6 (h may round up to 1); NaN -> 0
+  i = i >= 6 ? i - 6 : i;
+  const float p = clamp01(v * (1.0f - s));
+  const float q = clamp01(v * (1.0f - s * f));
+  const float t = clamp01(v * (1.0f - s * (1.0f - f)));
+  r = i == 0 ? v : i == 1 ? q : i == 2 ? p : i == 3 ? p : i == 4 ? t : v;
+  g = i == 0 ? t : i == 1 ? v : i == 2 ? v : i == 3 ? q : i == 4 ? p : p;
+  b = i == 0 ? p : i == 1 ? p : i == 2 ? t : i == 3 ? v : i == 4 ? v : q;
+}
+
+// Pixels x4 .. x4 + 3 of output row y of frame bt, the three channels: sampled by AugRow, jittered as the clip's code says, normalised.
+// The code is the same for every thread of a frame, so the dispatch is a branch the whole wave takes together (bar the one wave in
+// which one clip ends and the next begins).
+__device__ __forceinline__ void aug_color_group(const unsigned char* __restrict__ video, const int* __restrict__ boxes,
+                                                const float* __restrict__ color, int bt, int T, int Hs, int Ws, int R, int y, int x4,
+                                                const PatchNorm& nrm, float (&v)[3][4]) {
+  const AugRow rows[3] = {AugRow(video, boxes, bt, T, 3, 0, Hs, Ws, R, y, nrm), AugRow(video, boxes, bt, T, 3, 1, Hs, Ws, R, y, nrm),
+                          AugRow(video, boxes, bt, T, 3, 2, Hs, Ws, R, y, nrm)};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (ix + e < 0 || ix + e >= P) continue;
-      bf16_t h, l;
-      split_bf16(v[e], h, l);
-      dhi[ix + e] = h;
-      if (dlo) dlo[ix + e] = l;
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[c][e] = rows[c].sample(x4 + e);
+  const float* cj = color + (long)(bt / T) * 4;
+  const float fb = cj[0], fs = cj[1], fh = cj[2];
+  int code = (int)cj[3] & 63;
+#pragma unroll
+  for (int k = 0; k < 3; ++k, code >>= 2) {
+    const int op = code & 3;
+    if (op == 1) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) jitter_brightness(v[0][e], v[1][e], v[2][e], fb);
+    } else if (op == 2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) jitter_saturation(v[0][e], v[1][e], v[2][e], fs);
+    } else if (op == 3) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) jitter_hue(v[0][e], v[1][e], v[2][e], fh);
     }
   }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[c][e] = (v[c][e] - rows[c].mu) / rows[c].sd;
+}
+
+__global__ __launch_bounds__(256) void patch_gather_aug_color_kernel(const unsigned char* __restrict__ video, int BT, int T, int Hs,
+                                                                     int Ws, int R, int P, const int* __restrict__ boxes,
+                                                                     const float* __restrict__ color, bf16_t* __restrict__ ahi,
+                                                                     bf16_t* __restrict__ alo, long lda, const PatchNorm nrm) {
+  // thread -> (image bt, output row y, 4-pixel group xg), all three channels
+  const int WG = R / 4;
+  const long total = (long)BT * R * WG;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int xg = (int)(i % WG);
+  const long t = i / WG;
+  const int y = (int)(t % R);
+  const int bt = (int)(t / R);
+  float v[3][4];
+  aug_color_group(video, boxes, color, bt, T, Hs, Ws, R, y, xg * 4, nrm, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) store_patch4(v[c], bt, c, y, xg * 4, R, P, ahi, alo, lda);
+}
+
+// The same over the kept patches: thread -> (output row bt * K + j, patch row iy, group g), the straddling rule of
+// patch_gather_aug_sel_kernel.
+__global__ __launch_bounds__(256) void patch_gather_aug_color_sel_kernel(const unsigned char* __restrict__ video, int BT, int T, int Hs,
+                                                                         int Ws, int R, int P, int NG, const int* __restrict__ boxes,
+                                                                         const float* __restrict__ color, const int* __restrict__ keep,
+                                                                         int K, bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo,
+                                                                         long lda, const PatchNorm nrm) {
+  const long total = (long)BT * K * P * NG;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int g = (int)(i % NG);
+  const long t = i / NG;
+  const int iy = (int)(t % P);
+  const long orow = t / P;                      // bt * K + j
+  const int bt = (int)(orow / K);
+  const int gw = R / P;
+  const int pos = keep_at(keep, (long)(bt / T) * K + (orow - (long)bt * K), gw * gw);
+  const int py = pos / gw, px = pos - py * gw;
+  const int xq = (px * P) / 4 + g;              // the 4-pixel group of the whole output row
+  if (xq * 4 >= (px + 1) * P) return;
+  float v[3][4];
+  aug_color_group(video, boxes, color, bt, T, Hs, Ws, R, py * P + iy, xq * 4, nrm, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) store_patch4_sel(v[c], orow, c, iy, xq * 4 - px * P, P, ahi, alo, lda);
 }
 
 // ---- val / test transform fused into the patch gather (data_loader/transforms.py:49-60: Resize(S) -> CenterCrop(S) -> Resize(R) ->
@@ -593,17 +734,22 @@ int patch_gather_launch(const void* video, int BT, int T, int C, int H, int W, i
 }
 
 // the train-transform gathers: the R x R output frame is the gather's geometry, the Hs x Ws source only has to exist
+// color (NULL: no jitter): the jitter table of the *_color entry points, which have checked it and C == 3 -- one thread then owns a
+// group of all three channels
 int patch_gather_aug_launch(const uint8_t* video, int BT, int T, int C, int Hs, int Ws, int R, int P, const int32_t* boxes,
-                            const float* mean, const float* std, const int32_t* keep, int K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda,
-                            void* stream) {
+                            const float* color, const float* mean, const float* std, const int32_t* keep, int K, egv_bf16* a_hi,
+                            egv_bf16* a_lo, int64_t lda, void* stream) {
   PatchNorm nrm{};
   if (!boxes || Hs <= 0 || Ws <= 0 || R % 4 != 0 || !fill_norm(nrm, mean, std, C)) return EGV_ERR_ARG;
   if (!gather_geom_ok(video, a_hi, BT, T, C, R, R, P, lda, keep ? 4 : 2, keep, K)) return EGV_ERR_ARG;
   const int NG = P % 4 == 0 ? P / 4 : (P + 2) / 4;           // 4-pixel groups of the output row that can touch one patch row
+  const int CT = color ? 1 : C;                              // channels walked by the thread map
   dim3 grid;
-  if (!grid_of(keep ? (long)BT * K * C * P * NG : (long)BT * C * R * (R / 4), grid)) return EGV_ERR_ARG;
+  if (!grid_of(keep ? (long)BT * K * CT * P * NG : (long)BT * CT * R * (R / 4), grid)) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  if (keep) EGV_LAUNCH(patch_gather_aug_sel_kernel, grid, dim3(256), 0, s, video, BT, T, C, Hs, Ws, R, P, NG, boxes, keep, K, a_hi, a_lo, (long)lda, nrm);
+  if (color && keep) EGV_LAUNCH(patch_gather_aug_color_sel_kernel, grid, dim3(256), 0, s, video, BT, T, Hs, Ws, R, P, NG, boxes, color, keep, K, a_hi, a_lo, (long)lda, nrm);
+  else if (color) EGV_LAUNCH(patch_gather_aug_color_kernel, grid, dim3(256), 0, s, video, BT, T, Hs, Ws, R, P, boxes, color, a_hi, a_lo, (long)lda, nrm);
+  else if (keep) EGV_LAUNCH(patch_gather_aug_sel_kernel, grid, dim3(256), 0, s, video, BT, T, C, Hs, Ws, R, P, NG, boxes, keep, K, a_hi, a_lo, (long)lda, nrm);
   else EGV_LAUNCH(patch_gather_aug_kernel, grid, dim3(256), 0, s, video, BT, T, C, Hs, Ws, R, P, boxes, a_hi, a_lo, (long)lda, nrm);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
@@ -690,7 +836,7 @@ extern "C" int egv_patch_gather_u8_sel(const uint8_t* video, int32_t BT, int32_t
 extern "C" int egv_patch_gather_u8_aug(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws,
                                        int32_t R, int32_t P, const int32_t* boxes, const float* mean, const float* std,
                                        egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
-  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, mean, std, nullptr, 0, a_hi, a_lo, lda, stream);
+  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, nullptr, mean, std, nullptr, 0, a_hi, a_lo, lda, stream);
 }
 
 extern "C" int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws,
@@ -698,7 +844,22 @@ extern "C" int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int
                                            const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda,
                                            void* stream) {
   if (!keep) return EGV_ERR_ARG;
-  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, mean, std, keep, K, a_hi, a_lo, lda, stream);
+  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, nullptr, mean, std, keep, K, a_hi, a_lo, lda, stream);
+}
+
+extern "C" int egv_patch_gather_u8_aug_color(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws,
+                                             int32_t R, int32_t P, const int32_t* boxes, const float* color, const float* mean,
+                                             const float* std, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  if (!color || C != 3) return EGV_ERR_ARG;
+  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, color, mean, std, nullptr, 0, a_hi, a_lo, lda, stream);
+}
+
+extern "C" int egv_patch_gather_u8_aug_color_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws,
+                                                 int32_t R, int32_t P, const int32_t* boxes, const float* color, const float* mean,
+                                                 const float* std, const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo,
+                                                 int64_t lda, void* stream) {
+  if (!color || C != 3 || !keep) return EGV_ERR_ARG;
+  return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, color, mean, std, keep, K, a_hi, a_lo, lda, stream);
 }
 
 extern "C" int egv_patch_gather_u8_eval(const uint8_t* frames, int32_t F, const int32_t* index, int32_t BT, int32_t C, int32_t Hs,

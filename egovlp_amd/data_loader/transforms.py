@@ -1,12 +1,22 @@
 """Device-side counterpart of the reference's TRAIN transform (data_loader/transforms.py:14-19):
 
-    RandomResizedCrop(input_res, scale=randcrop_scale) -> RandomHorizontalFlip() -> ColorJitter(0, 0, 0) -> Normalize(mean, std)
+    RandomResizedCrop(input_res, scale=randcrop_scale) -> RandomHorizontalFlip()
+        -> ColorJitter(brightness=color_jitter[0], saturation=color_jitter[1], hue=color_jitter[2]) -> Normalize(mean, std)
 
 The reference runs it on the host, on float frames, and ships 4 x 3 x 224 x 224 floats per clip to the GPU.  Here only the
 RANDOM DRAWS stay on the host -- `train_transform_params` returns, per clip, the crop box and the flip flag -- and the pixels
 are produced by `egv_patch_gather_u8_aug` straight from the decoded uint8 clip inside the patch gather of the video encoder
 (`SpaceTimeTransformer.set_input_augmentation`).  One box per clip, as in the reference (the transform is applied to the
 [T, C, H, W] tensor as a whole).
+
+The colour jitter is the identity in the pre-training config (`color_jitter` = (0, 0, 0)) and a real stage in fine-tuning
+configs such as (0.4, 0.4, 0.1).  `train_transform_params_color` draws, next to the boxes, one row per clip of (brightness
+factor, saturation factor, hue shift, op code) in torchvision 0.13's order -- `randperm(4)` over (brightness, contrast,
+saturation, hue), then the factors of the enabled ops -- and `egv_patch_gather_u8_aug_color` applies the ops between the flip
+and Normalize (`set_input_augmentation(boxes, out_res, color)`).  A scalar b means the range [max(0, 1 - b), 1 + b] for
+brightness and saturation and [-h, h], 0 <= h <= 0.5, for hue; a (min, max) pair is taken as it is; a range that collapses onto
+the identity value disables the op (skipped, not run with factor 1: the hue round trip is not the identity in fp32).  Contrast
+cannot be set through the reference's `init_transform_dict` and is skipped wherever it lands in the permutation.
 
 The 'val' / 'test' transform (data_loader/transforms.py:49-60) is deterministic:
 
@@ -56,6 +66,57 @@ def train_transform_params(batch, height, width, randcrop_scale=(0.5, 1.0), flip
         flip = int(float(torch.rand(1, generator=generator)) < flip_p)
         rows.append([i, j, h, w, flip])
     return torch.tensor(rows, dtype=torch.int32)
+
+
+def _jitter_range(value, name, center, bound, clip_first_on_zero=True):
+    """torchvision 0.13 `ColorJitter._check_input`: -> (min, max), or None where the range is the identity value alone."""
+    if isinstance(value, (int, float)):
+        if value < 0:
+            raise ValueError(f"color_jitter: a scalar {name} is non-negative")
+        lo, hi = center - float(value), center + float(value)
+        if clip_first_on_zero:
+            lo = max(lo, 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        raise TypeError(f"color_jitter: {name} is a number or a (min, max) pair")
+    if not bound[0] <= lo <= hi <= bound[1]:
+        raise ValueError(f"color_jitter: {name} values lie in {bound}, got ({lo}, {hi})")
+    return None if lo == hi == center else (lo, hi)
+
+
+def train_transform_params_color(batch, height, width, randcrop_scale, color_jitter, flip_p=0.5, generator=None):
+    """-> (boxes int32 [batch, 5], color float32 [batch, 4] or None): the host half of the fused train transform with
+    ColorJitter(brightness=color_jitter[0], saturation=color_jitter[1], hue=color_jitter[2]).  Per clip, in this order: the box,
+    the flip, `randperm(4)`, then the brightness, saturation and hue draws of the enabled ops (torchvision's `get_params`).
+    color[b] = (brightness factor, saturation factor, hue shift, code); code is three base-4 digits stored exactly in the float,
+    the first applied op lowest (0 nothing, 1 brightness, 2 saturation, 3 hue).  With every op disabled: color is None and the
+    boxes are those of `train_transform_params` from the same generator state."""
+    if len(color_jitter) != 3:
+        raise ValueError("color_jitter: (brightness, saturation, hue)")
+    ranges = (_jitter_range(color_jitter[0], "brightness", 1.0, (0.0, float("inf"))),
+              _jitter_range(color_jitter[1], "saturation", 1.0, (0.0, float("inf"))),
+              _jitter_range(color_jitter[2], "hue", 0.0, (-0.5, 0.5), clip_first_on_zero=False))
+    if all(r is None for r in ranges):
+        return train_transform_params(batch, height, width, randcrop_scale, flip_p, generator), None
+    digit = {0: 1, 2: 2, 3: 3}                        # randperm index (1 = contrast: skipped) -> op digit
+    identity = (1.0, 1.0, 0.0)
+    boxes, color = [], []
+    for _ in range(batch):
+        i, j, h, w = random_resized_crop_box(height, width, randcrop_scale, generator=generator)
+        flip = int(float(torch.rand(1, generator=generator)) < flip_p)
+        boxes.append([i, j, h, w, flip])
+        order = torch.randperm(4, generator=generator).tolist()
+        factors = [identity[k] if r is None else float(torch.empty(1).uniform_(r[0], r[1], generator=generator))
+                   for k, r in enumerate(ranges)]
+        code = shift = 0
+        for fn in order:
+            d = digit.get(fn, 0)
+            if d and ranges[d - 1] is not None:
+                code |= d << shift
+                shift += 2
+        color.append(factors + [float(code)])
+    return torch.tensor(boxes, dtype=torch.int32), torch.tensor(color, dtype=torch.float32)
 
 
 def eval_transform_geometry(height, width, center_crop=256):

@@ -382,7 +382,10 @@ class _PatchTokensFn(torch.autograd.Function):
             a = ops.patch_gather_eval(video.contiguous(), ev[2], T, P_, Pp, ev[0], ev[1], mean, std)
         else:
             # uint8 frames: /255 + Normalize (and, with `aug`, the train transform's crop / resize / flip) inside the gather
-            a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug, keep=keep)
+            if aug is not None and len(aug) > 2:       # (boxes, out_res, colour-jitter table)
+                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug[:2], keep=keep, color=aug[2])
+            else:
+                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug, keep=keep)
         K = proj_w[0].numel()
         if a.cols == K:
             w_pl = wc.get(proj_w, need_t=False)[0]
@@ -644,18 +647,32 @@ class SpaceTimeTransformer(nn.Module):
     def no_weight_decay(self):
         return {'pos_embed', 'cls_token'}
 
-    def set_input_augmentation(self, boxes, out_res=None):
+    def set_input_augmentation(self, boxes, out_res=None, color=None):
         """Fuse the loader's train transform into the NEXT forward: `boxes` int32 [B, 5] (top, left, h, w, flip; see
         egovlp_amd.data_loader.transforms.train_transform_params) select, per clip, the region of the decoded uint8 frames
         that is resized to `out_res` (default: the model's img_size), flipped and normalised inside the patch gather.
+        `color` (float [B, 4]: brightness factor, saturation factor, hue shift, op code -- train_transform_params_color): the
+        transform's ColorJitter, applied per clip between the flip and Normalize.  A host-resident table is validated here; a
+        device table is taken as it is (no sync; the kernel masks the code and a bad factor spoils that clip's pixels only).
         One-shot: consumed by the next forward_features call."""
         if getattr(self, "_input_eval", None) is not None:
             raise ValueError("set_input_augmentation: an eval transform is pending for the next forward (set_input_eval_transform)")
         host = boxes.detach().to(dtype=torch.int64).cpu() if not boxes.is_cuda else None     # checked against the frame size in forward
         if host is not None and (host.dim() != 2 or host.shape[1] != 5 or bool((host[:, :2] < 0).any()) or bool((host[:, 2:4] < 1).any())):
             raise ValueError("set_input_augmentation: boxes are int [B, 5] rows (top >= 0, left >= 0, h >= 1, w >= 1, flip)")
-        self._input_aug = (boxes.to(device=self.cls_token.device, dtype=torch.int32).contiguous(),
-                           int(out_res or self.patch_embed.img_size[0]), host)
+        aug = (boxes.to(device=self.cls_token.device, dtype=torch.int32).contiguous(), int(out_res or self.patch_embed.img_size[0]), host)
+        if color is not None:
+            if not torch.is_tensor(color) or not color.is_floating_point() or color.dim() != 2 or tuple(color.shape) != (boxes.shape[0], 4):
+                raise ValueError("set_input_augmentation: color is a float [B, 4] table (brightness, saturation, hue, op code), one row per box")
+            if not color.is_cuda:
+                c = color.detach().double()
+                code = c[:, 3]
+                if not bool(torch.isfinite(c).all()) or bool((c[:, :2] < 0).any()) or bool((c[:, 2].abs() > 0.5).any()) \
+                        or bool((code != code.round()).any()) or bool((code < 0).any()) or bool((code > 63).any()):
+                    raise ValueError("set_input_augmentation: color rows are finite, brightness and saturation factors >= 0, "
+                                     "|hue shift| <= 0.5, op code an integer in 0..63")
+            aug = aug + (color.to(device=self.cls_token.device, dtype=torch.float32).contiguous(),)
+        self._input_aug = aug
 
     def set_input_eval_transform(self, center_crop=256, out_res=None, frame_index=None):
         """Fuse the loader's val / test transform (Resize(center_crop) -> CenterCrop(center_crop) -> Resize(out_res) -> Normalize,
@@ -706,7 +723,7 @@ class SpaceTimeTransformer(nn.Module):
             if host is not None and (host.shape[0] != b or bool((host[:, 0] + host[:, 2] > Hh).any())
                                      or bool((host[:, 1] + host[:, 3] > Ww).any())):
                 raise ValueError(f"set_input_augmentation: a crop box leaves the {Hh} x {Ww} frame (or the batch size changed)")
-            aug = aug[:2]
+            aug = aug[:2] + aug[3:]                                            # (boxes, out_res[, colour-jitter table])
             Hh = Ww = aug[1]                                                   # the resized crop is what gets patched
         n = (Hh // P_) * (Ww // P_)
         if n != self.patches_per_frame:

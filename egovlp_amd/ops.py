@@ -988,12 +988,15 @@ def patch_keep_draw(B, n, K, seed, seed_dev=None, device="cuda"):
     return keep
 
 
-def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None, keep=None) -> Planes:
+def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None, keep=None, color=None) -> Planes:
     """im2col planes [B*T*patches, K = C*P*P]; K is padded with zero columns to a multiple of 64 (the GEMM k-tile;
     588 -> 640 for ViT-L/14), `cols` of the returned planes is the PADDED width.  A uint8 `video5d` (decoded frames) is
     scaled and normalised in the kernel (x / 255, then (x - mean) / std per channel) -- the loader's host transform.
     aug = (boxes int32 [B, 5] on the device: top, left, h, w, flip; out_res): the train transform (RandomResizedCrop +
     RandomHorizontalFlip, data_loader/transforms.py:14-19) runs inside the gather on the decoded uint8 clip.
+    color (needs `aug` and 3 channels): contiguous fp32 [B, 4] on the device, per clip (brightness factor, saturation factor, hue
+    shift, op code) as `data_loader.transforms.train_transform_params_color` draws them -- the transform's ColorJitter, applied
+    between the flip and Normalize (the egv_patch_gather_u8_aug_color kernels).  None: the calls made without it.
     keep (patch dropout): int32 [B, Kp] on the device -- only those patch positions of every frame of clip b are gathered, row
     bt * Kp + j = patch keep[bt // T][j] of frame bt, the bits of that row of the full gather (the egv_patch_gather*_sel kernels)."""
     B, T, Cc, H, W = video5d.shape
@@ -1004,6 +1007,12 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
         if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, 5) or not boxes.is_cuda or not boxes.is_contiguous():
             raise ValueError("aug boxes: contiguous int32 [B, 5] on the device (top, left, h, w, flip)")
         H = W = int(R)
+    if color is not None:
+        if aug is None or Cc != 3:
+            raise ValueError("patch_gather: the colour jitter is a stage of the fused train transform (aug=...) on 3-channel frames")
+        if not torch.is_tensor(color) or color.dtype != torch.float32 or tuple(color.shape) != (B, 4) or not color.is_cuda \
+                or not color.is_contiguous():
+            raise ValueError("color: contiguous float32 [B, 4] on the device (brightness, saturation, hue, op code)")
     n = (H // P) * (W // P)
     per_frame = n if keep is None else _check_keep(keep, B, n, "patch_gather")
     rows = B * T * per_frame
@@ -1013,11 +1022,15 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
     if u8 and (len(norm_mean) != Cc or len(norm_std) != Cc):
         raise ValueError("patch_gather: one mean / std per channel")
     pl = empty_planes(rows, Kp, passes, video5d.device, zero=(Kp != K))
-    # egv_patch_gather[_u8[_aug]][_sel](video, B*T, [T,] C, geometry, [mean, std,] [keep, K,] planes, lda, stream); "_aug" only ever
-    # follows "_u8" (aug with fp32 frames was refused above), so the six names this can form are the six entry points
-    name = "egv_patch_gather" + ("_u8" if u8 else "") + ("_aug" if aug is not None else "") + ("" if keep is None else "_sel")
+    # egv_patch_gather[_u8[_aug[_color]]][_sel](video, B*T, [T,] C, geometry, [color,] [mean, std,] [keep, K,] planes, lda, stream);
+    # "_aug" only ever follows "_u8" (aug with fp32 frames was refused above) and "_color" only "_aug", so the eight names this can
+    # form are the eight entry points
+    name = "egv_patch_gather" + ("_u8" if u8 else "") + ("_aug" if aug is not None else "") + ("" if color is None else "_color") \
+        + ("" if keep is None else "_sel")
     clip = (T,) if aug is not None or keep is not None else ()
     geom = (H, W, P) if aug is None else (video5d.shape[3], video5d.shape[4], H, P, _p(aug[0]))
+    if color is not None:
+        geom = geom + (_p(color),)
     norm = ((C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)) if u8 else ()
     sel = () if keep is None else (_p(keep), per_frame)
     check(getattr(_lib.lib(), name)(_p(video5d), B * T, *clip, Cc, *geom, *norm, *sel, _p(pl.hi), _p(pl.lo), pl.ld,

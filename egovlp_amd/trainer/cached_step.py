@@ -33,13 +33,14 @@ def _rows(data, lo, hi):
 
 
 def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, rank=0, grad_sync=None, scaler=None, aug_boxes=None,
-                        check_replay=False, fused_head=True):
+                        check_replay=False, fused_head=True, aug_color=None):
     """`egoclip_step` with the per-GPU batch encoded `chunk` rows at a time: the loss and the gradients are those of the whole batch
     of B rows (times the world size), the activations held at any time those of one chunk.  `data`: one device batch as for
     `egoclip_step`; the last chunk may be shorter, `chunk >= B` is a single chunk.  Returns the detached (device) loss; no host sync.
 
     `aug_boxes` (int [B, 5], SpaceTimeTransformer.set_input_augmentation): the train transform fused into the patch gather -- each
-    chunk's slice is set before BOTH of its forwards.  `grad_sync`: its exchange is held while the chunks run (a gradient that exists
+    chunk's slice is set before BOTH of its forwards; `aug_color` (float [B, 4], needs `aug_boxes`): the colour-jitter table that goes
+    with them, sliced the same way.  `grad_sync`: its exchange is held while the chunks run (a gradient that exists
     after the first chunk is a partial sum) and leaves from `finish()`, un-overlapped, once per step.  `scaler`: as in `egoclip_step`;
     an inf / NaN in any chunk's gradients survives the fp32 sums, so the optimizer's scan of the accumulators skips the step as ever.
 
@@ -56,13 +57,17 @@ def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, ra
     chunk = int(chunk)
     if chunk <= 0:
         raise ValueError("egoclip_step_cached: chunk is a positive number of rows")
+    if aug_color is not None and aug_boxes is None:
+        raise ValueError("egoclip_step_cached: aug_color is a stage of the fused train transform and needs aug_boxes")
     core, ec, scaler = step_prologue(model, optimizer, scaler)
     B = data['video'].shape[0]
     spans = [(lo, min(lo + chunk, B)) for lo in range(0, B, chunk)]
     video_model, text_model = getattr(core, 'video_model', None), getattr(core, 'text_model', None)
 
     def encode(lo, hi):
-        if aug_boxes is not None:
+        if aug_color is not None:
+            video_model.set_input_augmentation(aug_boxes[lo:hi], color=aug_color[lo:hi])
+        elif aug_boxes is not None:
             video_model.set_input_augmentation(aug_boxes[lo:hi])
         return model(_rows(data, lo, hi))
 

@@ -299,6 +299,17 @@ int egv_patch_gather_u8(const uint8_t* video, int32_t BT, int32_t C, int32_t H, 
 int egv_patch_gather_u8_aug(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
                             int32_t P, const int32_t* boxes, const float* mean, const float* std, egv_bf16* a_hi,
                             egv_bf16* a_lo, int64_t lda, void* stream);
+/* egv_patch_gather_u8_aug with the transform's third stage, ColorJitter(brightness, saturation, hue) (torchvision 0.13's tensor path;
+ * data_loader/transforms.py:16), between the flip and Normalize.  color[B][4] fp32 on the DEVICE, the host's draws per clip:
+ * (brightness factor, saturation factor, hue shift in [-0.5, 0.5], code).  code = three base-4 digits stored exactly in the float,
+ * the first applied op lowest: 0 nothing, 1 brightness, 2 saturation, 3 hue -- which ops run, in torchvision's random order.  On RGB
+ * in [0, 1]: brightness clamp(f x); saturation clamp(f x + (1 - f) gray), gray = 0.2989 r + 0.587 g + 0.114 b; hue rgb -> hsv,
+ * h -> (h + d) mod 1, hsv -> rgb.  The kernel reads (int)code & 63: no table value addresses anything; a non-finite factor gives NaN
+ * pixels in that clip's frames only.  C == 3 and color != NULL, else EGV_ERR_ARG (nothing launched), as for everything
+ * egv_patch_gather_u8_aug refuses.  Contrast (not settable in the reference's configs) is not implemented. */
+int egv_patch_gather_u8_aug_color(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
+                                  int32_t P, const int32_t* boxes, const float* color, const float* mean, const float* std,
+                                  egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
 /* The same gather with the VAL / TEST transform of the loader fused in (data_loader/transforms.py:49-60: Resize(S) -> CenterCrop(S)
  * -> Resize(R) -> Normalize, applied to x / 255 in fp32; bilinear, align_corners = False, no antialias).  `frames` is a bank of F
  * decoded uint8 frames [F, C, Hs, Ws]; output frame bt is made from bank frame index[bt] (`index`: int32 [BT] on the DEVICE, entries
@@ -342,6 +353,10 @@ int egv_patch_gather_u8_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t
 int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
                                 int32_t P, const int32_t* boxes, const float* mean, const float* std, const int32_t* keep,
                                 int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
+/* egv_patch_gather_u8_aug_color over the kept patches: the bits of its rows bt*n + keep[bt / T][j]. */
+int egv_patch_gather_u8_aug_color_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
+                                      int32_t P, const int32_t* boxes, const float* color, const float* mean, const float* std,
+                                      const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
 /* x[b,0,:] = cls + pos[0]; x[b,1+f*K+j,:] = (pe[(b*T+f)*K+j,:] + pos[1+keep[b][j]]) + temporal[f] (:305-320 on the kept tokens):
  * the sum order of egv_assemble_tokens, so the rows are bit-identical to the matching rows of the full assembly.                  */
 int egv_assemble_tokens_sel(const float* pe, const float* cls, const float* pos, const float* temporal, const int32_t* keep,
