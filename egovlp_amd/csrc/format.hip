@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void relu_split_kernel(const float* __restrict
   f32x4_t v = *(const f32x4_t*)(x + (long)r * ldx + c);
   bf16_t h[4], l[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) split_bf16(fmaxf(v[e], 0.f), h[e], l[e]);
+  for (int e = 0; e < 4; ++e) split_bf16(v[e] <= 0.f ? 0.f : v[e], h[e], l[e]);   // not fmaxf: nn.ReLU hands a NaN on, fmaxf(NaN, 0) is 0
   *(u32x2_t*)(hi + (long)r * ldo + c) = (u32x2_t){pack2(h[0], h[1]), pack2(h[2], h[3])};
   if (lo) *(u32x2_t*)(lo + (long)r * ldo + c) = (u32x2_t){pack2(l[0], l[1]), pack2(l[2], l[3])};
 }

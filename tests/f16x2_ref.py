@@ -29,6 +29,13 @@ def encode(x: torch.Tensor, role: int):
     return p1, p2, raw.to(torch.bfloat16)
 
 
+def rep_bound(x: torch.Tensor) -> torch.Tensor:
+    """|p1 + p2 - x| of the first-operand encoding (role 0), |x| <= 65504.  p1 = fp16(t) with t = fp32(x - x e); r = x - p1 is exact in
+    fp32 (p1 / x is within [1/2, 2]) and |r| <= (e + 2^-24 + 2^-11) |x|; p2 = fp16(r) is within half an fp16 ulp of r: 2^-11 |r|, or
+    2^-25 where r is subnormal in fp16.  So p1 + p2 - x = p2 - r, at most 2^-17 (1 + 2^-4) |x| + 2^-25."""
+    return x.abs().double() * (2.0 ** -17 * (1.0 + 2.0 ** -4)) + 2.0 ** -25
+
+
 def product(a1, a2, b1, b2) -> torch.Tensor:
     """What egv_gemm_nt(passes = 2) computes from encoded operands: A1 B1^T + A2 B2^T, in fp64."""
     return a1.double() @ b1.double().t() + a2.double() @ b2.double().t()
