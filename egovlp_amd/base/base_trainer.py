@@ -76,6 +76,9 @@ class Multi_BaseTrainer_dist:
         self.loss = loss.to(self.device) if hasattr(loss, 'to') else loss
         self.metrics = metrics
         self.optimizer = optimizer
+        # a loss with parameters of its own (learnable temperature) joins the optimizer -- before a resume loads the optimizer's state
+        from ..trainer.common import register_loss_parameters
+        self._loss_param_group = register_loss_parameters(optimizer, self.loss, lr=getattr(args, 'temperature_lr', None))
 
         cfg_trainer = config['trainer']
         self.epochs = cfg_trainer['epochs']
@@ -175,6 +178,10 @@ class Multi_BaseTrainer_dist:
         ec = getattr(getattr(self.model, 'module', self.model), 'exec_ctx', None)
         if ec is not None and getattr(ec, '_scaler', None) is not None:
             state['loss_scaler'] = ec._scaler.state_dict()
+        # the parameters of the loss (learnable temperature); a loss without any adds no key
+        loss_sd = self.loss.state_dict() if hasattr(self.loss, 'state_dict') else {}
+        if len(loss_sd) > 0:
+            state['loss_state_dict'] = loss_sd
         return state
 
     def _save_checkpoint(self, epoch, save_best=False):
@@ -197,6 +204,22 @@ class Multi_BaseTrainer_dist:
         if has:
             return type(state_dict)((k[len('module.'):], v) for k, v in state_dict.items())
         return type(state_dict)(('module.' + k, v) for k, v in state_dict.items())
+
+    def _load_optimizer_state(self, opt_state):
+        """optimizer.load_state_dict; a checkpoint written WITHOUT the loss's parameter group (a run at a fixed temperature) restores
+        the model's groups and leaves the loss's group as the constructor made it."""
+        group = getattr(self, '_loss_param_group', None)
+        live = self.optimizer.param_groups
+        if group is not None and live and live[-1] is group and len(opt_state['param_groups']) == len(live) - 1:
+            live.pop()
+            try:
+                self.optimizer.load_state_dict(opt_state)
+            finally:
+                self.optimizer.param_groups.append(group)
+        else:
+            self.optimizer.load_state_dict(opt_state)
+            if group is not None:
+                self._loss_param_group = self.optimizer.param_groups[-1]
 
     def _resume_checkpoint(self, resume_path):
         resume_path = str(resume_path)
@@ -223,7 +246,9 @@ class Multi_BaseTrainer_dist:
             self.logger.warning("Warning: Optimizer type given in config file is different from that of checkpoint. "
                                 "Optimizer parameters not being resumed.")
         else:
-            self.optimizer.load_state_dict(ckpt['optimizer'])
+            self._load_optimizer_state(ckpt['optimizer'])
+        if isinstance(ckpt.get('loss_state_dict'), dict) and hasattr(self.loss, 'load_state_dict'):
+            self.loss.load_state_dict(ckpt['loss_state_dict'])
         ec = getattr(getattr(self.model, 'module', self.model), 'exec_ctx', None)
         if ec is not None and isinstance(ckpt.get('loss_scaler'), dict):
             ec.loss_scaler().load_state_dict(ckpt['loss_scaler'])

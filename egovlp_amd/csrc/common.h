@@ -98,6 +98,24 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- contrastive heads: temperature by value or learnable ------------------------------------------------
+// 1 / tau as the host passed it, or -- learnable temperature -- exp(s) of the device-side logit scale s = log(1 / tau): no host read
+__device__ __forceinline__ float egv_inv_tau(float inv_tau, const float* __restrict__ logit_scale) {
+  return logit_scale ? expf(logit_scale[0]) : inv_tau;
+}
+// sum of `count` fp32 partials by ONE workgroup of 256 threads, in double and in a fixed order; valid in thread 0.  red: [256] doubles
+__device__ __forceinline__ double egv_sum_partials_256(const float* __restrict__ part, int count, double* red) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < count; i += 256) s += (double)part[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {                // pairwise, fixed order
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 // exact (erf) GELU and its derivative -- nn.GELU default, model/video_transformer.py:37.
 // erf by Abramowitz & Stegun 7.1.26 (|abs error| <= 1.5e-7, i.e. fp32 round-off class): one v_rcp, one v_exp and five
 // FMAs instead of ocml's ~25-instruction branchy erff.  The GELU epilogues of fc1 / fc2-dgrad apply this to 77 M elements

@@ -9,6 +9,10 @@
 //   m_ij   = (simv_ij * simn_ij + [i==j]) > 0                       (EgoNCE, noun & verb)
 //   loss   = -1/n sum_i [log sum_j m_ij a_ij - log sum_j a_ij]      a_ij = exp(x_ij / tau)
 //            -1/n sum_i [log sum_j m_ij a_ji - log sum_j a_ji]
+// Learnable temperature (the *_ls entry points): 1 / tau = exp(s) is read from the device, and with G = dL/dx
+//   dL/ds  = sum_ij G_ij x_ij                                       s = log(1 / tau)
+// falls out of the gradient kernel, which holds x_ij and G_ij: one block_sum per row into n partials, then one
+// workgroup adds them in a fixed order in double.  No float atomics: two calls give the same bits.
 #include "common.h"
 #include "egovlp_hip.h"
 
@@ -124,9 +128,11 @@ __global__ __launch_bounds__(256) void egonce_rows_kernel(const float* __restric
 
 // B2: row statistics rmax_i, Z_i = sum_j a_ij, P_i = sum_j m_ij a_ij
 __global__ __launch_bounds__(256) void egonce_rowstat_kernel(const float* __restrict__ x, const float* __restrict__ mask,
-                                                             int n, float inv_tau, float* __restrict__ rstat) {
+                                                             int n, float inv_tau, const float* __restrict__ logit_scale,
+                                                             float* __restrict__ rstat) {
   __shared__ float sh[4];
   const int i = blockIdx.x;
+  inv_tau = egv_inv_tau(inv_tau, logit_scale);
   float lmax = -3e38f;
   for (int j = threadIdx.x; j < n; j += 256) lmax = fmaxf(lmax, x[(long)i * n + j]);
   const float rmax = block_max(lmax, sh);
@@ -216,9 +222,11 @@ __global__ __launch_bounds__(256) void sim_bwd_kernel(const float* __restrict__ 
 
 // C: column statistics for column c: cmax_c, C_c = sum_r a_rc, Q_c = sum_r m_cr a_rc
 __global__ __launch_bounds__(256) void egonce_cols_kernel(const float* __restrict__ x, const float* __restrict__ mask,
-                                                          int n, float inv_tau, float* __restrict__ cstat /* [3][n] */) {
+                                                          int n, float inv_tau, const float* __restrict__ logit_scale,
+                                                          float* __restrict__ cstat /* [3][n] */) {
   __shared__ float sh[4];
   const int c = blockIdx.x;
+  inv_tau = egv_inv_tau(inv_tau, logit_scale);
   float lmax = -3e38f;
   for (int r = threadIdx.x; r < n; r += 256) lmax = fmaxf(lmax, x[(long)r * n + c]);
   const float cmax = block_max(lmax, sh);
@@ -237,11 +245,15 @@ __global__ __launch_bounds__(256) void egonce_cols_kernel(const float* __restric
   }
 }
 
-// D: G_ij = dL/dx_ij (row i per block)
+// D: G_ij = dL/dx_ij (row i per block); ls_part[i] = sum_j G_ij x_ij, row i's share of dL/d(logit scale), when asked for
 __global__ __launch_bounds__(256) void egonce_grad_kernel(const float* __restrict__ x, const float* __restrict__ mask,
                                                           const float* __restrict__ rstat, const float* __restrict__ cstat,
-                                                          int n, float inv_tau, float* __restrict__ G) {
+                                                          int n, float inv_tau, const float* __restrict__ logit_scale,
+                                                          float* __restrict__ G, float* __restrict__ ls_part) {
+  __shared__ float sh[4];
   const int i = blockIdx.x;
+  inv_tau = egv_inv_tau(inv_tau, logit_scale);
+  float gx = 0.f;
   const float rmax = rstat[i], Zi = rstat[n + i], Pi = rstat[2 * n + i];
   const float sc = -inv_tau / (float)n;
   for (int j = threadIdx.x; j < n; j += 256) {
@@ -250,8 +262,22 @@ __global__ __launch_bounds__(256) void egonce_grad_kernel(const float* __restric
     const float ac = __expf((xv - cstat[j]) * inv_tau);         // column-normalised numerator
     const float g_row = mask[(long)i * n + j] * ar / Pi - ar / Zi;
     const float g_col = mask[(long)j * n + i] * ac / cstat[2 * n + j] - ac / cstat[n + j];
-    G[(long)i * n + j] = sc * (g_row + g_col);
+    const float g = sc * (g_row + g_col);
+    G[(long)i * n + j] = g;
+    gx += g * xv;
   }
+  if (ls_part) {                                                  // uniform over the workgroup
+    gx = block_sum(gx, sh);
+    if (threadIdx.x == 0) ls_part[i] = gx;
+  }
+}
+
+// dL/d(logit scale) = sum of the n row partials; one workgroup, double, fixed order
+__global__ __launch_bounds__(256) void egonce_scale_grad_kernel(const float* __restrict__ ls_part, int n,
+                                                                float* __restrict__ d_logit_scale) {
+  __shared__ double red[256];
+  const double s = egv_sum_partials_256(ls_part, n, red);
+  if (threadIdx.x == 0) d_logit_scale[0] = (float)s;
 }
 
 // E: loss scalar + embedding gradients.  Block i, thread d.
@@ -301,10 +327,11 @@ extern "C" int64_t egv_egonce_work_floats(int32_t n, int32_t D) {
   return 2LL * n * D + 3LL * n * n + 16LL * n;
 }
 
-extern "C" int egv_egonce_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
-                                  int32_t n, int32_t D, int32_t dn, int32_t dv, float temperature, float eps,
-                                  int32_t use_noun, int32_t use_verb, float* loss, float* sim, float* d_text,
-                                  float* d_video, float* work, void* stream) {
+// the short head; logit_scale != NULL: 1 / tau = exp(*logit_scale) on the device and, with the gradients, *d_logit_scale
+static int egonce_head(const float* text, const float* video, const float* noun, const float* verb, int32_t n, int32_t D,
+                       int32_t dn, int32_t dv, float inv_tau, const float* logit_scale, float eps, int32_t use_noun,
+                       int32_t use_verb, float* loss, float* sim, float* d_text, float* d_video, float* d_logit_scale,
+                       float* work, void* stream) {
   if (!text || !video || !loss || !work || n <= 0 || n > 1024 || D <= 0 || D > 256 || D % 4 != 0) return EGV_ERR_ARG;
   if ((noun != nullptr) != (verb != nullptr)) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -316,7 +343,7 @@ extern "C" int egv_egonce_fwd_bwd(const float* text, const float* video, const f
   float* stats = G + (long)n * n;  // 4n
   float* rstat = stats + 4 * n;    // 3n
   float* cstat = rstat + 3 * n;    // 3n
-  const float inv_tau = 1.0f / temperature;
+  float* ls_part = cstat + 3 * n;  // n (the workspace has 16n behind the matrices)
   EGV_LAUNCH(egonce_norm_kernel, dim3(n), dim3(256), 0, s, text, video, noun, verb, n, D, dn, dv, eps, tn, vn,
                      stats);
   EGV_CHECK_LAUNCH();
@@ -324,19 +351,42 @@ extern "C" int egv_egonce_fwd_bwd(const float* text, const float* video, const f
   EGV_LAUNCH(egonce_rows_kernel, dim3(n), dim3(256), lds, s, tn, vn, noun, verb, stats, n, D, dn, dv, inv_tau,
                      use_noun, use_verb, x, mask, rstat);
   EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(egonce_rowstat_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, rstat);
+  EGV_LAUNCH(egonce_rowstat_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, logit_scale, rstat);
   EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(egonce_cols_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, cstat);
+  EGV_LAUNCH(egonce_cols_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, logit_scale, cstat);
   EGV_CHECK_LAUNCH();
   EGV_LAUNCH(egonce_loss_kernel, dim3(1), dim3(256), 0, s, rstat, cstat, n, loss);
   EGV_CHECK_LAUNCH();
   if (d_text || d_video) {
-    EGV_LAUNCH(egonce_grad_kernel, dim3(n), dim3(256), 0, s, x, mask, rstat, cstat, n, inv_tau, G);
+    EGV_LAUNCH(egonce_grad_kernel, dim3(n), dim3(256), 0, s, x, mask, rstat, cstat, n, inv_tau, logit_scale, G,
+               d_logit_scale ? ls_part : nullptr);
     EGV_CHECK_LAUNCH();
+    if (d_logit_scale) {
+      EGV_LAUNCH(egonce_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
+      EGV_CHECK_LAUNCH();
+    }
     EGV_LAUNCH(egonce_embgrad_kernel, dim3(n), dim3(256), 0, s, G, tn, vn, stats, n, D, eps, d_text, d_video);
     EGV_CHECK_LAUNCH();
   }
   return EGV_OK;
+}
+
+extern "C" int egv_egonce_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
+                                  int32_t n, int32_t D, int32_t dn, int32_t dv, float temperature, float eps,
+                                  int32_t use_noun, int32_t use_verb, float* loss, float* sim, float* d_text,
+                                  float* d_video, float* work, void* stream) {
+  return egonce_head(text, video, noun, verb, n, D, dn, dv, 1.0f / temperature, nullptr, eps, use_noun, use_verb, loss, sim,
+                     d_text, d_video, nullptr, work, stream);
+}
+
+extern "C" int egv_egonce_fwd_bwd_ls(const float* text, const float* video, const float* noun, const float* verb,
+                                     int32_t n, int32_t D, int32_t dn, int32_t dv, const float* logit_scale, float eps,
+                                     int32_t use_noun, int32_t use_verb, float* loss, float* sim, float* d_text,
+                                     float* d_video, float* d_logit_scale, float* work, void* stream) {
+  if (!logit_scale) return EGV_ERR_ARG;
+  if ((d_text || d_video) && !d_logit_scale) return EGV_ERR_ARG;
+  return egonce_head(text, video, noun, verb, n, D, dn, dv, 0.f, logit_scale, eps, use_noun, use_verb, loss, sim, d_text,
+                     d_video, (d_text || d_video) ? d_logit_scale : nullptr, work, stream);
 }
 
 // API-compatible pieces -------------------------------------------------------------------------------
@@ -368,30 +418,49 @@ extern "C" int egv_sim_matrix_bwd(const float* g, const float* an, const float* 
   return EGV_OK;
 }
 
-extern "C" int egv_egonce_from_sim(const float* x, const float* sim_v, const float* sim_n, int32_t n,
-                                   float temperature, int32_t use_noun, int32_t use_verb, float* loss, float* dx,
-                                   float* work /* n*n + 6n floats */, void* stream) {
+static int egonce_from_sim(const float* x, const float* sim_v, const float* sim_n, int32_t n, float inv_tau,
+                           const float* logit_scale, int32_t use_noun, int32_t use_verb, float* loss, float* dx,
+                           float* d_logit_scale, float* work /* n*n + 6n floats, + n with d_logit_scale */, void* stream) {
   if (!x || !loss || !work || n <= 0 || n > 4096) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* mask = work;
   float* rstat = mask + (long)n * n;
   float* cstat = rstat + 3 * n;
-  const float inv_tau = 1.0f / temperature;
+  float* ls_part = cstat + 3 * n;
   const long nn = (long)n * n;
   EGV_LAUNCH(egonce_mask_from_sim_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, sim_v, sim_n, n,
                      use_noun, use_verb, mask);
   EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(egonce_rowstat_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, rstat);
+  EGV_LAUNCH(egonce_rowstat_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, logit_scale, rstat);
   EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(egonce_cols_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, cstat);
+  EGV_LAUNCH(egonce_cols_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, logit_scale, cstat);
   EGV_CHECK_LAUNCH();
   EGV_LAUNCH(egonce_loss_kernel, dim3(1), dim3(256), 0, s, rstat, cstat, n, loss);
   EGV_CHECK_LAUNCH();
   if (dx) {
-    EGV_LAUNCH(egonce_grad_kernel, dim3(n), dim3(256), 0, s, x, mask, rstat, cstat, n, inv_tau, dx);
+    EGV_LAUNCH(egonce_grad_kernel, dim3(n), dim3(256), 0, s, x, mask, rstat, cstat, n, inv_tau, logit_scale, dx,
+               d_logit_scale ? ls_part : nullptr);
     EGV_CHECK_LAUNCH();
+    if (d_logit_scale) {
+      EGV_LAUNCH(egonce_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
+      EGV_CHECK_LAUNCH();
+    }
   }
   return EGV_OK;
+}
+
+extern "C" int egv_egonce_from_sim(const float* x, const float* sim_v, const float* sim_n, int32_t n,
+                                   float temperature, int32_t use_noun, int32_t use_verb, float* loss, float* dx,
+                                   float* work /* n*n + 6n floats */, void* stream) {
+  return egonce_from_sim(x, sim_v, sim_n, n, 1.0f / temperature, nullptr, use_noun, use_verb, loss, dx, nullptr, work, stream);
+}
+
+extern "C" int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const float* sim_n, int32_t n,
+                                      const float* logit_scale, int32_t use_noun, int32_t use_verb, float* loss, float* dx,
+                                      float* d_logit_scale, float* work /* n*n + 7n floats */, void* stream) {
+  if (!logit_scale || (dx && !d_logit_scale)) return EGV_ERR_ARG;
+  return egonce_from_sim(x, sim_v, sim_n, n, 0.f, logit_scale, use_noun, use_verb, loss, dx, dx ? d_logit_scale : nullptr, work,
+                         stream);
 }
 
 // ---- max-margin ranking losses (model/loss.py:55-133; the EPIC-MIR / Charades fine-tuning heads on the same similarity

@@ -22,6 +22,11 @@
 //           swapped; raw partials per column range go to the workspace.
 //   finish  one workgroup per row: sums the partials in a fixed order and applies the backward of the normalisation
 //           (egonce.hip:281-282).
+//   scale   learnable temperature only (egv_egonce_long_fwd_bwd_ls: 1 / tau = exp(s) read from the device by every kernel above):
+//           dL/ds = sum_ij G_ij X_ij.  In the grad walk with roles (tn, vn) the X^T fragment and G_IJ sit in the same registers, so
+//           each lane accumulates G X (masked exactly like G), the workgroup reduces and stores ONE partial per (row tile, column
+//           range); one workgroup adds the partials in a fixed order in double.  The swapped walk would give the same number and
+//           is not used.  The loss kernel runs BEFORE the walk, so this sum is a launch of its own, of the same shape.
 //
 // k order.  The 16x16x4 MFMA takes k = lane >> 4 from each lane.  A lane reads FOUR consecutive floats (one 16-byte LDS read)
 // and feeds element t to MFMA t, so MFMA t of chunk c sums k = 16 c + 4 (lane >> 4) + t; both operands use the same map, which
@@ -47,7 +52,7 @@ __device__ __forceinline__ float egl_block_sum(float v, float* sh) {  // 256 thr
 
 struct EglLayout {
   int np, Dp, wn, W, ntiles, tps_s, ns_s, tps_g, ns_g;
-  long tn, vn, words, norms, flags, spart, stat, gpart, total;   // offsets in floats
+  long tn, vn, words, norms, flags, spart, stat, gpart, lpart, total;   // offsets in floats
 };
 
 inline void egl_split(int ntiles, int target, int& tps, int& ns) {
@@ -76,6 +81,7 @@ inline EglLayout egl_layout(int n, int D, int dn, int dv) {
   L.spart = o;  o += 2L * L.ns_s * 3 * np;
   L.stat = o;   o += 6 * np;
   L.gpart = o;  o += (long)L.ns_g * np * L.Dp;
+  L.lpart = o;  o += (long)L.ns_g * L.ntiles;          // dL/d(logit scale): one partial per workgroup of the grad walk
   L.total = o;
   return L;
 }
@@ -224,12 +230,14 @@ __device__ __forceinline__ void egl_xt(const float* bt, const f32x4_t (&a)[DP / 
 template <int DP>
 __global__ __launch_bounds__(256, 2) void egl_stats_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                            const uint32_t* __restrict__ words, int n, int np, int W, int wn,
-                                                           int mode, float inv_tau, int tps,
+                                                           int mode, float inv_tau,
+                                                           const float* __restrict__ logit_scale, int tps,
                                                            float* __restrict__ part /* [ranges][3][np] */) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int LD = DP + 4;
   float* bt = (float*)smem;
   uint32_t* mb = (uint32_t*)(bt + EGL_TILE * LD);
+  inv_tau = egv_inv_tau(inv_tau, logit_scale);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
@@ -294,9 +302,11 @@ __global__ __launch_bounds__(256, 2) void egl_stats_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------ loss
 __global__ __launch_bounds__(1024) void egl_loss_kernel(const float* __restrict__ spart /* [2][ranges][3][np] */, int ns, int n,
-                                                        int np, float inv_tau, const float* __restrict__ flags,
+                                                        int np, float inv_tau, const float* __restrict__ logit_scale,
+                                                        const float* __restrict__ flags,
                                                         float* __restrict__ stat /* [2][3][np] */, float* __restrict__ loss) {
   __shared__ double red[1024];
+  inv_tau = egv_inv_tau(inv_tau, logit_scale);
   double s = 0.0;
   int bad = 0;
   for (int i = threadIdx.x; i < n; i += 1024) {
@@ -335,13 +345,21 @@ __global__ __launch_bounds__(256, 2) void egl_grad_kernel(const float* __restric
                                                           const uint32_t* __restrict__ words,
                                                           const float* __restrict__ own /* [3][np]: statistics of A's rows */,
                                                           const float* __restrict__ oth /* [3][np]: of B's rows */, int n,
-                                                          int np, int W, int wn, int mode, float inv_tau, float sc, int tps,
-                                                          float* __restrict__ gpart /* [ranges][np][DP] */) {
+                                                          int np, int W, int wn, int mode, float inv_tau, float sc,
+                                                          const float* __restrict__ logit_scale, int tps,
+                                                          float* __restrict__ gpart /* [ranges][np][DP] */,
+                                                          float* __restrict__ lpart /* [ranges][tiles] or NULL */) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ float sh[4];
   constexpr int LD = DP + 4;
   float* bt = (float*)smem;
   uint32_t* mb = (uint32_t*)(bt + EGL_TILE * LD);
   float* cs = (float*)(mb + EGL_TILE * 4);            // [3][64]: max, 1 / Z, 1 / P of the tile's B rows
+  if (logit_scale) {                                  // uniform
+    inv_tau = expf(logit_scale[0]);
+    sc = -inv_tau / (float)n;
+  }
+  float gx = 0.f;                                     // this lane's share of sum G X
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, g = lane >> 4;
@@ -393,7 +411,9 @@ __global__ __launch_bounds__(256, 2) void egl_grad_kernel(const float* __restric
         const float ec = __expf((xv - cm4[r]) * inv_tau);     // under the maximum of B's row
         const float mm = ((mbits[jf] >> (4 * g + r)) & 1u) ? 1.f : 0.f;
         const float gv = sc * (eo * (mm * ipo - izo) + ec * (mm * ip4[r] - iz4[r]));
-        x[jf][r] = (live && j0 + jf * 16 + 4 * g + r < n) ? gv : 0.f;
+        const float gm = (live && j0 + jf * 16 + 4 * g + r < n) ? gv : 0.f;
+        gx += gm * xv;
+        x[jf][r] = gm;
       }
     }
     // dA[i][d] += sum_j G[i][j] B[j][d]: x[jf][r] is the A operand of k-step (jf, r) as it stands (k = j = 16 jf + 4 g + r)
@@ -415,6 +435,18 @@ __global__ __launch_bounds__(256, 2) void egl_grad_kernel(const float* __restric
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
       *(f32x4_t*)(out + (long)rr * DP + 64 * c) = (f32x4_t){acc[c][0][rr], acc[c][1][rr], acc[c][2][rr], acc[c][3][rr]};
+  if (lpart) {                                        // uniform over the workgroup
+    gx = egl_block_sum(gx, sh);
+    if (threadIdx.x == 0) lpart[(long)blockIdx.y * ntiles + blockIdx.x] = gx;
+  }
+}
+
+// dL/d(logit scale): the grad walk's partials, one workgroup, double, fixed order
+__global__ __launch_bounds__(256) void egl_scale_grad_kernel(const float* __restrict__ lpart, int count,
+                                                             float* __restrict__ d_logit_scale) {
+  __shared__ double red[256];
+  const double s = egv_sum_partials_256(lpart, count, red);
+  if (threadIdx.x == 0) d_logit_scale[0] = (float)s;
 }
 
 // sum of the column-range partials in a fixed order + the backward of the row normalisation (egonce.hip:281-282)
@@ -435,23 +467,25 @@ __global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict
 
 template <int DP>
 int egl_launch_stats(const EglLayout& L, const float* A, const float* B, const uint32_t* words, int n, int mode, float inv_tau,
-                     float* part, hipStream_t s) {
+                     const float* logit_scale, float* part, hipStream_t s) {
   constexpr int lds = EGL_TILE * (DP + 4) * 4 + EGL_TILE * 4 * 4;
   auto k = egl_stats_kernel<DP>;
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  EGV_LAUNCH(k, dim3(L.ntiles, L.ns_s), dim3(256), lds, s, A, B, words, n, L.np, L.W, L.wn, mode, inv_tau, L.tps_s, part);
+  EGV_LAUNCH(k, dim3(L.ntiles, L.ns_s), dim3(256), lds, s, A, B, words, n, L.np, L.W, L.wn, mode, inv_tau, logit_scale, L.tps_s,
+             part);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }
 
 template <int DP>
 int egl_launch_grad(const EglLayout& L, const float* A, const float* B, const uint32_t* words, const float* own,
-                    const float* oth, int n, int mode, float inv_tau, float* gpart, hipStream_t s) {
+                    const float* oth, int n, int mode, float inv_tau, const float* logit_scale, float* gpart, float* lpart,
+                    hipStream_t s) {
   constexpr int lds = EGL_TILE * (DP + 4) * 4 + EGL_TILE * 4 * 4 + 3 * EGL_TILE * 4;
   auto k = egl_grad_kernel<DP>;
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   EGV_LAUNCH(k, dim3(L.ntiles, L.ns_g), dim3(256), lds, s, A, B, words, own, oth, n, L.np, L.W, L.wn, mode, inv_tau,
-             -inv_tau / (float)n, L.tps_g, gpart);
+             -inv_tau / (float)n, logit_scale, L.tps_g, gpart, lpart);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }
@@ -469,14 +503,14 @@ extern "C" int64_t egv_egonce_long_work_floats(int32_t n, int32_t D, int32_t dn,
   return egl_layout(n, D, dn, dv).total;
 }
 
-extern "C" int egv_egonce_long_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb, int32_t n,
-                                       int32_t D, int32_t dn, int32_t dv, float temperature, float eps, int32_t use_noun,
-                                       int32_t use_verb, float* loss, float* d_text, float* d_video, float* work,
-                                       void* stream) {
+// the long head; logit_scale != NULL: 1 / tau = exp(*logit_scale) on the device (inv_tau unused) and, with d_text, *d_logit_scale
+static int egl_head(const float* text, const float* video, const float* noun, const float* verb, int32_t n, int32_t D, int32_t dn,
+                    int32_t dv, float inv_tau, const float* logit_scale, float eps, int32_t use_noun, int32_t use_verb,
+                    float* loss, float* d_text, float* d_video, float* d_logit_scale, float* work, void* stream) {
   if (!text || !video || !loss || !work) return EGV_ERR_ARG;
   if ((noun != nullptr) != (verb != nullptr)) return EGV_ERR_ARG;
   if (!noun) dn = dv = 0;
-  if (!egl_args_ok(n, D, dn, dv) || !(temperature > 0.f)) return EGV_ERR_ARG;
+  if (!egl_args_ok(n, D, dn, dv)) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const EglLayout L = egl_layout(n, D, dn, dv);
   float* tn = work + L.tn;
@@ -487,31 +521,57 @@ extern "C" int egv_egonce_long_fwd_bwd(const float* text, const float* video, co
   float* spart = work + L.spart;
   float* stat = work + L.stat;
   float* gpart = work + L.gpart;
+  float* lpart = d_logit_scale ? work + L.lpart : nullptr;
   // the mode of egonce_rows_kernel: noun and verb, noun only, else verb (the reference's else-branch)
   const int mode = !noun ? 0 : (use_noun && use_verb) ? 1 : use_noun ? 2 : 3;
-  const float inv_tau = 1.0f / temperature;
   const long np = L.np;
 
   EGV_LAUNCH(egl_prep_kernel, dim3(L.np), dim3(256), 0, s, text, video, noun, verb, n, L.np, D, L.Dp, dn, dv, L.wn, L.W, eps, tn,
              vn, words, norms, flags);
   EGV_CHECK_LAUNCH();
-  int rc = EGL_BY_DP(egl_launch_stats, L, tn, vn, words, n, mode, inv_tau, spart, s);
+  int rc = EGL_BY_DP(egl_launch_stats, L, tn, vn, words, n, mode, inv_tau, logit_scale, spart, s);
   if (rc != EGV_OK) return rc;
-  rc = EGL_BY_DP(egl_launch_stats, L, vn, tn, words, n, mode, inv_tau, spart + (long)L.ns_s * 3 * np, s);
+  rc = EGL_BY_DP(egl_launch_stats, L, vn, tn, words, n, mode, inv_tau, logit_scale,
+                  spart + (long)L.ns_s * 3 * np, s);
   if (rc != EGV_OK) return rc;
-  EGV_LAUNCH(egl_loss_kernel, dim3(1), dim3(1024), 0, s, spart, L.ns_s, n, L.np, inv_tau, flags, stat, loss);
+  EGV_LAUNCH(egl_loss_kernel, dim3(1), dim3(1024), 0, s, spart, L.ns_s, n, L.np, inv_tau, logit_scale, flags, stat, loss);
   EGV_CHECK_LAUNCH();
   if (d_text) {
-    rc = EGL_BY_DP(egl_launch_grad, L, tn, vn, words, stat, stat + 3 * np, n, mode, inv_tau, gpart, s);
+    rc = EGL_BY_DP(egl_launch_grad, L, tn, vn, words, stat, stat + 3 * np, n, mode, inv_tau, logit_scale, gpart, lpart, s);
     if (rc != EGV_OK) return rc;
+    if (lpart) {
+      EGV_LAUNCH(egl_scale_grad_kernel, dim3(1), dim3(256), 0, s, lpart, L.ns_g * L.ntiles, d_logit_scale);
+      EGV_CHECK_LAUNCH();
+    }
     EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns_g, tn, norms, L.np, D, L.Dp, eps, d_text);
     EGV_CHECK_LAUNCH();
   }
   if (d_video) {
-    rc = EGL_BY_DP(egl_launch_grad, L, vn, tn, words, stat + 3 * np, stat, n, mode, inv_tau, gpart, s);
+    rc = EGL_BY_DP(egl_launch_grad, L, vn, tn, words, stat + 3 * np, stat, n, mode, inv_tau, logit_scale, gpart,
+                   nullptr, s);
     if (rc != EGV_OK) return rc;
     EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns_g, vn, norms + np, L.np, D, L.Dp, eps, d_video);
     EGV_CHECK_LAUNCH();
   }
   return EGV_OK;
+}
+
+extern "C" int egv_egonce_long_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb, int32_t n,
+                                       int32_t D, int32_t dn, int32_t dv, float temperature, float eps, int32_t use_noun,
+                                       int32_t use_verb, float* loss, float* d_text, float* d_video, float* work,
+                                       void* stream) {
+  if (!(temperature > 0.f)) return EGV_ERR_ARG;
+  return egl_head(text, video, noun, verb, n, D, dn, dv, 1.0f / temperature, nullptr, eps, use_noun, use_verb, loss, d_text,
+                  d_video, nullptr, work, stream);
+}
+
+extern "C" int egv_egonce_long_fwd_bwd_ls(const float* text, const float* video, const float* noun, const float* verb, int32_t n,
+                                          int32_t D, int32_t dn, int32_t dv, const float* logit_scale, float eps,
+                                          int32_t use_noun, int32_t use_verb, float* loss, float* d_text, float* d_video,
+                                          float* d_logit_scale, float* work, void* stream) {
+  if (!logit_scale) return EGV_ERR_ARG;
+  // the scale's gradient comes out of the (tn, vn) walk: it needs d_text
+  if ((d_text || d_video) && !(d_text && d_logit_scale)) return EGV_ERR_ARG;
+  return egl_head(text, video, noun, verb, n, D, dn, dv, 0.f, logit_scale, eps, use_noun, use_verb, loss, d_text, d_video,
+                  d_text ? d_logit_scale : nullptr, work, stream);
 }

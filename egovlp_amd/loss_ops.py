@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the contrastive-head kernels (include/egovlp_hip.h: egv_sim_matrix_*,
-egv_egonce_from_sim, egv_egonce_fwd_bwd, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
+egv_egonce_from_sim, egv_egonce_fwd_bwd and their *_ls variants, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
 the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
 import torch
 
@@ -34,18 +34,27 @@ def sim_bwd(data, g):
     return da, db
 
 
-def egonce_from_sim(x, sim_v, sim_n, temperature, use_noun, use_verb, want_grad=True):
+def egonce_from_sim(x, sim_v, sim_n, temperature, use_noun, use_verb, want_grad=True, logit_scale=None):
+    """EgoNCE / NormSoftmaxLoss on a given similarity matrix -> (loss[1], dx).  `logit_scale` (a device tensor holding
+    s = log(1 / tau); `temperature` is then unused) -> (loss[1], dx, d_logit_scale [1]) -- egv_egonce_from_sim_ls."""
     ops._need_cuda(x)
     x = x.contiguous()
     n = x.shape[0]
     if x.shape[1] != n:
         raise ValueError("EgoNCE / NormSoftmaxLoss need a square similarity matrix")
     dev = x.device
-    work = torch.empty(n * n + 6 * n, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dx = torch.empty_like(x) if want_grad else None
     sv = sim_v.contiguous() if sim_v is not None else None
     sn = sim_n.contiguous() if sim_n is not None else None
+    if logit_scale is not None:
+        ls = ops._logit_scale_arg(logit_scale, x)
+        work = torch.empty(n * n + 7 * n, dtype=torch.float32, device=dev)
+        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
+        check(_lib.lib().egv_egonce_from_sim_ls(_p(x), _p(sv), _p(sn), n, _p(ls), int(use_noun), int(use_verb), _p(loss), _p(dx),
+                                                _p(dls), _p(work), ops._stream()), "egv_egonce_from_sim_ls")
+        return loss, dx, dls
+    work = torch.empty(n * n + 6 * n, dtype=torch.float32, device=dev)
     check(_lib.lib().egv_egonce_from_sim(_p(x), _p(sv), _p(sn), n, float(temperature), int(use_noun), int(use_verb),
                                          _p(loss), _p(dx), _p(work), ops._stream()), "egv_egonce_from_sim")
     return loss, dx

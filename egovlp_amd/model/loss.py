@@ -6,6 +6,8 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip):
   * the fused hot path  `loss.fused(text, video, noun, verb)`: ONE call computes the three similarity
     matrices, the mask, the loss and the gradients w.r.t. both embeddings (egv_egonce_fwd_bwd; past 1 024 rows the tiled
     egv_egonce_long_fwd_bwd of csrc/egonce_long.hip, which forms no n x n matrix).
+Both losses take `learnable_temperature=True` (not in the reference): the temperature becomes CLIP's learnable logit scale, read on the
+device by the *_ls variants of the same entry points, which also return its gradient (_TemperatureMixin below).
 MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EPIC-MIR / Charades fine-tuning heads over the
 same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
 of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR
@@ -13,6 +15,8 @@ classification fine-tunes on the [B, classes] scores of FrozenInTime(video_only=
 egv_cross_entropy_fwd_bwd; its `fused(feats, weight, bias, target[, state])` is the whole head of those steps on ONE autograd
 node: the narrow projection (egv_cls_head_fwd), one packed collective, loss and backward (egv_cls_head_loss_bwd).
 """
+import math
+
 import torch
 from torch import nn
 
@@ -48,31 +52,116 @@ class _FusedHeadFn(torch.autograd.Function):
         return dt * g, dv * g, None, None, None, None, None
 
 
-class NormSoftmaxLoss(nn.Module):
-    def __init__(self, temperature=0.05):
-        super().__init__()
+class _LossFromSimScaleFn(torch.autograd.Function):
+    """_LossFromSimFn with the temperature read from the device parameter `logit_scale`; also returns dL/d(logit_scale)."""
+
+    @staticmethod
+    def forward(ctx, x, mask_v, mask_n, logit_scale, use_noun, use_verb):
+        loss, dx, dls = loss_ops.egonce_from_sim(x, mask_v, mask_n, None, use_noun, use_verb, want_grad=True, logit_scale=logit_scale)
+        ctx.save_for_backward(dx, _over_world(dls))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dx, dls = ctx.saved_tensors
+        return dx * g, None, None, dls * g, None, None
+
+
+class _FusedHeadScaleFn(torch.autograd.Function):
+    """_FusedHeadFn with the temperature read from the device parameter `logit_scale`; also returns dL/d(logit_scale)."""
+
+    @staticmethod
+    def forward(ctx, text, video, noun, verb, logit_scale, use_noun, use_verb):
+        loss, _, dt, dv, dls = ops.egonce_fwd_bwd(text.contiguous(), video.contiguous(),
+                                                  None if noun is None else noun.contiguous().float(),
+                                                  None if verb is None else verb.contiguous().float(),
+                                                  None, use_noun=use_noun, use_verb=use_verb, logit_scale=logit_scale)
+        ctx.save_for_backward(dt, dv, _over_world(dls))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dt, dv, dls = ctx.saved_tensors
+        return dt * g, dv * g, None, None, dls * g, None, None
+
+
+def _over_world(dls):
+    """Every rank runs the head on the same gathered batch with deterministic kernels, so dL/ds is bit-identical everywhere and
+    is NOT exchanged (it is no part of Bf16GradSync).  The model's gradients leave the exchange as (1 / W) grad L_global
+    (egovlp_amd/gather.py); the scale's is stored with the same factor, so that the optimizer -- and its global-norm clipping -- sees
+    one consistent gradient vector."""
+    W = gather._world()
+    return dls if W == 1 else dls / W
+
+
+class _TemperatureMixin:
+    """temperature = 0.05 of the reference (model/loss.py:8-11,28-32), fixed -- or, `learnable_temperature=True`, CLIP's learnable
+    logit scale: `self.logit_scale` = s = log(1 / tau), one fp32 parameter initialised to log(1 / temperature); the head kernels
+    read it on the device and return dL/ds.  Off (the default) the module has no parameter and makes the calls it always made."""
+
+    def _init_temperature(self, temperature, learnable_temperature, max_logit_scale):
         self.temperature = temperature
+        self.learnable_temperature = bool(learnable_temperature)
+        self.max_logit_scale = float(max_logit_scale)
+        # the clamp runs in fp32: its upper bound is the largest fp32 value <= max_logit_scale (fp32(ln 100) itself rounds UP)
+        hi = torch.tensor(self.max_logit_scale, dtype=torch.float32)
+        if float(hi) > self.max_logit_scale:
+            hi = torch.nextafter(hi, torch.tensor(float("-inf")))
+        self._clamp_hi = float(hi)
+        if self.learnable_temperature:
+            if not temperature > 0:
+                raise ValueError("learnable_temperature: the initial temperature must be positive")
+            self.logit_scale = nn.Parameter(torch.full((1,), math.log(1.0 / temperature), dtype=torch.float32))
+
+    def current_temperature(self):
+        """tau = exp(-s) read back from the device (synchronises: logs and tests); the fixed value when not learnable."""
+        if not self.learnable_temperature:
+            return float(self.temperature)
+        return math.exp(-float(self.logit_scale.detach().float().cpu()))
+
+    @torch.no_grad()
+    def clamp_logit_scale_(self):
+        """s <- clamp(s, 0, max_logit_scale) in place (CLIP: max ln 100): one tiny device op, no synchronisation.  The steps call it
+        after optimizer.step."""
+        if self.learnable_temperature:
+            self.logit_scale.clamp_(0.0, self._clamp_hi)
+        return self
+
+
+class NormSoftmaxLoss(_TemperatureMixin, nn.Module):
+    def __init__(self, temperature=0.05, learnable_temperature=False, max_logit_scale=math.log(100)):
+        super().__init__()
+        self._init_temperature(temperature, learnable_temperature, max_logit_scale)
 
     def forward(self, x):
         "x: similarity matrix N x N in [-1, 1] (model/loss.py:13-25)"
+        if self.learnable_temperature:
+            return _LossFromSimScaleFn.apply(x, None, None, self.logit_scale, True, True)
         return _LossFromSimFn.apply(x, None, None, self.temperature, True, True)
 
     def fused(self, text_embeds, video_embeds):
+        if self.learnable_temperature:
+            return _FusedHeadScaleFn.apply(text_embeds, video_embeds, None, None, self.logit_scale, True, True)
         return _FusedHeadFn.apply(text_embeds, video_embeds, None, None, self.temperature, True, True)
 
 
-class EgoNCE(nn.Module):
-    def __init__(self, temperature=0.05, noun=True, verb=True):
+class EgoNCE(_TemperatureMixin, nn.Module):
+    def __init__(self, temperature=0.05, noun=True, verb=True, learnable_temperature=False, max_logit_scale=math.log(100)):
         super().__init__()
         self.noun = noun
         self.verb = verb
-        self.temperature = temperature
+        self._init_temperature(temperature, learnable_temperature, max_logit_scale)
 
     def forward(self, x, mask_v, mask_n):
         # noun=False, verb=False falls into the reference's else-branch (mask_v), model/loss.py:40-41
+        if self.learnable_temperature:
+            return _LossFromSimScaleFn.apply(x, mask_v, mask_n, self.logit_scale, self.noun, self.verb or not self.noun)
         return _LossFromSimFn.apply(x, mask_v, mask_n, self.temperature, self.noun, self.verb or not self.noun)
 
     def fused(self, text_embeds, video_embeds, noun_vec, verb_vec):
+        if self.learnable_temperature:
+            return _FusedHeadScaleFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.logit_scale, self.noun,
+                                           self.verb or not self.noun)
         return _FusedHeadFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.temperature, self.noun,
                                   self.verb or not self.noun)
 

@@ -1262,19 +1262,29 @@ def embed_bwd(ids, d_e, word_shape, pos_shape, pad_id=-1):
 
 
 # ------------------------------------------------------------------------------------------- loss / optim
+def _logit_scale_arg(logit_scale, like):
+    """The learnable heads read s = log(1 / tau) from the device: one fp32 on the inputs' device."""
+    ls = logit_scale.detach()
+    if ls.dtype != torch.float32 or ls.numel() != 1 or ls.device != like.device:
+        raise ValueError("logit_scale must be one fp32 value on the device of the embeddings")
+    return ls.contiguous()
+
+
 def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
-                   want_sim=False):
+                   want_sim=False, logit_scale=None):
     """The contrastive head in one call -> (loss[1], sim or None, d_text, d_video).  Up to EGONCE_SHORT_MAX rows: the latency-bound
-    kernels of csrc/egonce.hip; beyond: egonce_long_fwd_bwd (no n x n matrix exists there, so `want_sim` is refused)."""
+    kernels of csrc/egonce.hip; beyond: egonce_long_fwd_bwd (no n x n matrix exists there, so `want_sim` is refused).
+    `logit_scale` (a device tensor holding s = log(1 / tau); `temperature` is then unused): the kernels form 1 / tau = exp(s) on the
+    device and the call returns a fifth value, d_logit_scale [1] = dL/ds (None without want_grads) -- egv_egonce_fwd_bwd_ls."""
     _need_cuda(text, video, noun, verb)
     n, D = text.shape
     if n > EGONCE_SHORT_MAX:
         if want_sim:
             raise ValueError("egonce_fwd_bwd: want_sim needs n <= %d (the long head materialises no n x n matrix), got n = %d"
                              % (EGONCE_SHORT_MAX, n))
-        loss, dt, dvv = egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=eps, use_noun=use_noun, use_verb=use_verb,
-                                            want_grads=want_grads)
-        return loss, None, dt, dvv
+        out = egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=eps, use_noun=use_noun, use_verb=use_verb,
+                                  want_grads=want_grads, logit_scale=logit_scale)
+        return (out[0], None) + tuple(out[1:])
     dev = text.device
     dn = noun.shape[1] if noun is not None else 0
     dv = verb.shape[1] if verb is not None else 0
@@ -1284,6 +1294,13 @@ def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True
     sim = torch.empty((n, n), dtype=torch.float32, device=dev) if want_sim else None
     dt = torch.empty_like(text) if want_grads else None
     dvv = torch.empty_like(video) if want_grads else None
+    if logit_scale is not None:
+        ls = _logit_scale_arg(logit_scale, text)
+        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads else None
+        check(_lib.lib().egv_egonce_fwd_bwd_ls(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), float(eps),
+                                               int(use_noun), int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv), _p(dls),
+                                               _p(work), _stream(text)), "egv_egonce_fwd_bwd_ls")
+        return loss, sim, dt, dvv, dls
     check(_lib.lib().egv_egonce_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, float(temperature),
                                         float(eps), int(use_noun), int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv),
                                         _p(work), _stream(text)), "egv_egonce_fwd_bwd")
@@ -1294,9 +1311,11 @@ EGONCE_SHORT_MAX = 1024      # rows of egv_egonce_fwd_bwd; egonce_fwd_bwd switch
 EGONCE_LONG_MAX = 65536      # rows of egv_egonce_long_fwd_bwd
 
 
-def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True):
+def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                        logit_scale=None):
     """egv_egonce_long_fwd_bwd for ANY n in [1, 65536] -> (loss[1], d_text, d_video): the tiled fp32-MFMA head with a workspace
-    linear in n.  noun / verb: non-negative multi-hots (only entry > 0 is used); a negative or NaN entry makes the loss NaN."""
+    linear in n.  noun / verb: non-negative multi-hots (only entry > 0 is used); a negative or NaN entry makes the loss NaN.
+    `logit_scale`: as in egonce_fwd_bwd -> (loss[1], d_text, d_video, d_logit_scale [1]) -- egv_egonce_long_fwd_bwd_ls."""
     _need_cuda(text, video, noun, verb)
     n, D = text.shape
     dev = text.device
@@ -1307,6 +1326,13 @@ def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dt = torch.empty_like(text) if want_grads else None
     dvv = torch.empty_like(video) if want_grads else None
+    if logit_scale is not None:
+        ls = _logit_scale_arg(logit_scale, text)
+        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads else None
+        check(_lib.lib().egv_egonce_long_fwd_bwd_ls(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), float(eps),
+                                                    int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(dls), _p(work),
+                                                    _stream(text)), "egv_egonce_long_fwd_bwd_ls")
+        return loss, dt, dvv, dls
     check(_lib.lib().egv_egonce_long_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, float(temperature),
                                              float(eps), int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(work),
                                              _stream(text)), "egv_egonce_long_fwd_bwd")

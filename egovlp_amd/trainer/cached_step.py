@@ -24,7 +24,7 @@ import torch
 
 from .. import ops
 from ..gather import AllGatherFused
-from .common import egoclip_head_loss, step_prologue
+from .common import clamp_loss_scale, egoclip_head_loss, step_prologue
 
 
 def _rows(data, lo, hi):
@@ -141,4 +141,5 @@ def egoclip_step_cached(model, loss_fn, optimizer, data, chunk, world_size=1, ra
         optimizer.step()
     else:
         optimizer.step(scaler=scaler)
+    clamp_loss_scale(loss_fn)       # a learnable temperature: its gradient came from pass 2, the head over the WHOLE batch
     return loss.detach()

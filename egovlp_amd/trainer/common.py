@@ -37,6 +37,30 @@ def step_epilogue(loss, ec, optimizer, grad_sync, scaler):
     return loss.detach()
 
 
+def clamp_loss_scale(loss_fn):
+    """After optimizer.step of the EgoClip steps: a loss with a learnable temperature clamps its logit scale (one tiny device op, no
+    synchronisation); any other loss: nothing is called."""
+    if getattr(loss_fn, 'learnable_temperature', False):
+        loss_fn.clamp_logit_scale_()
+
+
+def register_loss_parameters(optimizer, loss_fn, lr=None):
+    """The reference builds its optimizer from `model.parameters()` only (run/train_egoclip.py:72-73); a loss with parameters of its
+    own (EgoNCE / NormSoftmaxLoss with `learnable_temperature=True`: the logit scale) gets ONE more parameter group here:
+    weight_decay 0, `lr` defaulting to the first group's.  Parameters the optimizer already holds are left where they are (calling
+    this twice adds nothing).  -> the new group, or None when there was nothing to add."""
+    if not hasattr(loss_fn, 'parameters'):
+        return None
+    held = {id(p) for g in optimizer.param_groups for p in g['params']}
+    params = [p for p in loss_fn.parameters() if p.requires_grad and id(p) not in held]
+    if not params:
+        return None
+    own_lr = lr is not None
+    optimizer.add_param_group({'params': params, 'weight_decay': 0.0, 'lr': float(lr) if own_lr else optimizer.param_groups[0]['lr'],
+                               'loss_parameters': True, 'base_lr': float(lr) if own_lr else None})
+    return optimizer.param_groups[-1]
+
+
 def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fused_head=True):
     """Similarity + loss of the EgoClip step on the (gathered) global batch, trainer/trainer_egoclip.py:130-137 -- shared by
     `egoclip_step` and `egoclip_step_cached`."""
@@ -155,10 +179,14 @@ class TrainerBase(Multi_BaseTrainer_dist):
 
     def _adjust_learning_rate(self, optimizer, epoch, args):
         lr = args.learning_rate1                                            # :75-80
+        decay = 1.
         for milestone in args.schedule:
             lr *= 0.1 if epoch >= milestone else 1.
+            decay *= 0.1 if epoch >= milestone else 1.
         for param_group in optimizer.param_groups:
-            param_group['lr'] = lr
+            # the loss's group keeps a learning rate of its own (args.temperature_lr) under the same schedule
+            own = param_group.get('base_lr') if param_group.get('loss_parameters') else None
+            param_group['lr'] = lr if own is None else own * decay
 
     def _step(self, data):
         """The optimisation step of one device batch -> its (device) loss."""
@@ -194,6 +222,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 total = int(self.data_loader[dl_idx].n_samples / self.n_gpu) if hasattr(self.data_loader[dl_idx], 'n_samples') else 0
                 current = batch_idx * self.data_loader[dl_idx].batch_size
                 self.writer.add_scalar(f'Loss_training/loss_{dl_idx}', float(loss), (epoch - 1) * total + current)   # :143-148
+                if getattr(getattr(self, 'loss', None), 'learnable_temperature', False):   # float(loss) has just synchronised: the read-back is free
+                    self.writer.add_scalar(f'Loss_training/temperature_{dl_idx}', self.loss.current_temperature(), (epoch - 1) * total + current)
                 # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has
                 # just synchronised anyway (off: nothing is computed, nothing is read)
                 if getattr(self.optimizer, 'max_grad_norm', None) is not None:

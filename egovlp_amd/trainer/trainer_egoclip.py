@@ -14,7 +14,8 @@ from ..gather import AllGatherFused, _gather_rows, _world
 from ..model.model import sim_matrix
 from .common import _prefetched  # noqa: F401  (re-exported: the feed of the epoch loop, timed on its own by bench.py)
 from .cached_step import egoclip_step_cached  # noqa: F401  (re-exported: the same step over a batch larger than memory)
-from .common import TrainerBase, egoclip_head_loss, step_epilogue, step_prologue
+from .common import TrainerBase, clamp_loss_scale, egoclip_head_loss, step_epilogue, step_prologue
+from .common import register_loss_parameters  # noqa: F401  (re-exported: the optimizer group of a loss with parameters)
 
 
 def _pad_tokens(text, multiple):
@@ -32,14 +33,18 @@ def egoclip_step(model, loss_fn, optimizer, data, world_size=1, rank=0, fused_he
     `grad_sync` (egovlp_amd.dist.Bf16GradSync, world size > 1) averages the gradients over the ranks -- its all-reduces
     are launched by grad-ready hooks during backward; `finish()` waits for them before the optimizer reads p.grad.
     `scaler` (egovlp_amd.optim.LossScaler; default when the model's backward precision is 'f16': exec_ctx.loss_scaler()): the loss is multiplied by the device-side
-    loss scale before backward() and the optimizer un-scales, or skips the step after an overflow -- no host synchronisation."""
+    loss scale before backward() and the optimizer un-scales, or skips the step after an overflow -- no host synchronisation.
+    A `loss_fn` with a learnable temperature (its `logit_scale` must be in the optimizer: `register_loss_parameters`) gets that
+    parameter's gradient from the head's own node, and its clamp runs after optimizer.step."""
     _, ec, scaler = step_prologue(model, optimizer, scaler)
     text_embeds, video_embeds = model(data)
     n_embeds, v_embeds = data['noun_vec'], data['verb_vec']
     video_embeds, text_embeds, n_embeds, v_embeds = AllGatherFused.apply(
         video_embeds, text_embeds, n_embeds, v_embeds, world_size, rank)
     loss = egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fused_head)   # :130-137
-    return step_epilogue(loss, ec, optimizer, grad_sync, scaler)            # :139-141
+    loss = step_epilogue(loss, ec, optimizer, grad_sync, scaler)            # :139-141
+    clamp_loss_scale(loss_fn)               # a learnable temperature: clamp the logit scale the optimizer has just moved
+    return loss
 
 
 class Multi_Trainer_dist(TrainerBase):

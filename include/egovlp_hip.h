@@ -523,6 +523,26 @@ int egv_sim_matrix_bwd(const float* g, const float* an, const float* bn, const f
 int egv_egonce_from_sim(const float* x, const float* sim_v, const float* sim_n, int32_t n, float temperature,
                         int32_t use_noun, int32_t use_verb, float* loss, float* dx,
                         float* work /* n*n + 6n floats */, void* stream);
+/* Learnable temperature: the three heads above with the logit scale s = log(1 / tau) (CLIP's logit_scale) read from the DEVICE --
+ * `logit_scale` points to one fp32, 1 / tau = expf(s) is formed by the kernels, nothing is read back -- in place of the by-value
+ * `temperature` of model/loss.py:8-11,28-32 (`x / self.temperature`, :15-16,44-45).  Same kernels, same loss and embedding
+ * gradients; next to them `d_logit_scale` (one fp32) receives
+ *   dL/ds = sum_ij G_ij x_ij,      G = dL/dx (the matrix the gradient kernels already form), x = sim_matrix(text, video),
+ * reduced without float atomics (per-row / per-workgroup partials, then one workgroup in double, fixed order): two calls give the
+ * same bits.  d_logit_scale is written when gradients are (short head: d_text or d_video; long head: d_text, whose walk carries the
+ * sum; from_sim: dx) and must be non-NULL then; with no gradient pointer the loss alone is computed.  The short head's workspace
+ * is egv_egonce_work_floats as before; the long head's egv_egonce_long_work_floats (it includes the partials: linear in n). */
+int egv_egonce_fwd_bwd_ls(const float* text, const float* video, const float* noun, const float* verb,
+                          int32_t n, int32_t D, int32_t dn, int32_t dv, const float* logit_scale, float eps,
+                          int32_t use_noun, int32_t use_verb,
+                          float* loss, float* sim, float* d_text, float* d_video, float* d_logit_scale, float* work, void* stream);
+int egv_egonce_long_fwd_bwd_ls(const float* text, const float* video, const float* noun, const float* verb,
+                               int32_t n, int32_t D, int32_t dn, int32_t dv, const float* logit_scale, float eps,
+                               int32_t use_noun, int32_t use_verb,
+                               float* loss, float* d_text, float* d_video, float* d_logit_scale, float* work, void* stream);
+int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const float* sim_n, int32_t n, const float* logit_scale,
+                           int32_t use_noun, int32_t use_verb, float* loss, float* dx, float* d_logit_scale,
+                           float* work /* n*n + 7n floats */, void* stream);
 
 /* Max-margin ranking losses of the fine-tuning heads (model/loss.py:55-133) on a square similarity matrix x [n, n]:
  *   loss = mean_{kept (i,j)} relu(w_i m - x_ii + x_ij) + relu(w_i m - x_ii + x_ji),   w = NULL: MaxMarginRankingLoss (w_i = 1),
