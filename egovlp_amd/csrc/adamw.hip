@@ -6,6 +6,7 @@
 // pure HBM traffic, 16 B read + 12 B written per parameter (+4 B when the bf16 planes are refreshed).
 #include "common.h"
 #include "egovlp_hip.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -20,9 +21,9 @@ struct AdamTable {
   bf16_t* wh[MAX_T];
   bf16_t* wl[MAX_T];
   long numel[MAX_T];
-  int blk_start[MAX_T + 1];  // first block of each tensor (prefix sum of chunk counts)
-  int count;
+  MtIndex<MAX_T> ix;
 };
+static_assert(sizeof(AdamTable) <= 4096, "the table travels in the kernel arguments");
 
 __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t, float lr, float b1, float b2, float eps, float wd,
                                                     float step_size, float grad_scale, const float* __restrict__ hyper) {
@@ -35,9 +36,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamTable t, float lr,
     step_size = hyper[1];
     grad_scale = hyper[2];
   }
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;   // <= 47 scalar compares
-  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * CHUNK;
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long base = (long)w.block * CHUNK;
   const long n = t.numel[ti];
   float* __restrict__ p = t.p[ti];
   const float* __restrict__ g = t.g[ti];
@@ -94,17 +95,17 @@ constexpr int NF_MAX_T = 96;
 struct NonfiniteTable {
   const float* g[NF_MAX_T];
   long numel[NF_MAX_T];
-  int blk_start[NF_MAX_T + 1];
-  int count;
+  MtIndex<NF_MAX_T> ix;
 };
+static_assert(sizeof(NonfiniteTable) <= 4096, "the table travels in the kernel arguments");
 __global__ __launch_bounds__(256) void grad_nonfinite_kernel(const NonfiniteTable t, int* __restrict__ state) {
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
-  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * (4 * CHUNK);
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long base = (long)w.block * (4 * CHUNK);
   const long n = t.numel[ti];
   const float* __restrict__ g = t.g[ti];
   const long end = min(n, base + 4 * CHUNK);
-  // |x| as an integer: finite <=> exponent field < 255 <=> (bits & 0x7fffffff) < 0x7f800000; the OR of the "bad" bits of all elements
+  // the OR of the "bad" bits (egv_nonfinite) of all elements
   unsigned bad = 0u;
   if (((n & 3) == 0) && ((((size_t)g) & 15) == 0)) {
     // four independent 16-byte loads per lane in flight (a pure read stream: 724 MB per step, HBM-bound)
@@ -116,15 +117,15 @@ __global__ __launch_bounds__(256) void grad_nonfinite_kernel(const NonfiniteTabl
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) bad |= ((w[u][e] & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+        for (int e = 0; e < 4; ++e) bad |= egv_nonfinite(w[u][e]) ? 1u : 0u;
     }
     for (; i < end; i += 1024) {
       const u32x4_t w = __builtin_bit_cast(u32x4_t, egv_load<EGV_NT_ADAMW_LD, f32x4_t>(g + i));
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bad |= ((w[e] & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+      for (int e = 0; e < 4; ++e) bad |= egv_nonfinite(w[e]) ? 1u : 0u;
     }
   } else {
-    for (long i = base + threadIdx.x; i < end; i += 256) bad |= ((__float_as_uint(g[i]) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+    for (long i = base + threadIdx.x; i < end; i += 256) bad |= egv_nonfinite(__float_as_uint(g[i])) ? 1u : 0u;
   }
   if (__any(bad != 0u) && (threadIdx.x & 63) == 0) atomicOr(state + 2, 1);      // one atomic per wave that saw one; normally none
 }
@@ -183,19 +184,14 @@ struct AccumTable {
   float* d[ACC_MAX_T];
   const float* s[ACC_MAX_T];
   long numel[ACC_MAX_T];
-  int blk_start[ACC_MAX_T + 1];
-  int count;
+  MtIndex<ACC_MAX_T> ix;
 };
 static_assert(sizeof(AccumTable) <= 4096, "the table travels in the kernel arguments");
 
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccumTable t) {
-  int lo = 0, hi = t.count - 1;          // the tensor this block works on: last ti with blk_start[ti] <= blockIdx.x (<= 7 scalar steps)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((int)blockIdx.x >= t.blk_start[mid]) lo = mid; else hi = mid - 1;
-  }
-  const int ti = lo;
-  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * CHUNK;
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long base = (long)w.block * CHUNK;
   const long n = t.numel[ti];
   float* __restrict__ d = t.d[ti];
   const float* __restrict__ s = t.s[ti];
@@ -231,9 +227,9 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccumTable t
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const NonfiniteTable t, float* __restrict__ partials, int first,
                                                           int* __restrict__ state) {
   __shared__ float sh[4];
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
-  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * (4 * CHUNK);
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long base = (long)w.block * (4 * CHUNK);
   const long n = t.numel[ti];
   const float* __restrict__ g = t.g[ti];
   const long end = min(n, base + 4 * CHUNK);
@@ -249,7 +245,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const NonfiniteTable t
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        bad |= ((__float_as_uint(w[u][e]) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+        bad |= egv_nonfinite(__float_as_uint(w[u][e])) ? 1u : 0u;
         acc[e] = fmaf(w[u][e], w[u][e], acc[e]);
       }
   }
@@ -257,13 +253,13 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const NonfiniteTable t
     const f32x4_t w = egv_load<EGV_NT_ADAMW_LD, f32x4_t>(g + i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      bad |= ((__float_as_uint(w[e]) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+      bad |= egv_nonfinite(__float_as_uint(w[e])) ? 1u : 0u;
       acc[e] = fmaf(w[e], w[e], acc[e]);
     }
   }
   for (long j = max(base, vend) + threadIdx.x; j < end; j += 256) {
     const float x = g[j];
-    bad |= ((__float_as_uint(x) & 0x7fffffffu) >= 0x7f800000u) ? 1u : 0u;
+    bad |= egv_nonfinite(__float_as_uint(x)) ? 1u : 0u;
     acc[0] = fmaf(x, x, acc[0]);
   }
   if (state && __any(bad != 0u) && (threadIdx.x & 63) == 0) atomicOr(state + 2, 1);      // as the scan: an integer OR, normally none
@@ -302,7 +298,7 @@ __global__ __launch_bounds__(256) void grad_clip_update_kernel(const float* __re
   const float inv = state ? fs[6] : grad_scale;
   const bool skipped = state ? (fs[7] != 0.f) : false;
   const float norm = (float)(sqrt(total) * (double)inv);
-  const bool nonfinite = skipped || ((__float_as_uint(norm) & 0x7fffffffu) >= 0x7f800000u);
+  const bool nonfinite = skipped || egv_nonfinite(__float_as_uint(norm));
   float coef = 0.f;
   if (nonfinite) {
     norm_block[4] += 1;
@@ -328,70 +324,50 @@ __global__ __launch_bounds__(256) void grad_clip_update_kernel(const float* __re
 
 extern "C" int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* const* src, const int64_t* numel, void* stream) {
   if (count < 0 || (count > 0 && (!dst || !src || !numel))) return EGV_ERR_ARG;
-  for (int i = 0; i < count; ++i) {      // validate everything before the first launch: a bad argument enqueues nothing
-    if (numel[i] < 0) return EGV_ERR_ARG;
-    if (numel[i] == 0) continue;
-    if (!dst[i] || !src[i]) return EGV_ERR_ARG;
-    if (dst[i] < src[i] + numel[i] && src[i] < dst[i] + numel[i]) return EGV_ERR_ARG;      // overlapping ranges
-  }
   hipStream_t s = (hipStream_t)stream;
-  AccumTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
-    EGV_LAUNCH(grad_accumulate_kernel, dim3(nb), dim3(256), 0, s, t);
-    EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
-    return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (numel[i] == 0) continue;
-    if (nt == ACC_MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    t.d[nt] = dst[i];
-    t.s[nt] = src[i];
-    t.numel[nt] = numel[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((numel[i] + CHUNK - 1) / CHUNK);
-    ++nt;
-  }
-  return flush();
+  return mt_for_each_launch<AccumTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (numel[i] <= 0) return numel[i];                                               // 0 is skipped, a negative size is invalid
+        if (!dst[i] || !src[i]) return -1;
+        if (dst[i] < src[i] + numel[i] && src[i] < dst[i] + numel[i]) return -1;          // overlapping ranges
+        return pieces(numel[i], CHUNK);
+      },
+      [&](AccumTable& t, int k, int i) { t.d[k] = dst[i]; t.s[k] = src[i]; t.numel[k] = numel[i]; },
+      [&](const AccumTable& t, int nb) -> int {
+        EGV_LAUNCH(grad_accumulate_kernel, dim3(nb), dim3(256), 0, s, t);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
+}
+
+// The work list of the two gradient scans: (tensor, 4 * CHUNK-element piece) per block.  launch(t, nb, first): `first` = the blocks of
+// the launches before this one.  A NULL pointer of a non-empty tensor is invalid; a negative size is invalid or skipped, as the caller says.
+template <typename Launch>
+static int for_each_scan_launch(int32_t count, const float* const* g, const int64_t* numel, bool negative_is_invalid, Launch launch) {
+  int first = 0;
+  return mt_for_each_launch<NonfiniteTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (numel[i] <= 0) return negative_is_invalid ? numel[i] : 0;
+        return g[i] ? pieces(numel[i], 4 * CHUNK) : -1;
+      },
+      [&](NonfiniteTable& t, int k, int i) { t.g[k] = g[i]; t.numel[k] = numel[i]; },
+      [&](const NonfiniteTable& t, int nb) -> int {
+        const int rc = launch(t, nb, first);
+        first += nb;
+        return rc;
+      });
 }
 
 extern "C" int egv_grad_nonfinite_multi(int32_t count, const float* const* g, const int64_t* numel, int32_t* state, void* stream) {
   if (count < 0 || !g || !numel || !state) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  NonfiniteTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
+  return for_each_scan_launch(count, g, numel, false, [&](const NonfiniteTable& t, int nb, int) -> int {
     EGV_LAUNCH(grad_nonfinite_kernel, dim3(nb), dim3(256), 0, s, t, state);
     EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
     return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (numel[i] <= 0) continue;
-    if (!g[i]) return EGV_ERR_ARG;
-    if (nt == NF_MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    t.g[nt] = g[i];
-    t.numel[nt] = numel[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((numel[i] + 4 * CHUNK - 1) / (4 * CHUNK));
-    ++nt;
-  }
-  return flush();
+  });
 }
 
 // blocks (= partials) of a gradient list, or -1 for a list no launch sequence can take
@@ -399,8 +375,9 @@ static int64_t sqnorm_parts(int32_t count, const int64_t* numel) {
   if (count < 0 || (count > 0 && !numel)) return -1;
   int64_t parts = 0;
   for (int i = 0; i < count; ++i) {
-    if (numel[i] < 0) return -1;
-    parts += (numel[i] + 4 * CHUNK - 1) / (4 * CHUNK);
+    const int64_t b = pieces(numel[i], 4 * CHUNK);
+    if (b < 0) return -1;
+    parts += b;
     if (parts > 0x7fffffff) return -1;
   }
   return parts;
@@ -410,37 +387,14 @@ extern "C" int egv_grad_sqnorm_parts(int32_t count, const int64_t* numel) { retu
 
 extern "C" int egv_grad_sqnorm_multi(int32_t count, const float* const* g, const int64_t* numel, float* partials,
                                      int32_t parts_capacity, int32_t* state, void* stream) {
-  const int64_t parts = sqnorm_parts(count, numel);      // validate everything before the first launch: a bad argument enqueues nothing
+  const int64_t parts = sqnorm_parts(count, numel);
   if (parts < 0 || parts_capacity < parts || (parts > 0 && (!g || !partials))) return EGV_ERR_ARG;
-  for (int i = 0; i < count; ++i)
-    if (numel[i] > 0 && !g[i]) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  NonfiniteTable t;
-  int nt = 0, nb = 0, first = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
+  return for_each_scan_launch(count, g, numel, true, [&](const NonfiniteTable& t, int nb, int first) -> int {
     EGV_LAUNCH(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, s, t, partials, first, state);
     EGV_CHECK_LAUNCH();
-    first += nb;
-    nt = 0;
-    nb = 0;
     return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (numel[i] == 0) continue;
-    if (nt == NF_MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    t.g[nt] = g[i];
-    t.numel[nt] = numel[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((numel[i] + 4 * CHUNK - 1) / (4 * CHUNK));
-    ++nt;
-  }
-  return flush();
+  });
 }
 
 extern "C" int egv_grad_clip_update(const float* partials, int32_t parts, const int32_t* state, float grad_scale, float max_norm,
@@ -487,33 +441,21 @@ extern "C" int egv_adamw_multi(int32_t count, float* const* p, const float* cons
     step_size = (float)((double)lr * sqrt(bc2) / bc1);
   }
   hipStream_t s = (hipStream_t)stream;
-  AdamTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
-    EGV_LAUNCH(adamw_kernel, dim3(nb), dim3(256), 0, s, t, lr, beta1, beta2, eps, weight_decay, step_size,
-                       grad_scale, hyper_dev);
-    EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
-    return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (numel[i] <= 0) continue;
-    if (!p[i] || !g[i] || !m[i] || !v[i]) return EGV_ERR_ARG;
-    if (nt == MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    t.p[nt] = p[i]; t.g[nt] = g[i]; t.m[nt] = m[i]; t.v[nt] = v[i];
-    t.wh[nt] = w_hi ? w_hi[i] : nullptr;
-    t.wl[nt] = w_lo ? w_lo[i] : nullptr;
-    t.numel[nt] = numel[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((numel[i] + CHUNK - 1) / CHUNK);
-    ++nt;
-  }
-  return flush();
+  return mt_for_each_launch<AdamTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (numel[i] <= 0) return 0;
+        return (p[i] && g[i] && m[i] && v[i]) ? pieces(numel[i], CHUNK) : -1;
+      },
+      [&](AdamTable& t, int k, int i) {
+        t.p[k] = p[i]; t.g[k] = g[i]; t.m[k] = m[i]; t.v[k] = v[i];
+        t.wh[k] = w_hi ? w_hi[i] : nullptr;
+        t.wl[k] = w_lo ? w_lo[i] : nullptr;
+        t.numel[k] = numel[i];
+      },
+      [&](const AdamTable& t, int nb) -> int {
+        EGV_LAUNCH(adamw_kernel, dim3(nb), dim3(256), 0, s, t, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, hyper_dev);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
 }

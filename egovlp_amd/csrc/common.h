@@ -86,6 +86,12 @@ __device__ __forceinline__ void split_bf16x2(float a, float b, uint32_t& hi, uin
 
 __device__ __forceinline__ uint32_t pack2(bf16_t a, bf16_t b) { return (uint32_t)a | ((uint32_t)b << 16); }
 
+// inf or NaN, from the bits of an fp32: |x| as an integer; finite <=> exponent field < 255 <=> (bits & 0x7fffffff) < 0x7f800000
+__device__ __forceinline__ bool egv_nonfinite(uint32_t bits) { return (bits & 0x7fffffffu) >= 0x7f800000u; }
+
+// pieces of `piece` elements that cover numel elements (host: the block counts of the element-wise launches); -1 for a negative size
+static inline int64_t pieces(int64_t numel, int64_t piece) { return numel < 0 ? -1 : (numel + piece - 1) / piece; }
+
 // ---- wave64 reductions ------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

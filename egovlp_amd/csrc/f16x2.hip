@@ -3,6 +3,7 @@
 // Linears of :103 and :47).  HBM-bound; every lane owns 8 consecutive elements.
 #include "f16x2.h"
 #include "egovlp_hip.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -49,14 +50,14 @@ struct EncodeTable {
   unsigned short* p1[ENC_MAX_T];
   unsigned short* p2[ENC_MAX_T];
   int ldx[ENC_MAX_T], ldo[ENC_MAX_T], rows[ENC_MAX_T], cols[ENC_MAX_T];
-  int blk_start[ENC_MAX_T + 1];
-  int count;
+  MtIndex<ENC_MAX_T> ix;
 };
+static_assert(sizeof(EncodeTable) <= 4096, "the table travels in the kernel arguments");
 template <int ROLE>
 __global__ __launch_bounds__(256) void f16x2_encode_multi_kernel(const EncodeTable t) {
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
-  const long piece = (long)((int)blockIdx.x - t.blk_start[ti]) * 256 + threadIdx.x;
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long piece = (long)w.block * 256 + threadIdx.x;
   if (piece >= (long)t.rows[ti] * (t.cols[ti] >> 3)) return;
   encode_piece<ROLE>(t.x[ti], t.ldx[ti], t.cols[ti], t.p1[ti], t.p2[ti], nullptr, t.ldo[ti], piece);
 }
@@ -153,35 +154,24 @@ extern "C" int egv_f16x2_encode_multi(int32_t count, const float* const* x, cons
                                       void* stream) {
   if (count < 0 || !x || !ldx || !rows || !cols || !p1 || !p2 || !ldo || (role != 0 && role != 1)) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  EncodeTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
-    if (role == 0) EGV_LAUNCH(f16x2_encode_multi_kernel<0>, dim3(nb), dim3(256), 0, s, t);
-    else EGV_LAUNCH(f16x2_encode_multi_kernel<1>, dim3(nb), dim3(256), 0, s, t);
-    EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
-    return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (!x[i] || !p1[i] || !p2[i] || rows[i] <= 0 || cols[i] <= 0 || cols[i] % 8 != 0 || ldo[i] % 8 != 0 || ldx[i] % 4 != 0 ||
-        ldx[i] > 0x7fffffff || ldo[i] > 0x7fffffff)
-      return EGV_ERR_ARG;
-    if (nt == ENC_MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    const long pieces = (long)rows[i] * (cols[i] >> 3);
-    t.x[nt] = x[i]; t.p1[nt] = p1[i]; t.p2[nt] = p2[i];
-    t.ldx[nt] = (int)ldx[i]; t.ldo[nt] = (int)ldo[i]; t.rows[nt] = rows[i]; t.cols[nt] = cols[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((pieces + 255) / 256);
-    ++nt;
-  }
-  return flush();
+  return mt_for_each_launch<EncodeTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (!x[i] || !p1[i] || !p2[i] || rows[i] <= 0 || cols[i] <= 0 || cols[i] % 8 != 0 || ldo[i] % 8 != 0 || ldx[i] % 4 != 0 ||
+            ldx[i] > 0x7fffffff || ldo[i] > 0x7fffffff)
+          return -1;
+        return pieces((int64_t)rows[i] * (cols[i] >> 3), 256);      // 8-element pieces, one per thread
+      },
+      [&](EncodeTable& t, int k, int i) {
+        t.x[k] = x[i]; t.p1[k] = p1[i]; t.p2[k] = p2[i];
+        t.ldx[k] = (int)ldx[i]; t.ldo[k] = (int)ldo[i]; t.rows[k] = rows[i]; t.cols[k] = cols[i];
+      },
+      [&](const EncodeTable& t, int nb) -> int {
+        if (role == 0) EGV_LAUNCH(f16x2_encode_multi_kernel<0>, dim3(nb), dim3(256), 0, s, t);
+        else EGV_LAUNCH(f16x2_encode_multi_kernel<1>, dim3(nb), dim3(256), 0, s, t);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
 }
 
 extern "C" int egv_layernorm_fwd_f16x2(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int32_t rows,

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "f16x2.h"
 #include "egovlp_hip.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -119,15 +120,14 @@ struct SplitTable {
   unsigned short* t16[SPLIT_MAX_T];
   int ldx[SPLIT_MAX_T], ldo[SPLIT_MAX_T], ldt[SPLIT_MAX_T], rows[SPLIT_MAX_T], cols[SPLIT_MAX_T], text[SPLIT_MAX_T];
   int tiles_x[SPLIT_MAX_T];
-  int blk_start[SPLIT_MAX_T + 1];
-  int count;
+  MtIndex<SPLIT_MAX_T> ix;
 };
+static_assert(sizeof(SplitTable) <= 4096, "the table travels in the kernel arguments");
 
 __global__ __launch_bounds__(256) void split_multi_kernel(const SplitTable t) {
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
-  const int local = (int)blockIdx.x - t.blk_start[ti];
-  const int ty = local / t.tiles_x[ti], tx = local - ty * t.tiles_x[ti];
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const int ty = w.block / t.tiles_x[ti], tx = w.block - ty * t.tiles_x[ti];
   split_transpose_tile<false>(t.x[ti], nullptr, nullptr, t.ldx[ti], t.rows[ti], t.cols[ti], t.hi[ti], t.lo[ti], t.ldo[ti],
                               t.thi[ti], t.tlo[ti], t.ldt[ti], nullptr, ty * 64, tx * 64, t.text[ti], t.t16[ti]);
 }
@@ -210,39 +210,29 @@ extern "C" int egv_split_f32_multi_t16(int32_t count, const float* const* x, con
                                        uint16_t* const* t16, void* stream) {
   if (count < 0 || !x || !ldx || !rows || !cols || !hi || !lo || !ldo || !t_hi || !t_lo || !ldt || !t_cols) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  SplitTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
-    EGV_LAUNCH(split_multi_kernel, dim3(nb), dim3(256), 0, s, t);
-    EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
-    return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    unsigned short* const tf = t16 ? t16[i] : nullptr;
-    const bool has_t = t_hi[i] || tf;
-    if (!x[i] || rows[i] <= 0 || cols[i] <= 0 || cols[i] % 4 != 0 || (!hi[i] && !has_t)) return EGV_ERR_ARG;
-    if (has_t && (ldt[i] < rows[i] || ldt[i] % 4 != 0 || t_cols[i] < rows[i] || t_cols[i] > ldt[i] || t_cols[i] % 4 != 0)) return EGV_ERR_ARG;
-    if (ldx[i] > 0x7fffffff || ldo[i] > 0x7fffffff || ldt[i] > 0x7fffffff) return EGV_ERR_ARG;
-    if (nt == SPLIT_MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    const int row_extent = has_t ? t_cols[i] : rows[i];   // cover this tensor's share of the zero pad of the transposed planes
-    const int tx = (cols[i] + 63) / 64, ty = (row_extent + 63) / 64;
-    t.x[nt] = x[i]; t.hi[nt] = hi[i]; t.lo[nt] = lo[i]; t.thi[nt] = t_hi[i]; t.tlo[nt] = t_lo[i];
-    t.ldx[nt] = (int)ldx[i]; t.ldo[nt] = (int)ldo[i]; t.ldt[nt] = (int)ldt[i]; t.rows[nt] = rows[i]; t.cols[nt] = cols[i]; t.text[nt] = has_t ? t_cols[i] : rows[i];
-    t.t16[nt] = tf;
-    t.tiles_x[nt] = tx;
-    t.blk_start[nt] = nb;
-    nb += tx * ty;
-    ++nt;
-  }
-  return flush();
+  auto t16_of = [&](int i) -> unsigned short* { return t16 ? t16[i] : nullptr; };
+  // rows of the tile grid: with transposed planes, this tensor's share of their zero pad is covered too
+  auto row_extent = [&](int i) -> int { return (t_hi[i] || t16_of(i)) ? t_cols[i] : rows[i]; };
+  return mt_for_each_launch<SplitTable>(
+      count,
+      [&](int i) -> int64_t {
+        const bool has_t = t_hi[i] || t16_of(i);
+        if (!x[i] || rows[i] <= 0 || cols[i] <= 0 || cols[i] % 4 != 0 || (!hi[i] && !has_t)) return -1;
+        if (has_t && (ldt[i] < rows[i] || ldt[i] % 4 != 0 || t_cols[i] < rows[i] || t_cols[i] > ldt[i] || t_cols[i] % 4 != 0)) return -1;
+        if (ldx[i] > 0x7fffffff || ldo[i] > 0x7fffffff || ldt[i] > 0x7fffffff) return -1;
+        return pieces(cols[i], 64) * pieces(row_extent(i), 64);
+      },
+      [&](SplitTable& t, int k, int i) {
+        t.x[k] = x[i]; t.hi[k] = hi[i]; t.lo[k] = lo[i]; t.thi[k] = t_hi[i]; t.tlo[k] = t_lo[i];
+        t.ldx[k] = (int)ldx[i]; t.ldo[k] = (int)ldo[i]; t.ldt[k] = (int)ldt[i]; t.rows[k] = rows[i]; t.cols[k] = cols[i]; t.text[k] = row_extent(i);
+        t.t16[k] = t16_of(i);
+        t.tiles_x[k] = (cols[i] + 63) / 64;
+      },
+      [&](const SplitTable& t, int nb) -> int {
+        EGV_LAUNCH(split_multi_kernel, dim3(nb), dim3(256), 0, s, t);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
 }
 
 extern "C" int egv_transpose_planes(const egv_bf16* hi, const egv_bf16* lo, int64_t ldx, int32_t rows, int32_t cols,

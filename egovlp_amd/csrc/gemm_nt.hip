@@ -26,6 +26,7 @@
 // the weight panel they all stream, sit in one XCD's L2.
 #include "common.h"
 #include "egovlp_hip.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -226,14 +227,13 @@ struct ReduceTable {
   float* colsum[RED_MAX_T];
   long mn[RED_MAX_T];
   int m[RED_MAX_T], ks[RED_MAX_T];
-  int blk_start[RED_MAX_T + 1];     // first block of entry i (its product slab blocks, then its column-sum blocks)
-  int blocks1[RED_MAX_T];           // product-slab blocks of entry i
-  int count;
+  int blocks1[RED_MAX_T];           // product-slab blocks of entry i (its column-sum blocks follow them)
+  MtIndex<RED_MAX_T> ix;
 };
+static_assert(sizeof(ReduceTable) <= 4096, "the table travels in the kernel arguments");
 __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(const ReduceTable t) {
-  int e = 0;
-  while (e + 1 < t.count && (int)blockIdx.x >= t.blk_start[e + 1]) ++e;
-  const int local = (int)blockIdx.x - t.blk_start[e];
+  const MtWork w = mt_locate(t.ix);
+  const int e = w.item, local = w.block;
   const int ks = t.ks[e];
   const float* partial = t.partial[e];
   float* out = t.out[e];
@@ -258,23 +258,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(const ReduceTa
 extern "C" int egv_splitk_reduce_multi(int32_t count, const float* const* partial, float* const* out, const int64_t* mn, const int32_t* ksplit,
                                        float* const* colsum, const int32_t* m, void* stream) {
   if (count < 1 || count > RED_MAX_T || !partial || !out || !mn || !ksplit) return EGV_ERR_ARG;
-  ReduceTable t = {};
-  int nb = 0;
-  for (int i = 0; i < count; ++i) {
-    if (!partial[i] || !out[i] || mn[i] <= 0 || mn[i] % 4 != 0 || ksplit[i] < 2) return EGV_ERR_ARG;
-    const bool cs = colsum && colsum[i];
-    if (cs && (!m || m[i] <= 0 || m[i] % 4 != 0)) return EGV_ERR_ARG;
-    t.partial[i] = partial[i]; t.out[i] = out[i]; t.colsum[i] = cs ? colsum[i] : nullptr;
-    t.mn[i] = mn[i]; t.m[i] = cs ? m[i] : 0; t.ks[i] = ksplit[i];
-    t.blk_start[i] = nb;
-    t.blocks1[i] = (int)((mn[i] / 4 + 255) / 256);
-    nb += t.blocks1[i] + (cs ? (m[i] / 4 + 255) / 256 : 0);
-  }
-  t.blk_start[count] = nb;
-  t.count = count;
-  EGV_LAUNCH(splitk_reduce_multi_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, t);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
+  // count <= RED_MAX_T: ONE launch (the block call relies on it); 4-element pieces, one per thread
+  auto has_colsum = [&](int i) -> bool { return colsum && colsum[i]; };
+  return mt_for_each_launch<ReduceTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (!partial[i] || !out[i] || mn[i] <= 0 || mn[i] % 4 != 0 || ksplit[i] < 2) return -1;
+        if (has_colsum(i) && (!m || m[i] <= 0 || m[i] % 4 != 0)) return -1;
+        return pieces(mn[i] / 4, 256) + (has_colsum(i) ? pieces(m[i] / 4, 256) : 0);
+      },
+      [&](ReduceTable& t, int k, int i) {
+        const bool cs = has_colsum(i);
+        t.partial[k] = partial[i]; t.out[k] = out[i]; t.colsum[k] = cs ? colsum[i] : nullptr;
+        t.mn[k] = mn[i]; t.m[k] = cs ? m[i] : 0; t.ks[k] = ksplit[i];
+        t.blocks1[k] = (int)pieces(mn[i] / 4, 256);
+      },
+      [&](const ReduceTable& t, int nb) -> int {
+        EGV_LAUNCH(splitk_reduce_multi_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, t);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
 }
 
 int egv_gemm_big_launch(const egv_gemm_desc& p, hipStream_t s, int variant);  // gemm_big.hip

@@ -6,6 +6,7 @@
 // 4 B read + 2 B written per element packing, 2 B + 4 B unpacking.
 #include "common.h"
 #include "egovlp_hip.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -16,15 +17,15 @@ struct PackTable {
   float* f32[MAX_T];             // the fp32 side (source when packing, destination when unpacking)
   long off[MAX_T];               // element offset of the tensor inside the flat bf16 buffer
   long numel[MAX_T];
-  int blk_start[MAX_T + 1];
-  int count;
+  MtIndex<MAX_T> ix;
 };
+static_assert(sizeof(PackTable) <= 4096, "the table travels in the kernel arguments");
 
 template <bool PACK>
 __global__ __launch_bounds__(256) void grad_pack_kernel(const PackTable t, bf16_t* __restrict__ flat, float scale) {
-  int ti = 0;
-  while (ti + 1 < t.count && (int)blockIdx.x >= t.blk_start[ti + 1]) ++ti;
-  const long base = (long)((int)blockIdx.x - t.blk_start[ti]) * CHUNK;
+  const MtWork w = mt_locate(t.ix);
+  const int ti = w.item;
+  const long base = (long)w.block * CHUNK;
   const long n = t.numel[ti];
   float* __restrict__ f = t.f32[ti];
   bf16_t* __restrict__ b = flat + t.off[ti];
@@ -52,33 +53,18 @@ __global__ __launch_bounds__(256) void grad_pack_kernel(const PackTable t, bf16_
 template <bool PACK>
 int run(int32_t count, float* const* f32, const int64_t* numel, bf16_t* flat, const int64_t* off, float scale, hipStream_t s) {
   if (count < 0 || !f32 || !numel || !flat || !off) return EGV_ERR_ARG;
-  PackTable t;
-  int nt = 0, nb = 0;
-  auto flush = [&]() -> int {
-    if (nt == 0) return EGV_OK;
-    t.blk_start[nt] = nb;
-    t.count = nt;
-    EGV_LAUNCH(grad_pack_kernel<PACK>, dim3(nb), dim3(256), 0, s, t, flat, scale);
-    EGV_CHECK_LAUNCH();
-    nt = 0;
-    nb = 0;
-    return EGV_OK;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (numel[i] <= 0) continue;
-    if (!f32[i] || off[i] < 0) return EGV_ERR_ARG;
-    if (nt == MAX_T) {
-      const int rc = flush();
-      if (rc) return rc;
-    }
-    t.f32[nt] = f32[i];
-    t.off[nt] = off[i];
-    t.numel[nt] = numel[i];
-    t.blk_start[nt] = nb;
-    nb += (int)((numel[i] + CHUNK - 1) / CHUNK);
-    ++nt;
-  }
-  return flush();
+  return mt_for_each_launch<PackTable>(
+      count,
+      [&](int i) -> int64_t {
+        if (numel[i] <= 0) return 0;
+        return (f32[i] && off[i] >= 0) ? pieces(numel[i], CHUNK) : -1;
+      },
+      [&](PackTable& t, int k, int i) { t.f32[k] = f32[i]; t.off[k] = off[i]; t.numel[k] = numel[i]; },
+      [&](const PackTable& t, int nb) -> int {
+        EGV_LAUNCH(grad_pack_kernel<PACK>, dim3(nb), dim3(256), 0, s, t, flat, scale);
+        EGV_CHECK_LAUNCH();
+        return EGV_OK;
+      });
 }
 
 // The local step of the DIRECT exchange (egovlp_amd.dist.Bf16GradSync, exchange = "direct"): after the all-to-all every rank holds

@@ -63,8 +63,7 @@ def timed(name, fn):
 def _hip_pack(grads, flat, offsets, scale):
     from . import _lib, ops
     n = len(grads)
-    P = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
-    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    P, N = ops._addrs(grads), ops._numels(grads)
     O = (C.c_int64 * n)(*offsets)
     _lib.check(_lib.lib().egv_grad_pack_bf16(n, P, N, flat.data_ptr(), O, float(scale), ops._stream()), "egv_grad_pack_bf16")
 
@@ -78,8 +77,7 @@ def _hip_slice_sum(recv, world, slice_elems, out):
 def _hip_unpack(grads, flat, offsets):
     from . import _lib, ops
     n = len(grads)
-    P = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
-    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    P, N = ops._addrs(grads), ops._numels(grads)
     O = (C.c_int64 * n)(*offsets)
     _lib.check(_lib.lib().egv_grad_unpack_bf16(n, P, N, flat.data_ptr(), O, ops._stream()), "egv_grad_unpack_bf16")
 

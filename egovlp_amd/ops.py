@@ -526,6 +526,16 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _addrs(tensors):
+    """The host array of device addresses a multi-tensor entry point takes."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _numels(tensors):
+    """The host array of element counts that goes with _addrs."""
+    return (C.c_int64 * len(tensors))(*[t.numel() for t in tensors])
+
+
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -1344,8 +1354,8 @@ def grad_nonfinite_multi(grads, state):
     n = len(grads)
     if n == 0:
         return
-    G = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
-    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    G = _addrs(grads)
+    N = _numels(grads)
     check(_lib.lib().egv_grad_nonfinite_multi(n, G, N, _p(state), _stream(grads[0])), "egv_grad_nonfinite_multi")
 
 
@@ -1362,9 +1372,9 @@ def grad_accumulate_multi(dst_list, src_list):
         if d.dtype != torch.float32 or s.dtype != torch.float32 or d.numel() != s.numel() or not (d.is_contiguous() and s.is_contiguous()):
             raise ValueError("grad_accumulate_multi: pairs of dense contiguous fp32 tensors of equal size")
     _need_cuda(*dst_list, *src_list)
-    D = (C.c_void_p * n)(*[d.data_ptr() for d in dst_list])
-    S = (C.c_void_p * n)(*[s.data_ptr() for s in src_list])
-    N = (C.c_int64 * n)(*[d.numel() for d in dst_list])
+    D = _addrs(dst_list)
+    S = _addrs(src_list)
+    N = _numels(dst_list)
     check(_lib.lib().egv_grad_accumulate_multi(n, D, S, N, _stream(dst_list[0])), "egv_grad_accumulate_multi")
 
 
@@ -1377,7 +1387,7 @@ def loss_scale_update(state, hyper_out, lr, beta1, beta2, step, correct_bias, gr
 def grad_sqnorm_parts(grads):
     """How many partial sums grad_sqnorm_multi writes for this list (egv_grad_sqnorm_parts: one per 65 536-element piece of a tensor)."""
     n = len(grads)
-    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    N = _numels(grads)
     parts = int(_lib.lib().egv_grad_sqnorm_parts(n, N))
     if parts < 0:
         raise ValueError("grad_sqnorm_parts: the gradient list is beyond 2^31 - 1 pieces")
@@ -1397,8 +1407,8 @@ def grad_sqnorm_multi(grads, partials, state=None):
     if partials.dtype != torch.float32 or not partials.is_contiguous():
         raise ValueError("grad_sqnorm_multi: `partials` is a contiguous fp32 tensor")
     _need_cuda(*grads, partials)
-    G = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
-    N = (C.c_int64 * n)(*[g.numel() for g in grads])
+    G = _addrs(grads)
+    N = _numels(grads)
     check(_lib.lib().egv_grad_sqnorm_multi(n, G, N, _p(partials), partials.numel(), _p(state), _stream(grads[0])),
           "egv_grad_sqnorm_multi")
 
@@ -1413,7 +1423,7 @@ def grad_clip_update(partials, parts, norm_block, max_norm, hyper_blocks, state=
         raise ValueError("grad_clip_update: 1 .. 64 hyper blocks (parameter groups / launch groups) per step")
     if state is None and (lrs is None or step_sizes is None or len(lrs) != n or len(step_sizes) != n):
         raise ValueError("grad_clip_update: without a scaler state, one lr and one step size per hyper block")
-    H = (C.c_void_p * n)(*[h.data_ptr() for h in hyper_blocks])
+    H = _addrs(hyper_blocks)
     L = (C.c_float * n)(*[float(x) for x in lrs]) if state is None else None
     S = (C.c_float * n)(*[float(x) for x in step_sizes]) if state is None else None
     check(_lib.lib().egv_grad_clip_update(_p(partials), int(parts), _p(state), float(grad_scale), float(max_norm), n, H, L, S,
@@ -1422,17 +1432,14 @@ def grad_clip_update(partials, parts, norm_block, max_norm, hyper_blocks, state=
 
 def adamw_tables(params, ms, vs):
     """The argument tables of egv_adamw_multi that do not change from step to step (parameter / moment addresses, sizes)."""
-    n = len(params)
-    arr = C.c_void_p * n
-    return (arr(*[p.data_ptr() for p in params]), arr(*[m.data_ptr() for m in ms]), arr(*[v.data_ptr() for v in vs]),
-            (C.c_int64 * n)(*[p.numel() for p in params]))
+    return _addrs(params), _addrs(ms), _addrs(vs), _numels(params)
 
 
 def adamw_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias=True, grad_scale=1.0, hyper_dev=None,
                 tables=None):
     n = len(params)
     P, M_, V, N = tables if tables is not None else adamw_tables(params, ms, vs)
-    G = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
+    G = _addrs(grads)
     check(_lib.lib().egv_adamw_multi(n, P, G, M_, V, None, None, N, float(lr), float(beta1), float(beta2),
                                      float(eps), float(weight_decay), int(step), int(correct_bias),
                                      float(grad_scale), _p(hyper_dev), _stream(params[0])), "egv_adamw_multi")

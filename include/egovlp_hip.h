@@ -112,7 +112,8 @@ int egv_split_f32(const float* x, int64_t ldx, int32_t rows, int32_t cols,
 /* The same for `count` tensors in one launch (host arrays of device pointers / sizes; no column sums): the once-per-
  * optimizer-step refresh of every weight's operand planes W[N,K] and W^T[K,N] (~100 tensors per step).
  * t_cols[i] = columns of the transposed planes tensor i owns (rows[i] <= t_cols[i] <= ldt[i]; rows[i] .. t_cols[i]-1 are
- * zero-filled) -- several tensors may share one pair of transposed planes side by side (DistilBERT's fused q/k/v weight). */
+ * zero-filled) -- several tensors may share one pair of transposed planes side by side (DistilBERT's fused q/k/v weight).
+ * Everything is validated before the first launch: an invalid tensor anywhere in the list enqueues nothing.               */
 int egv_split_f32_multi(int32_t count, const float* const* x, const int64_t* ldx, const int32_t* rows, const int32_t* cols,
                         egv_bf16* const* hi, egv_bf16* const* lo, const int64_t* ldo, egv_bf16* const* t_hi,
                         egv_bf16* const* t_lo, const int64_t* ldt, const int32_t* t_cols, void* stream);
@@ -141,7 +142,8 @@ int egv_transpose_planes(const egv_bf16* hi, const egv_bf16* lo, int64_t ldx, in
  * forward operands only.                                                                                                          */
 int egv_f16x2_encode(const float* x, int64_t ldx, int32_t rows, int32_t cols, uint16_t* p1, uint16_t* p2, egv_bf16* bf,
                      int64_t ldo, int32_t role, void* stream);
-/* `count` tensors in one launch (HOST arrays of device pointers / sizes): the once-per-optimizer-step refresh of the weights.     */
+/* `count` tensors in one launch (HOST arrays of device pointers / sizes): the once-per-optimizer-step refresh of the weights.
+ * Everything is validated before the first launch: an invalid tensor anywhere in the list enqueues nothing.                       */
 int egv_f16x2_encode_multi(int32_t count, const float* const* x, const int64_t* ldx, const int32_t* rows, const int32_t* cols,
                            uint16_t* const* p1, uint16_t* const* p2, const int64_t* ldo, int32_t role, void* stream);
 /* nn.LayerNorm (model/video_transformer.py:146,156,159 -> the qkv / fc1 Linears) with the output written in the f16x2 format,
@@ -672,7 +674,9 @@ int egv_row_normalize(const float* x, int64_t ldx, int32_t rows, int32_t D, floa
  * Replaces the fp32 bucket copies of DistributedDataParallel (base/base_trainer.py:258): `count` fp32 gradient tensors
  * (HOST arrays of device pointers / sizes) are scaled by `scale` (= 1 / world size), rounded to bf16 (RNE) and written to
  * flat[offsets[i] .. offsets[i] + numel[i]) -- the buffer RCCL all-reduces -- and read back into the fp32 tensors
- * afterwards.  offsets are in elements; multiples of 8 keep every access 16 bytes wide.                               */
+ * afterwards.  offsets are in elements; multiples of 8 keep every access 16 bytes wide.  Tensors with numel <= 0 are
+ * skipped.  Everything is validated before the first launch: a NULL pointer or a negative offset of a non-empty tensor
+ * anywhere in the list enqueues nothing.                                                                              */
 int egv_grad_pack_bf16(int32_t count, const float* const* grads, const int64_t* numel, egv_bf16* flat,
                        const int64_t* offsets, float scale, void* stream);
 int egv_grad_unpack_bf16(int32_t count, float* const* grads, const int64_t* numel, const egv_bf16* flat,
@@ -690,7 +694,9 @@ int egv_slice_sum_bf16(const egv_bf16* recv, int32_t world, int64_t slice_elems,
  * hyper_dev (optional, DEVICE, 4 floats {lr, step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t), grad_scale, skip}): when given,
  * the kernel takes the step-dependent scalars from there instead of lr / step / grad_scale, and does NOTHING when skip != 0 --
  * the block egv_loss_scale_update writes on the same stream (dynamic loss scale of the fp16 backward: whether the step is applied,
- * the 1 / S that un-scales the gradients and the bias correction at the number of APPLIED steps are decided on the device).   */
+ * the 1 / S that un-scales the gradients and the bias correction at the number of APPLIED steps are decided on the device).
+ * Tensors with numel <= 0 are skipped.  Everything is validated before the first launch: a NULL p / g / m / v of a non-empty
+ * tensor anywhere in the list enqueues nothing.                                                                               */
 int egv_adamw_multi(int32_t count, float* const* p, const float* const* g, float* const* m, float* const* v,
                     egv_bf16* const* w_hi, egv_bf16* const* w_lo, const int64_t* numel,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
@@ -716,7 +722,9 @@ int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* con
  * egv_loss_scale_update (one thread): advance != 0: found_inf ? (skip = 1, skipped += 1, S = max(S * backoff_factor, 1), good = 0)
  * : (skip = 0, good += 1; good == growth_interval ? S = min(S * growth_factor, max_scale), good = 0), found_inf = 0, 1 / S of the
  * scale the step RAN with -> state[6]; then {lr, step_size at t = step - skipped, state[6], state[7]} -> hyper_out (NULL: state + 4;
- * advance == 0 fills a further parameter group's block from the decision already taken).                                          */
+ * advance == 0 fills a further parameter group's block from the decision already taken).
+ * egv_grad_nonfinite_multi skips tensors with numel <= 0; everything is validated before the first launch: a NULL pointer of a
+ * non-empty tensor anywhere in the list enqueues nothing.                                                                         */
 int egv_grad_nonfinite_multi(int32_t count, const float* const* grads, const int64_t* numel, int32_t* state, void* stream);
 int egv_loss_scale_update(int32_t* state, float* hyper_out, float lr, float beta1, float beta2, int32_t step, int32_t correct_bias,
                           float growth_factor, float backoff_factor, int32_t growth_interval, float max_scale, int32_t advance,

@@ -71,6 +71,38 @@ def f32(x):
     return float(np.float32(x))
 
 
+# ------------------------------------------------------------------------------------------------------------------------- work list
+MT_MAX_GRID = 2 ** 31 - 1
+
+
+def mt_plan(blocks, max_t, launch_results=()):
+    """What mt_for_each_launch (csrc/multi_tensor.h) does with a list of block counts and a table of max_t items, written out
+    independently: -> (result, launches), a launch being (nb, [item of every slot], blk_start row of count + 1 entries).  A negative
+    count or one above 2^31 - 1 anywhere: result 1 and no launch.  Zeros take no slot.  A launch goes out when the table is full or
+    the next item would push its grid past 2^31 - 1.  launch_results[k]: what the k-th launch returns (0 when not given); the first
+    non-zero one ends the call and is the result."""
+    if any(b < 0 or b > MT_MAX_GRID for b in blocks):
+        return 1, []
+    groups, cur = [], []
+    for i, b in enumerate(blocks):
+        if b == 0:
+            continue
+        if len(cur) == max_t or sum(blocks[j] for j in cur) + b > MT_MAX_GRID:
+            groups.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        groups.append(cur)
+    launches = []
+    for k, items in enumerate(groups):
+        starts = [sum(blocks[j] for j in items[:n]) for n in range(len(items) + 1)]
+        launches.append((starts[-1], items, starts))
+        rc = launch_results[k] if k < len(launch_results) else 0
+        if rc:
+            return rc, launches
+    return 0, launches
+
+
 # ------------------------------------------------------------------------------------------------------------------------- arena
 class Arena:
     """The tensors of a case carved out of ONE flat buffer that is filled with a sentinel bit pattern: at least GUARD sentinel elements

@@ -642,3 +642,83 @@ def test_splitk_reduce_multi_rejects_what_it_cannot_hold(ops):
     assert _reduce_call(ops, mixed, [partial[0], partial[-1]], out, cs) == 1
     assert _reduce_call(ops, entries, partial, out, cs, count=0) == 1
     assert torch.equal(out.bits, snap_o) and torch.equal(cs.bits, snap_c)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- validation
+def _bad_adamw(ops):
+    n = R.TABLE["adamw"] + 1
+    numels = [4] * n
+    ar = _adamw_arenas(numels, {s: [0] * n for s in "pgmv"}, R.adamw_inputs(numels, 1000, 1.0, 5))
+    g = ar["g"].ptrs()
+    g[-1] = None
+    outs = [ar[s] for s in "pmv"]
+    call = lambda: _h().egv_adamw_multi(n, _vp(ar["p"].ptrs()), _vp(g), _vp(ar["m"].ptrs()), _vp(ar["v"].ptrs()), None, None, _i64(numels),
+                                        LR, B1, B2, EPS, 0.01, 1000, 1, 1.0, None, _stream(ops))
+    return [call], outs
+
+
+def _bad_nonfinite(ops):
+    n = R.TABLE["nonfinite"] + 1
+    data = [torch.ones(4) for _ in range(n)]
+    data[0][1] = float("inf")
+    arena = R.Arena([(4, 0)] * n).fill(data).to(DEV)
+    g = arena.ptrs()
+    g[-1] = None
+    state = torch.zeros(8, dtype=torch.int32, device=DEV)
+    call = lambda: _h().egv_grad_nonfinite_multi(n, _vp(g), _i64([4] * n), state.data_ptr(), _stream(ops))
+    return [call], [state]
+
+
+def _bad_pack_unpack(ops):
+    n = R.TABLE["gradsync"] + 1
+    gen = torch.Generator().manual_seed(6)
+    src = R.Arena([(4, 0)] * n).fill([torch.randn(4, generator=gen) for _ in range(n)]).to(DEV)
+    dst = R.Arena([(4, 0)] * n).to(DEV)
+    offs = [8 * i for i in range(n - 1)] + [-1]
+    flat = torch.full((8 * n,), R.SENTINEL[torch.bfloat16], dtype=torch.int16, device=DEV)
+    pack = lambda: _h().egv_grad_pack_bf16(n, _vp(src.ptrs()), _i64([4] * n), flat.data_ptr(), _i64(offs), 1.0, _stream(ops))
+    unpack = lambda: _h().egv_grad_unpack_bf16(n, _vp(dst.ptrs()), _i64([4] * n), flat.data_ptr(), _i64(offs), _stream(ops))
+    return [pack, unpack], [flat, dst]
+
+
+def _bad_split(ops):
+    n = R.TABLE["split"] + 1
+    x = torch.randn(n, 4, 8, generator=torch.Generator().manual_seed(7)).to(DEV)
+    hi, lo = (R.Arena([(32, 0)] * n, dtype=torch.bfloat16).to(DEV) for _ in range(2))
+    cols = [8] * (n - 1) + [6]
+    null, zero = _vp([None] * n), _i64([0] * n)
+    call = lambda: _h().egv_split_f32_multi(n, _vp([x[i].data_ptr() for i in range(n)]), _i64([8] * n), _i32([4] * n), _i32(cols),
+                                            _vp(hi.ptrs()), _vp(lo.ptrs()), _i64([8] * n), null, null, zero, _i32([0] * n), _stream(ops))
+    return [call], [hi, lo]
+
+
+def _bad_encode(ops):
+    n = R.TABLE["f16x2"] + 1
+    x = torch.randn(n, 4, 8, generator=torch.Generator().manual_seed(8)).to(DEV)
+    p1, p2 = (R.Arena([(32, 0)] * n, dtype=torch.float16).to(DEV) for _ in range(2))
+    cols = [8] * (n - 1) + [4]
+    call = lambda: _h().egv_f16x2_encode_multi(n, _vp([x[i].data_ptr() for i in range(n)]), _i64([8] * n), _i32([4] * n), _i32(cols),
+                                               _vp(p1.ptrs()), _vp(p2.ptrs()), _i64([8] * n), 1, _stream(ops))
+    return [call], [p1, p2]
+
+
+BAD_ITEM = {"egv_adamw_multi": _bad_adamw, "egv_grad_nonfinite_multi": _bad_nonfinite, "egv_grad_pack_bf16-egv_grad_unpack_bf16": _bad_pack_unpack,
+            "egv_split_f32_multi": _bad_split, "egv_f16x2_encode_multi": _bad_encode}
+
+
+@pytest.mark.parametrize("entry", list(BAD_ITEM))
+def test_invalid_item_behind_the_first_table_enqueues_nothing(ops, entry):
+    """One full table of valid items (4 to 32 elements each) and, directly behind it, an item the host refuses -- a NULL gradient,
+    a NULL tensor of 4 elements, a flat offset of -1, cols = 6 (not a multiple of 4), cols = 4 (not a multiple of 8): the call
+    returns 1 and, after a synchronize, every output -- p / m / v, the scaler's state (its found-inf word stays 0 although tensor 0
+    holds an inf), the flat buffer and the fp32 destinations, the planes -- has the bits it had before, guards included: the
+    first table was not launched."""
+    calls, outs = BAD_ITEM[entry](ops)
+    bits = lambda o: o.bits if isinstance(o, R.Arena) else o
+    before = [bits(o).clone() for o in outs]
+    torch.cuda.synchronize()
+    for call in calls:
+        assert call() == 1
+    torch.cuda.synchronize()
+    for i, (o, b) in enumerate(zip(outs, before)):
+        assert torch.equal(bits(o), b), (entry, "output %d was written" % i)

@@ -1,6 +1,11 @@
 """The references of tests/multi_tensor_ref.py judged on their own, without a GPU: adamw_ref64 against the oracle's AdamW in fp64, the
 fp32 oracle inside the element-wise bound the GPU test applies (on the GPU test's own inputs), loss_scale_ref against traces written
-out by hand, the arena helper, and the table sizes the GPU tests hard-code against the .hip sources."""
+out by hand, the arena helper, the table sizes the GPU tests hard-code against the .hip sources, and the host half of csrc/multi_tensor.h
+(a stand-alone program under the address and undefined-behaviour sanitizers) against the plan of R.mt_plan."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 import torch
@@ -207,3 +212,90 @@ def test_table_sizes_and_chunk_match_the_sources():
             assert have.get(name) == value, (fname, name, have.get(name), value)
     assert R.TABLE == {"adamw": 48, "nonfinite": 96, "accumulate": 120, "gradsync": 96, "split": 40, "f16x2": 48, "splitk_reduce": 8}
     assert R.CHUNK == 16384
+
+
+# ------------------------------------------------------------------------------------------------------------------------- work list
+MT_DRIVER = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "multi_tensor.h"
+
+struct Table {
+  int item[3];
+  MtIndex<3> ix;
+};
+
+// argv: <launch call that fails, 0 = none> <what it returns> <block count of every item ...>
+int main(int argc, char** argv) {
+  const int fail_at = atoi(argv[1]), fail_rc = atoi(argv[2]);
+  std::vector<long long> blocks;
+  for (int a = 3; a < argc; ++a) blocks.push_back(atoll(argv[a]));
+  int calls = 0;
+  const int rc = mt_for_each_launch<Table>(
+      (int)blocks.size(), [&](int i) -> int64_t { return blocks[i]; }, [&](Table& t, int slot, int i) { t.item[slot] = i; },
+      [&](const Table& t, int nb) -> int {
+        printf("launch nb %d count %d items", nb, t.ix.count);
+        for (int k = 0; k < t.ix.count; ++k) printf(" %d", t.item[k]);
+        printf(" blk_start");
+        for (int k = 0; k <= t.ix.count; ++k) printf(" %d", t.ix.blk_start[k]);
+        printf("\n");
+        return ++calls == fail_at ? fail_rc : 0;
+      });
+  printf("result %d\n", rc);
+  return 0;
+}
+"""
+
+G = R.MT_MAX_GRID
+MT_CASES = [                                                        # (id, block counts, launch call that fails, its result)
+    ("empty", [], 0, 0),
+    ("only-zeros", [0, 0], 0, 0),
+    ("zeros-front-middle-end", [0, 0, 5, 0, 2, 0, 0, 9, 4, 0, 0], 0, 0),
+    ("3-items-one-launch", [4, 1, 7], 0, 0),
+    ("4-items-two-launches", [4, 1, 7, 2], 0, 0),
+    ("7-items-three-launches", [1, 2, 3, 4, 5, 6, 7], 0, 0),
+    ("negative-first", [-1, 1, 1, 1, 1], 0, 0),
+    ("negative-behind-the-first-table", [1, 1, 1, -1, 1], 0, 0),
+    ("negative-last", [1, 1, 1, 1, 1, 1, -5], 0, 0),
+    ("one-item-of-2^31-blocks", [1, G + 1], 0, 0),
+    ("two-items-of-2^31-1-blocks", [G, G], 0, 0),
+    ("sum-past-2^31-1-with-room-in-the-table", [G - 1, 1, 1], 0, 0),
+    ("second-launch-returns-7", [1, 2, 3, 4, 5, 6, 7], 2, 7),
+]
+
+
+@pytest.fixture(scope="module")
+def mt_driver(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("mt_driver")
+    src, exe = d / "driver.cpp", d / "driver"
+    src.write_text(MT_DRIVER)
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "egovlp_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror", "-I", csrc,
+                           str(src), "-o", str(exe)])
+    return str(exe)
+
+
+@pytest.mark.parametrize("case", MT_CASES, ids=[c[0] for c in MT_CASES])
+def test_mt_for_each_launch_follows_the_plan(mt_driver, case):
+    """mt_for_each_launch with a table of 3 items and a recording `launch`: the grid, the count, the item of every slot and the
+    blk_start row of every launch, and the result, equal R.mt_plan's -- an invalid item anywhere launches nothing."""
+    _, blocks, fail_at, fail_rc = case
+    run = subprocess.run([mt_driver, str(fail_at), str(fail_rc)] + [str(b) for b in blocks], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", (run.returncode, run.stderr)
+    result, launches = R.mt_plan(blocks, 3, [fail_rc if k + 1 == fail_at else 0 for k in range(fail_at)])
+    want = ["launch nb %d count %d items %s blk_start %s" % (nb, len(items), " ".join(map(str, items)), " ".join(map(str, starts)))
+            for nb, items, starts in launches] + ["result %d" % result]
+    assert run.stdout.splitlines() == want
+
+
+def test_mt_plan_on_cases_written_out_by_hand():
+    assert R.mt_plan([], 3) == (0, [])
+    assert R.mt_plan([0, 5, 0, 2], 3) == (0, [(7, [1, 3], [0, 5, 7])])
+    assert R.mt_plan([4, 1, 7, 2], 3) == (0, [(12, [0, 1, 2], [0, 4, 5, 12]), (2, [3], [0, 2])])
+    assert len(R.mt_plan([1] * 7, 3)[1]) == 3
+    assert R.mt_plan([1, 1, 1, -1], 3) == (1, []) and R.mt_plan([G + 1], 3) == (1, [])
+    assert R.mt_plan([G, G], 3) == (0, [(G, [0], [0, G]), (G, [1], [0, G])])
+    assert R.mt_plan([1] * 7, 3, [0, 7]) == (7, [(3, [0, 1, 2], [0, 1, 2, 3]), (3, [3, 4, 5], [0, 1, 2, 3])])

@@ -8,7 +8,8 @@ the whole step `egoclip_step` and the optimizer alone (`optimizer.step` on the g
 max_grad_norm off and on, in the benchmarked 'f16mix' / 'f16' mode (the model's loss scaler: the reduction rides on the scan) and in
 'bf16x3' / 'bf16' (no scaler: the reduction is one more read of the gradients).  One JSON line: median ms per leg, all rounds.
 (a) One child process per measurement, alternating parent, this tree, parent, ... (`rounds` times): the step rate with clipping off
-of both trees, and the spread between the parent's own runs -- the difference between the trees means something only beyond it."""
+of both trees and the optimizer alone (`optimizer.step` with the model's loss scaler, on the gradients the last backward left), and
+the spread between the parent's own runs -- the difference between the trees means something only beyond it."""
 import argparse
 import contextlib
 import json
@@ -52,7 +53,8 @@ def timed(torch, fn, n):
 
 
 def child(args):
-    """One tree, clipping off, the benchmarked mode: ms per step (median of `rounds` windows of `steps` steps)."""
+    """One tree, clipping off, the benchmarked mode: ms per step and per optimizer step alone (medians of `rounds` windows of `steps`
+    steps / 40 x `steps` optimizer steps: ~1 ms each, so that its window is no shorter)."""
     torch, m, ec, dev = build(args.root, ("f16mix", "f16"), args.batch, args.frames, args.text_dropout)
     from egovlp_amd.model.loss import EgoNCE
     from egovlp_amd.optim import AdamW
@@ -62,21 +64,31 @@ def child(args):
     for _ in range(3):
         step()
     ms = [timed(torch, step, args.steps) * 1e3 for _ in range(args.rounds)]
-    print(json.dumps({"root": args.root, "ms": round(statistics.median(ms), 3), "ms_rounds": [round(x, 3) for x in ms]}))
+    scaler = ec.loss_scaler(device="cuda") if ec.bwd_passes == 4 else None
+    opt_step = (lambda: opt.step(scaler=scaler)) if scaler is not None else opt.step
+    opt_ms = [timed(torch, opt_step, 40 * args.steps) * 1e3 for _ in range(args.rounds)]
+    print(json.dumps({"root": args.root, "ms": round(statistics.median(ms), 3), "ms_rounds": [round(x, 3) for x in ms],
+                      "optimizer_ms": round(statistics.median(opt_ms), 4), "optimizer_ms_rounds": [round(x, 4) for x in opt_ms]}))
 
 
 def against(args):
     runs = {"parent": [], "this": []}
+    opt = {"parent": [], "this": []}
     order = (["parent", "this"] * args.rounds) + ["parent"]
     for who in order:
         root = args.against if who == "parent" else HERE
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--batch", str(args.batch), "--frames",
                               str(args.frames), "--steps", str(args.steps), "--rounds", str(args.rounds), "--text-dropout",
                               str(args.text_dropout)], check=True, capture_output=True, text=True, timeout=600).stdout
-        runs[who].append(json.loads(out.strip().splitlines()[-1])["ms"])
+        line = json.loads(out.strip().splitlines()[-1])
+        runs[who].append(line["ms"])
+        opt[who].append(line["optimizer_ms"])
     p, t = runs["parent"], runs["this"]
     print(json.dumps({"batch": args.batch, "frames": args.frames, "precision": "f16mix/f16", "order": order, "parent_ms": p, "this_off_ms": t,
                       "parent_spread_ms": round(max(p) - min(p), 3), "this_minus_parent_ms": round(statistics.median(t) - statistics.median(p), 3),
+                      "parent_optimizer_ms": opt["parent"], "this_optimizer_ms": opt["this"],
+                      "parent_optimizer_spread_ms": round(max(opt["parent"]) - min(opt["parent"]), 4),
+                      "this_minus_parent_optimizer_ms": round(statistics.median(opt["this"]) - statistics.median(opt["parent"]), 4),
                       "parent_clip_pairs_per_s": round(args.batch / statistics.median(p) * 1e3, 2),
                       "this_off_clip_pairs_per_s": round(args.batch / statistics.median(t) * 1e3, 2)}))
 
