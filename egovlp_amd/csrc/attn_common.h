@@ -13,6 +13,9 @@
 // It is chosen so that the C-layout of a preceding 16x16 MFMA pair (rows 4g..4g+3 of two fragments) IS
 // the B operand of the next MFMA without any cross-lane movement.
 #pragma once
+#include <type_traits>
+
+#include "attn_dispatch.h"
 #include "common.h"
 #include "f16x2.h"
 
@@ -323,8 +326,54 @@ __device__ __forceinline__ float frag_dot8(bf16x8_t ah, bf16x8_t al, bool a_lo, 
 }
 
 
-// Key-tiled ("long") kernels for groups of more than 288 keys (attn_long.hip); `mode` is MODE_SPACE or MODE_TEXT.  They take over
-// where dispatch_fwd / dispatch_bwd of the LDS-resident kernels end and accept / reject the same precision combinations.
-int egv_attn_long_fwd(int mode, const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
-                      float* cls_ws, hipStream_t s);
-int egv_attn_long_bwd(int mode, const AttGeom& g, const AttGrad& gr, int ngroups, int passes, hipStream_t s);
+// ---- host: from a pick (attn_dispatch.h) to a launch ---------------------------------------------------------------------------
+// One launch of `kern` as `p` describes it.  The dynamic-LDS attribute is set per launch (it is per device).
+template <typename K, typename... Args>
+int att_launch(K kern, const AttPick& p, hipStream_t s, Args... args) {
+  if (p.lds) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+    if (e != hipSuccess) return EGV_ERR_LAUNCH + (int)e;
+  }
+  EGV_LAUNCH(kern, dim3(p.grid), dim3(p.threads), p.lds, s, args...);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+// f(N, PASSES, F16) as compile-time constants: N = the one of Ns that equals the pick's fragment count, (PASSES, F16) its (products,
+// fp16).  A kernel file names a kernel only under the `if constexpr` that lists the combinations it has (the others spill or have no
+// caller) and answers EGV_ERR_ARG for the rest.
+template <int... Ns, typename F>
+int att_instance(const AttPick& p, F f) {
+  using P1 = std::integral_constant<int, 1>;
+  using P3 = std::integral_constant<int, 3>;
+  int rc = EGV_ERR_ARG;
+  auto with_n = [&](auto n) {
+    if (p.products == 3) rc = p.f16 ? f(n, P3{}, std::true_type{}) : f(n, P3{}, std::false_type{});
+    if (p.products == 1) rc = p.f16 ? f(n, P1{}, std::true_type{}) : f(n, P1{}, std::false_type{});
+    return true;
+  };
+  (void)((p.frags == Ns && with_n(std::integral_constant<int, Ns>{})) || ...);
+  return rc;
+}
+
+// the geometry of a space call (the fused qkv planes) and of a text call (fp32 q / k / v, `ld` elements between tokens)
+inline AttGeom att_space_geom(const bf16_t* qkv_hi, const bf16_t* qkv_lo, int B, int T, int n, int H, int out_fmt, int f16) {
+  AttGeom g = {};
+  g.ph = qkv_hi; g.pl = qkv_lo;
+  g.tok_stride = 3L * H * ATT_D;
+  g.B = B; g.T = T; g.n = n; g.H = H; g.S = 1 + T * n;
+  g.nq = n; g.nk = n + 1;
+  g.drop = egv_make_drop(0.f, 0);
+  g.out_fmt = out_fmt; g.f16 = f16;
+  return g;
+}
+inline AttGeom att_text_geom(const float* q, const float* k, const float* v, int64_t ld, const int64_t* mask, int B, int L, int H,
+                             float dropout_p, uint64_t seed, const uint64_t* seed_dev) {
+  AttGeom g = {};
+  g.q = q; g.k = k; g.v = v;
+  g.tok_stride = ld;
+  g.B = B; g.T = 1; g.n = L; g.H = H; g.S = L;
+  g.nq = L; g.nk = L;
+  g.mask = (const long long*)mask;
+  g.drop = egv_make_drop(dropout_p, seed, seed_dev);
+  return g;
+}

@@ -29,19 +29,21 @@
 // from L2: a group's planes are 0.3 - 0.4 MB and its blocks are neighbours in the grid.
 //
 // Every (passes, f16, out_fmt) / (passes, o_fmt, g_fmt, f16) / text (passes, dropout) combination of the short path is accepted
-// and the same ones are rejected; operand loading, the fp16 split and the output formats are those of attn_common.h.  The text
-// mode's dropout mask is the counter-based one of common.h at the ABSOLUTE element index ((b H + h) S + q) S + k.
+// and the same ones are rejected (one check serves both: attn_dispatch.h); operand loading, the fp16 split and the output formats
+// are those of attn_common.h.  The text mode's dropout mask is the counter-based one of common.h at the ABSOLUTE element index
+// ((b H + h) S + q) S + k.
 #include "attn_common.h"
 #include "egovlp_hip.h"
 
 namespace {
 
-constexpr int LONG_ROWS = 64;                                // rows (keys; queries in dK / dV) per LDS tile
-constexpr int LONG_WAVES = 8;                                // waves per workgroup: 128 queries (keys in dK / dV) per block
+constexpr int LONG_ROWS = ATT_TILE_ROWS;                     // rows (keys; queries in dK / dV) per LDS tile
+constexpr int LONG_WAVES = ATT_TILE_WAVES;                   // waves per workgroup: 128 queries (keys in dK / dV) per block
 constexpr int LONG_PLANE = LONG_ROWS * ATT_ROW_BYTES;        // 8 KiB
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 constexpr int long_buf_bytes(int passes, int nvec) { return (passes == 3 ? 4 : 2) * LONG_PLANE + nvec * LONG_ROWS * (int)sizeof(float); }
+static_assert(2 * long_buf_bytes(3, 2) == att_tiled_lds(3, 2) && 2 * long_buf_bytes(1, 1) == att_tiled_lds(1, 1), "the ring the picks ask for");
 
 // waves per SIMD the instances are compiled for: 4 (two 8-wave workgroups per CU, <= 128 VGPRs).  The three-product TEXT instances
 // (fp32 sources split in registers, 64-bit dropout indices) need 134 / 142 VGPRs and would spill under that bound: they keep 3,
@@ -529,72 +531,37 @@ __global__ __launch_bounds__(LONG_WAVES * 64, long_min_waves(MODE, PASSES)) void
   }
 }
 
-// blocks of 128 rows per group; the grid is one-dimensional (groups x blocks)
-inline bool long_grid(int ngroups, int rows, int& nblk, unsigned& grid) {
-  nblk = (rows + LONG_WAVES * 16 - 1) / (LONG_WAVES * 16);
-  const long long total = (long long)ngroups * nblk;
-  if (ngroups <= 0 || total > 0x7fffffffLL) return false;
-  grid = (unsigned)total;
-  return true;
-}
-
-template <int MODE, int PASSES, bool F16>
-int launch_long_fwd(const AttGeom& g, int ngroups, bf16_t* oh, bf16_t* ol, long ostride, float* lse, float* cls_ws, hipStream_t s) {
-  int nqb;
-  unsigned grid;
-  if (!long_grid(ngroups, MODE == MODE_SPACE ? g.nq + 1 : g.nq, nqb, grid)) return EGV_ERR_ARG;
-  constexpr int lds = 2 * long_buf_bytes(PASSES, 1);
-  auto kern = attn_long_fwd_kernel<MODE, PASSES, F16>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  EGV_LAUNCH(kern, dim3(grid), dim3(LONG_WAVES * 64), lds, s, g, oh, ol, ostride, lse, cls_ws, nqb);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
-template <int MODE, int PASSES, bool F16>
-int launch_long_bwd(const AttGeom& g, const AttGrad& gr, int ngroups, hipStream_t s) {
-  int nqb, nkb;
-  unsigned grid1, grid2;
-  if (!long_grid(ngroups, MODE == MODE_SPACE ? g.nq + 1 : g.nq, nqb, grid1) || !long_grid(ngroups, g.nk, nkb, grid2)) return EGV_ERR_ARG;
-  constexpr int lds1 = 2 * long_buf_bytes(PASSES, 1), lds2 = 2 * long_buf_bytes(PASSES, 2);
-  auto k1 = attn_long_dq_kernel<MODE, PASSES, F16>;
-  auto k2 = attn_long_dkv_kernel<MODE, PASSES, F16>;
-  (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-  (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-  EGV_LAUNCH(k1, dim3(grid1), dim3(LONG_WAVES * 64), lds1, s, g, gr, nqb);
-  EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(k2, dim3(grid2), dim3(LONG_WAVES * 64), lds2, s, g, gr, nkb);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
 }  // namespace
 
-// The accepted combinations are those of launch_fwd / launch_bwd for the 197- and 257-key sizes (attn_mfma_fwd.hip, attn_mfma_bwd.hip).
-int egv_attn_long_fwd(int mode, const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
-                      float* cls_ws, hipStream_t s) {
-  if (mode == MODE_SPACE) {
-    if (passes == 3) {
-      if (ol == nullptr && g.out_fmt != ATT_OUT_F16) return EGV_ERR_ARG;      // a missing second plane is an argument error
-      if (g.f16) return launch_long_fwd<MODE_SPACE, 3, true>(g, ngroups, oh, ol, ostride, lse, cls_ws, s);
-      return launch_long_fwd<MODE_SPACE, 3, false>(g, ngroups, oh, ol, ostride, lse, cls_ws, s);
-    }
-    if (g.f16) return EGV_ERR_ARG;                    // the fp16 forward is the three-product one
-    return launch_long_fwd<MODE_SPACE, 1, false>(g, ngroups, oh, nullptr, ostride, lse, cls_ws, s);
-  }
-  if (mode != MODE_TEXT) return EGV_ERR_ARG;
-  if (passes == 3) return launch_long_fwd<MODE_TEXT, 3, false>(g, ngroups, oh, ol, ostride, lse, cls_ws, s);
-  return launch_long_fwd<MODE_TEXT, 1, false>(g, ngroups, oh, nullptr, ostride, lse, cls_ws, s);
+// The picks (attn_dispatch.h) carry the blocks of 128 rows per group -- a kernel argument -- and the one-dimensional grid groups x
+// blocks.  fp16 operands exist in the space instances the LDS-resident path has them in: three-product forward, one-product backward.
+int egv_attn_long_fwd(int mode, const AttPick& p, const AttGeom& g, bf16_t* oh, bf16_t* ol, long ostride, float* lse, float* cls_ws,
+                      hipStream_t s) {
+  return att_instance<0>(p, [&](auto, auto passes, auto f16) -> int {
+    constexpr int PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 3)
+      if (mode == MODE_SPACE) return att_launch(attn_long_fwd_kernel<MODE_SPACE, PASSES, F16>, p, s, g, oh, ol, ostride, lse, cls_ws, p.nblk);
+    if constexpr (!F16)
+      if (mode == MODE_TEXT) return att_launch(attn_long_fwd_kernel<MODE_TEXT, PASSES, false>, p, s, g, oh, ol, ostride, lse, cls_ws, p.nblk);
+    return EGV_ERR_ARG;
+  });
 }
 
-int egv_attn_long_bwd(int mode, const AttGeom& g, const AttGrad& gr, int ngroups, int passes, hipStream_t s) {
-  if (mode == MODE_SPACE) {
-    if (gr.oh == nullptr) return EGV_ERR_ARG;         // delta = rowsum(dO o O) is taken from the forward's output planes
-    if (passes == 3) return launch_long_bwd<MODE_SPACE, 3, false>(g, gr, ngroups, s);
-    if (g.f16) return launch_long_bwd<MODE_SPACE, 1, true>(g, gr, ngroups, s);
-    return launch_long_bwd<MODE_SPACE, 1, false>(g, gr, ngroups, s);
-  }
-  if (mode != MODE_TEXT) return EGV_ERR_ARG;
-  if (passes == 3) return launch_long_bwd<MODE_TEXT, 3, false>(g, gr, ngroups, s);
-  return launch_long_bwd<MODE_TEXT, 1, false>(g, gr, ngroups, s);
+int egv_attn_long_bwd(int mode, const AttPick& dq, const AttPick& dkv, const AttGeom& g, const AttGrad& gr, hipStream_t s) {
+  return att_instance<0>(dq, [&](auto, auto passes, auto f16) -> int {
+    constexpr int PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 1)
+      if (mode == MODE_SPACE) {
+        const int rc = att_launch(attn_long_dq_kernel<MODE_SPACE, PASSES, F16>, dq, s, g, gr, dq.nblk);
+        return rc ? rc : att_launch(attn_long_dkv_kernel<MODE_SPACE, PASSES, F16>, dkv, s, g, gr, dkv.nblk);
+      }
+    if constexpr (!F16)
+      if (mode == MODE_TEXT) {
+        const int rc = att_launch(attn_long_dq_kernel<MODE_TEXT, PASSES, false>, dq, s, g, gr, dq.nblk);
+        return rc ? rc : att_launch(attn_long_dkv_kernel<MODE_TEXT, PASSES, false>, dkv, s, g, gr, dkv.nblk);
+      }
+    return EGV_ERR_ARG;
+  });
 }

@@ -564,170 +564,62 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const AttGeom g, cons
   }
 }
 
-template <int MODE, int NF>
-int launch_bwd(const AttGeom& g, const AttGrad& gr, int ngroups, int passes, hipStream_t s) {
-  const int planes = passes == 3 ? 4 : 2;
-  const size_t lds = (size_t)planes * NF * 16 * ATT_ROW_BYTES + 2 * NF * 16 * sizeof(float);
-#ifndef EGV_BWD_STREAM18
-#define EGV_BWD_STREAM18 1      // ViT-L/14's 257-key groups on the streaming dQ kernel as well: the register-resident attn_bwd_dq_kernel<0,18,3>
-#endif                          // spills 51 VGPRs (the all-bf16x3 parity mode of config 5 dispatched it); 0: A/B builds
-  if constexpr (MODE == MODE_SPACE && (NF == 14 || (NF == 18 && EGV_BWD_STREAM18))) {     // streaming dQ kernel (measured on ViT-B/16), then the dK/dV kernel
-    if (gr.oh == nullptr) return EGV_ERR_ARG;          // delta = rowsum(dO o O) is taken from the forward's output planes
-    {
-      const size_t lds1 = (size_t)planes * NF * 16 * ATT_ROW_BYTES + NF * 16 * sizeof(float);
-      if (passes == 3) {
-        auto k1 = attn_bwd_dq_stream_kernel<NF, 3>;
-        auto k2 = attn_bwd_dkv_kernel<MODE, NF, 3>;
-        (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        EGV_LAUNCH(k1, dim3(ngroups), dim3(1024), lds1, s, g, gr);
-        EGV_CHECK_LAUNCH();
-        EGV_LAUNCH(k2, dim3(ngroups), dim3(256), lds, s, g, gr);
-      } else if (g.f16) {
-        auto k1 = attn_bwd_dq_stream_kernel<NF, 1, true>;
-        auto k2 = attn_bwd_dkv_kernel<MODE, NF, 1, true>;
-        (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        EGV_LAUNCH(k1, dim3(ngroups), dim3(512), lds1, s, g, gr);
-        EGV_CHECK_LAUNCH();
-        EGV_LAUNCH(k2, dim3(ngroups), dim3(512), lds, s, g, gr);
-      } else {
-        auto k1 = attn_bwd_dq_stream_kernel<NF, 1>;
-        auto k2 = attn_bwd_dkv_kernel<MODE, NF, 1>;
-        (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        EGV_LAUNCH(k1, dim3(ngroups), dim3(512), lds1, s, g, gr);
-        EGV_CHECK_LAUNCH();
-        EGV_LAUNCH(k2, dim3(ngroups), dim3(512), lds, s, g, gr);
-      }
-      EGV_CHECK_LAUNCH();
-      return EGV_OK;
-    }
-  } else if constexpr (MODE == MODE_TEXT && (NF == 14 || NF == 18)) {     // captions of 65 .. 288 tokens: two-pass streaming dQ, then dK / dV
-    if (passes == 3) {
-      auto k1 = attn_bwd_dq_text_stream_kernel<NF, 3>;
-      auto k2 = attn_bwd_dkv_kernel<MODE, NF, 3>;
-      (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      EGV_LAUNCH(k1, dim3(ngroups), dim3(512), lds, s, g, gr);
-      EGV_CHECK_LAUNCH();
-      EGV_LAUNCH(k2, dim3(ngroups), dim3(256), lds, s, g, gr);
-    } else {
-      auto k1 = attn_bwd_dq_text_stream_kernel<NF, 1>;
-      auto k2 = attn_bwd_dkv_kernel<MODE, NF, 1>;
-      (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      EGV_LAUNCH(k1, dim3(ngroups), dim3(512), lds, s, g, gr);
-      EGV_CHECK_LAUNCH();
-      EGV_LAUNCH(k2, dim3(ngroups), dim3(512), lds, s, g, gr);
-    }
-    EGV_CHECK_LAUNCH();
-    return EGV_OK;
-  } else {        // (else-branch of the if constexpr: the register-resident dQ kernel is not even instantiated for the streamed sizes)
-  if (passes == 3) {
-    auto k1 = attn_bwd_dq_kernel<MODE, NF, 3>;
-    auto k2 = attn_bwd_dkv_kernel<MODE, NF, 3>;
-    (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    EGV_LAUNCH(k1, dim3(ngroups), dim3(256), lds, s, g, gr);
-    EGV_CHECK_LAUNCH();
-    EGV_LAUNCH(k2, dim3(ngroups), dim3(256), lds, s, g, gr);
-  } else if (MODE == MODE_SPACE && g.f16) {
-    if constexpr (MODE == MODE_SPACE) {
-      auto k1 = attn_bwd_dq_kernel<MODE, NF, 1, true>;
-      auto k2 = attn_bwd_dkv_kernel<MODE, NF, 1, true>;
-      (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      EGV_LAUNCH(k1, dim3(ngroups), dim3(512), lds, s, g, gr);
-      EGV_CHECK_LAUNCH();
-      EGV_LAUNCH(k2, dim3(ngroups), dim3(512), lds, s, g, gr);
-    }
-  } else {
-    auto k1 = attn_bwd_dq_kernel<MODE, NF, 1>;
-    auto k2 = attn_bwd_dkv_kernel<MODE, NF, 1>;
-    (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    constexpr int nthr = 512;   // 8 waves per group
-    EGV_LAUNCH(k1, dim3(ngroups), dim3(nthr), lds, s, g, gr);
-    EGV_CHECK_LAUNCH();
-    EGV_LAUNCH(k2, dim3(ngroups), dim3(nthr), lds, s, g, gr);
-  }
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-  }
-}
-
+// Two picks (attn_dispatch.h att_pick_dq / att_pick_dkv: one fragment count) to the dQ kernel, then the dK / dV kernel.  Space at 14 / 18
+// fragments: the streaming dQ kernel (delta = rowsum(dO o O) from the forward's output planes); text there: the two-walk streaming dQ;
+// the register-resident dQ kernel is not instantiated for those sizes (it spills), nor are fp16 operands outside the one-product space
+// backward.
 template <int MODE>
-int dispatch_bwd(const AttGeom& g, const AttGrad& gr, int ngroups, int passes, hipStream_t s) {
-  const int nq_all = (MODE == MODE_SPACE) ? g.nq + 1 : g.nq;
-  const int m = g.nk > nq_all ? g.nk : nq_all;  // one fragment count covers both the key and the query extent
-  if (m <= 32) return launch_bwd<MODE, 2>(g, gr, ngroups, passes, s);
-  if (m <= 64) return launch_bwd<MODE, 4>(g, gr, ngroups, passes, s);
-  if (m <= 224) return launch_bwd<MODE, 14>(g, gr, ngroups, passes, s);
-  if (m <= 288) return launch_bwd<MODE, 18>(g, gr, ngroups, passes, s);
-  return egv_attn_long_bwd(MODE, g, gr, ngroups, passes, s);      // key- and query-tiled kernels (attn_long.hip): no upper bound
+int launch_bwd(const AttPick& dq, const AttPick& dkv, const AttGeom& g, const AttGrad& gr, hipStream_t s) {
+  if (dq.family == ATT_KEY_TILED) return egv_attn_long_bwd(MODE, dq, dkv, g, gr, s);
+  return att_instance<2, 4, 14, 18>(dq, [&](auto nf, auto passes, auto f16) -> int {
+    constexpr int NF = nf, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (F16 && (MODE != MODE_SPACE || PASSES != 1)) {
+      return EGV_ERR_ARG;
+    } else {
+      int rc;
+      if constexpr (NF >= 14 && MODE == MODE_SPACE) rc = att_launch(attn_bwd_dq_stream_kernel<NF, PASSES, F16>, dq, s, g, gr);
+      else if constexpr (NF >= 14) rc = att_launch(attn_bwd_dq_text_stream_kernel<NF, PASSES>, dq, s, g, gr);
+      else rc = att_launch(attn_bwd_dq_kernel<MODE, NF, PASSES, F16>, dq, s, g, gr);
+      return rc ? rc : att_launch(attn_bwd_dkv_kernel<MODE, NF, PASSES, F16>, dkv, s, g, gr);
+    }
+  });
 }
 
 }  // namespace
 
-int egv_attn_space_bwd_impl(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* out_hi, const bf16_t* out_lo,
-                            const bf16_t* do_hi, const bf16_t* do_lo,
-                            const float* lse, float* delta, float* dcls, int B, int T, int n, int H, int passes,
-                            bf16_t* dqkv_hi, bf16_t* dqkv_lo, int o_fmt, int g_fmt, int f16, hipStream_t s) {
-  AttGeom g;
+int egv_attn_space_bwd_impl(const AttPick& dq, const AttPick& dkv, const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* out_hi,
+                            const bf16_t* out_lo, const bf16_t* do_hi, const bf16_t* do_lo, const float* lse, float* delta, float* dcls,
+                            int B, int T, int n, int H, bf16_t* dqkv_hi, bf16_t* dqkv_lo, int o_fmt, int g_fmt, hipStream_t s) {
   const long HD = (long)H * ATT_D;
-  g.q = g.k = g.v = nullptr;
-  g.ph = qkv_hi;
-  g.pl = (passes == 3) ? qkv_lo : nullptr;
-  g.tok_stride = 3 * HD;
-  g.B = B; g.T = T; g.n = n; g.H = H; g.S = 1 + T * n;
-  g.nq = n; g.nk = n + 1;
-  g.mask = nullptr;
-  g.drop = egv_make_drop(0.f, 0);
-  g.out_fmt = 0;
-  g.f16 = f16;
-  if (f16 && passes != 1) return EGV_ERR_ARG;
-  AttGrad gr;
-  gr.dq = gr.dk = gr.dv = nullptr;
-  gr.gh = dqkv_hi;
-  gr.gl = (passes == 3) ? dqkv_lo : nullptr;
+  const AttGeom g = att_space_geom(qkv_hi, qkv_lo, B, T, n, H, 0, dq.f16);
+  AttGrad gr = {};
+  gr.gh = dqkv_hi; gr.gl = dqkv_lo;
   gr.tok_stride = 3 * HD;
-  gr.d_out = nullptr;
-  gr.doh = do_hi;
-  gr.dol = (passes == 3) ? do_lo : nullptr;
+  gr.doh = do_hi; gr.dol = do_lo;
   gr.do_stride = HD;
   gr.oh = out_hi; gr.ol = out_lo;                   // [B*S, H*64] planes, same row stride as d_out
   gr.lse = lse; gr.delta = delta; gr.dcls = dcls;
   gr.o_fmt = o_fmt; gr.g_fmt = g_fmt;
-  return dispatch_bwd<MODE_SPACE>(g, gr, B * T * H, passes, s);
+  return launch_bwd<MODE_SPACE>(dq, dkv, g, gr, s);
 }
 
 extern "C" int egv_text_attn_bwd(const float* q, const float* k, const float* v, int64_t ldqkv, const int64_t* mask,
                                  const float* d_out, const float* lse, int32_t B, int32_t L, int32_t H, int32_t passes,
                                  float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dq, float* dk, float* dv,
                                  int64_t lddqkv, float* delta_work, void* stream) {
-  if (!q || !k || !v || !mask || !d_out || !lse || !dq || !dk || !dv || !delta_work) return EGV_ERR_ARG;
-  if (passes != 1 && passes != 3) return EGV_ERR_ARG;
-  AttGeom g;
-  const long HD = (long)H * ATT_D;
-  g.q = q; g.k = k; g.v = v;
-  g.ph = g.pl = nullptr;
-  g.tok_stride = ldqkv;
-  g.B = B; g.T = 1; g.n = L; g.H = H; g.S = L;
-  g.nq = L; g.nk = L;
-  g.mask = (const long long*)mask;
-  if (ldqkv < HD || lddqkv < HD || ldqkv % 4 != 0 || lddqkv % 4 != 0) return EGV_ERR_ARG;
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return EGV_ERR_ARG;
-  g.drop = egv_make_drop(dropout_p, seed, seed_dev);      // the (p, seed, device seed words) of the matching egv_text_attn_fwd call
-  g.out_fmt = 0;
-  g.f16 = 0;
-  AttGrad gr;
+  AttPick pq, pkv;
+  if (att_check_text_bwd(B, L, H, passes, q && k && v && mask && d_out && lse && dq && dk && dv && delta_work, ldqkv, lddqkv, dropout_p))
+    return EGV_ERR_ARG;
+  if (att_pick_dq(false, (int64_t)B * H, L, L, passes, 0, &pq) || att_pick_dkv(false, (int64_t)B * H, L, L, passes, 0, &pkv))
+    return EGV_ERR_ARG;
+  // the (p, seed, device seed words) of the matching egv_text_attn_fwd call
+  const AttGeom g = att_text_geom(q, k, v, ldqkv, mask, B, L, H, dropout_p, seed, seed_dev);
+  AttGrad gr = {};
   gr.dq = dq; gr.dk = dk; gr.dv = dv;
-  gr.gh = gr.gl = nullptr;
   gr.tok_stride = lddqkv;
-  gr.d_out = d_out; gr.doh = gr.dol = nullptr; gr.do_stride = HD;
-  gr.oh = gr.ol = nullptr;
-  gr.lse = lse; gr.delta = delta_work; gr.dcls = nullptr;
-  gr.o_fmt = 0; gr.g_fmt = 0;
-  return dispatch_bwd<MODE_TEXT>(g, gr, B * H, passes, (hipStream_t)stream);
+  gr.d_out = d_out;
+  gr.do_stride = (long)H * ATT_D;
+  gr.lse = lse; gr.delta = delta_work;
+  return launch_bwd<MODE_TEXT>(pq, pkv, g, gr, (hipStream_t)stream);
 }

@@ -10,7 +10,6 @@
 // operand of O^T = V^T.P^T -- V^T fragments come from the row-major V image through the CDNA4
 // transpose read.  q/k/v are read directly out of the fused qkv buffer with index arithmetic; none
 // of the reference's rearrange / repeat / cat copies exist.
-#include <cstdlib>
 #include <type_traits>
 
 #include "attn_common.h"
@@ -471,116 +470,39 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream3_kernel(const AttGeom g,
   }
 }
 
-template <int MODE, int NKF>
-int launch_fwd(const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
-               float* cls_ws, hipStream_t s) {
-  const int planes = passes == 3 ? 4 : 2;
-  const size_t lds = (size_t)planes * NKF * 16 * ATT_ROW_BYTES + NKF * 16 * sizeof(float);
-#ifndef EGV_STREAM18
-#define EGV_STREAM18 1      // the streaming kernel for ViT-L/14's 257-key groups as well (17 query tiles on 16 waves: two rounds, and still
-#endif                      // +0.25 % on config 5 against attn_fwd_kernel<0,18,3>: 234.6 vs 234.0 pairs/s, profiles/r05e_ab_config5_stream18.txt; 0: A/B builds
-  if constexpr (MODE == MODE_SPACE && (NKF == 14 || (NKF == 18 && EGV_STREAM18))) {   // measured on ViT-B/16 (13 query tiles on 16 waves): 137 -> 130 us
-    if (passes == 3 && (ol != nullptr || g.out_fmt == ATT_OUT_F16)) {
-      // persistent: one 16-wave workgroup per CU (115 / 148 KiB of LDS); EGV_ATTN_PERSIST=0 restores one workgroup per group (A/B)
-      static const int persist = getenv("EGV_ATTN_PERSIST") ? atoi(getenv("EGV_ATTN_PERSIST")) : 1;
-      const int grid = persist ? (ngroups < 256 ? ngroups : 256) : ngroups;
-      if (g.f16) {
-        auto kern = attn_fwd_stream3_kernel<NKF, true>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        EGV_LAUNCH(kern, dim3(grid), dim3(1024), lds, s, g, oh, ol, ostride, lse, cls_ws, ngroups);
-      } else {
-        auto kern = attn_fwd_stream3_kernel<NKF>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        EGV_LAUNCH(kern, dim3(grid), dim3(1024), lds, s, g, oh, ol, ostride, lse, cls_ws, ngroups);
-      }
-      EGV_CHECK_LAUNCH();
-      return EGV_OK;
-    }
-    // a three-pass space forward of these sizes ALWAYS runs the streaming kernel (a missing second plane is an argument error): the
-    // register-resident attn_fwd_kernel<0, 14, 3> spills and is not instantiated for them
-    if (passes == 3) return EGV_ERR_ARG;
-    {
-      auto kern = attn_fwd_kernel<MODE, NKF, 1>;
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      EGV_LAUNCH(kern, dim3(ngroups), dim3(512), lds, s, g, oh, nullptr, ostride, lse, cls_ws);
-      EGV_CHECK_LAUNCH();
-      return EGV_OK;
-    }
-  } else {
-  if (MODE == MODE_SPACE && g.f16) {
-    if (passes != 3) return EGV_ERR_ARG;              // the fp16 forward is the three-product one
-    if constexpr (MODE == MODE_SPACE) {
-      auto kern = attn_fwd_kernel<MODE, NKF, 3, true>;
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      EGV_LAUNCH(kern, dim3(ngroups), dim3(512), lds, s, g, oh, ol, ostride, lse, cls_ws);
-    }
-  } else if (passes == 3) {
-    auto kern = attn_fwd_kernel<MODE, NKF, 3>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    // three-pass mode keeps four K/V planes in LDS (115 KiB: one workgroup per CU), so it runs 8 waves per workgroup to have
-    // two waves per SIMD; the single-pass kernel fits two 4-wave workgroups per CU
-    EGV_LAUNCH(kern, dim3(ngroups), dim3(512), lds, s, g, oh, ol, ostride, lse, cls_ws);
-  } else {
-    auto kern = attn_fwd_kernel<MODE, NKF, 1>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    constexpr int nthr = 512;
-    EGV_LAUNCH(kern, dim3(ngroups), dim3(nthr), lds, s, g, oh, nullptr, ostride, lse, cls_ws);
-  }
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-  }
+// A pick (attn_dispatch.h att_pick_fwd) to its instance.  Not instantiated, on purpose: the register-resident three-product space
+// kernel at 14 / 18 fragments (it spills: those sizes stream) and fp16 operands outside the three-product space forward.
+template <int MODE>
+int launch_fwd(const AttPick& p, const AttGeom& g, int ngroups, bf16_t* oh, bf16_t* ol, long ostride, float* lse, float* cls_ws,
+               hipStream_t s) {
+  if (p.family == ATT_KEY_TILED) return egv_attn_long_fwd(MODE, p, g, oh, ol, ostride, lse, cls_ws, s);
+  return att_instance<2, 4, 14, 18>(p, [&](auto nkf, auto passes, auto f16) -> int {
+    constexpr int NKF = nkf, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (MODE == MODE_SPACE && NKF >= 14 && PASSES == 3)
+      return att_launch(attn_fwd_stream3_kernel<NKF, F16>, p, s, g, oh, ol, ostride, lse, cls_ws, ngroups);
+    else if constexpr (!F16 || (MODE == MODE_SPACE && PASSES == 3))
+      return att_launch(attn_fwd_kernel<MODE, NKF, PASSES, F16>, p, s, g, oh, ol, ostride, lse, cls_ws);
+    else
+      return EGV_ERR_ARG;
+  });
 }
 
 }  // namespace
 
-// dispatch on the padded key count (NKF 16-key fragments, even): 2 (<=32 keys: DistilBERT L<=32 and the
-// tiny test configs), 4, 14 (ViT-B/16: 197 keys), 18 (ViT-L/14: 257 keys); more than 288 keys (higher input resolutions, long captions)
-// go to the key-tiled online-softmax kernel of attn_long.hip
-template <int MODE>
-static int dispatch_fwd(const AttGeom& g, int ngroups, int passes, bf16_t* oh, bf16_t* ol, long ostride, float* lse,
-                        float* cls_ws, hipStream_t s) {
-  if (g.nk <= 32) return launch_fwd<MODE, 2>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
-  if (g.nk <= 64) return launch_fwd<MODE, 4>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
-  if (g.nk <= 224) return launch_fwd<MODE, 14>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
-  if (g.nk <= 288) return launch_fwd<MODE, 18>(g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);
-  return egv_attn_long_fwd(MODE, g, ngroups, passes, oh, ol, ostride, lse, cls_ws, s);      // key-tiled kernel (attn_long.hip): no upper bound
-}
-
-int egv_attn_space_fwd_impl(const bf16_t* qkv_hi, const bf16_t* qkv_lo, int B, int T, int n, int H, int passes,
-                            bf16_t* out_hi, bf16_t* out_lo, float* lse, float* cls_ws, int out_fmt, int f16, hipStream_t s) {
-  AttGeom g;
-  g.out_fmt = out_fmt;
-  g.f16 = f16;
-  const long HD = (long)H * ATT_D;
-  g.q = g.k = g.v = nullptr;
-  g.ph = qkv_hi;
-  g.pl = (passes == 3) ? qkv_lo : nullptr;
-  g.tok_stride = 3 * HD;
-  g.B = B; g.T = T; g.n = n; g.H = H; g.S = 1 + T * n;
-  g.nq = n; g.nk = n + 1;
-  g.mask = nullptr;
-  g.drop = egv_make_drop(0.f, 0);
-  return dispatch_fwd<MODE_SPACE>(g, B * T * H, passes, out_hi, out_lo, HD, lse, cls_ws, s);
+int egv_attn_space_fwd_impl(const AttPick& p, const bf16_t* qkv_hi, const bf16_t* qkv_lo, int B, int T, int n, int H, bf16_t* out_hi,
+                            bf16_t* out_lo, float* lse, float* cls_ws, int out_fmt, hipStream_t s) {
+  const AttGeom g = att_space_geom(qkv_hi, qkv_lo, B, T, n, H, out_fmt, p.f16);
+  return launch_fwd<MODE_SPACE>(p, g, B * T * H, out_hi, out_lo, (long)H * ATT_D, lse, cls_ws, s);
 }
 
 extern "C" int egv_text_attn_fwd(const float* q, const float* k, const float* v, int64_t ldqkv, const int64_t* mask,
                                  int32_t B, int32_t L, int32_t H, int32_t passes, float dropout_p, uint64_t seed,
                                  const uint64_t* seed_dev, egv_bf16* out_hi, egv_bf16* out_lo, float* lse, void* stream) {
-  if (!q || !k || !v || !out_hi || B <= 0 || L <= 0 || H <= 0) return EGV_ERR_ARG;
-  if (passes != 1 && passes != 3) return EGV_ERR_ARG;
-  if (passes == 3 && !out_lo) return EGV_ERR_ARG;
-  AttGeom g;
-  g.out_fmt = 0;
-  g.f16 = 0;
-  const long HD = (long)H * ATT_D;
-  g.q = q; g.k = k; g.v = v;
-  g.ph = g.pl = nullptr;
-  g.tok_stride = ldqkv;
-  g.B = B; g.T = 1; g.n = L; g.H = H; g.S = L;
-  g.nq = L; g.nk = L;
-  g.mask = (const long long*)mask;
-  if (!mask || ldqkv < HD || ldqkv % 4 != 0) return EGV_ERR_ARG;
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return EGV_ERR_ARG;
-  g.drop = egv_make_drop(dropout_p, seed, seed_dev);
-  return dispatch_fwd<MODE_TEXT>(g, B * H, passes, out_hi, out_lo, HD, lse, nullptr, (hipStream_t)stream);
+  bool has_lo = out_lo != nullptr;
+  AttPick p;
+  if (att_check_text_fwd(B, L, H, passes, q && k && v && mask && out_hi, &has_lo, ldqkv, dropout_p)) return EGV_ERR_ARG;
+  if (att_pick_fwd(false, (int64_t)B * H, L, L, passes, 0, &p)) return EGV_ERR_ARG;
+  const AttGeom g = att_text_geom(q, k, v, ldqkv, mask, B, L, H, dropout_p, seed, seed_dev);
+  return launch_fwd<MODE_TEXT>(p, g, B * H, out_hi, has_lo ? out_lo : nullptr, (long)H * ATT_D, lse, nullptr, (hipStream_t)stream);
 }

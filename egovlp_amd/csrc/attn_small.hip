@@ -6,6 +6,7 @@
 // planes.  Only the CLS token's own gradients (shared by all groups of a clip) go through fp32 atomics + egv_attn_cls_finish.
 // (Rounds 1 - 3 also had the vector-ALU time-attention kernels in this file; they lost to the matrix-core kernels at every T --
 // T = 4 in-step: 835 -> 846 pairs/s, profiles/r04n_* -- and were removed in round 4.)
+#include "attn_dispatch.h"
 #include "common.h"
 #include "f16x2.h"
 #include "egovlp_hip.h"
@@ -117,31 +118,6 @@ __global__ __launch_bounds__(64) void attn_cls_finish_kernel(const float* __rest
 }
 
 }  // namespace
-
-int egv_attn_time_mfma_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse,
-                                float* ws, int out_fmt, int f16, hipStream_t s);
-int egv_attn_time_mfma_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
-                                const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s);
-// 16 < T <= 64: attn_time_long.hip
-int egv_attn_time_long_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse,
-                                float* ws, int out_fmt, int f16, hipStream_t s);
-int egv_attn_time_long_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
-                                const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s);
-
-int egv_attn_time_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol,
-                           float* lse, float* ws, int out_fmt, int f16, hipStream_t s) {
-  if (T > 64) return EGV_ERR_ARG;
-  if (T > 16) return egv_attn_time_long_fwd_impl(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-  return egv_attn_time_mfma_fwd_impl(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-}
-
-int egv_attn_time_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
-                           const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16,
-                           hipStream_t s) {
-  if (T > 64) return EGV_ERR_ARG;
-  if (T > 16) return egv_attn_time_long_bwd_impl(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-  return egv_attn_time_mfma_bwd_impl(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-}
 
 int egv_attn_cls_combine_impl(const float* ws, int B, int G, int S, int H, bf16_t* oh, bf16_t* ol, float* lse, int out_fmt,
                               hipStream_t s) {

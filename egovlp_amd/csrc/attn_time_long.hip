@@ -495,51 +495,29 @@ __global__ __launch_bounds__(64 * NT) void attn_time_long_bwd_kernel(const bf16_
   for (int x = threadIdx.x; x < 192; x += 64 * NT) atomicAdd(dcls + ((long)b * H + h) * 192 + x, red[x]);
 }
 
-template <int NT>
-int launch_fwd(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse, float* ws, int out_fmt,
-               int f16, hipStream_t s) {
-  const dim3 grid((unsigned)((long)B * n * H)), block(64 * NT);
-  if (f16) {
-    if (!ql) return EGV_ERR_ARG;        // the fp16 forward is the three-product one
-    EGV_LAUNCH((attn_time_long_fwd_kernel<3, NT, true>), grid, block, 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt);
-  } else if (ql)
-    EGV_LAUNCH((attn_time_long_fwd_kernel<3, NT>), grid, block, 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt);
-  else
-    EGV_LAUNCH((attn_time_long_fwd_kernel<1, NT>), grid, block, 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, 0);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
-template <int NT>
-int launch_bwd(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse, const float* delta, int B, int T,
-               int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s) {
-  const dim3 grid((unsigned)((long)B * n * H)), block(64 * NT);
-  if (f16)
-    EGV_LAUNCH((attn_time_long_bwd_kernel<1, NT, true>), grid, block, 0, s, qh, nullptr, doh, nullptr, lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  else if (ql && dol)
-    EGV_LAUNCH((attn_time_long_bwd_kernel<3, NT>), grid, block, 0, s, qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  else
-    EGV_LAUNCH((attn_time_long_bwd_kernel<1, NT>), grid, block, 0, s, qh, nullptr, doh, nullptr, lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
 }  // namespace
 
-// 16 < T <= 64 (the callers check): NT = ceil(T / 16) tiles per location, one workgroup of NT waves per (clip, location, head)
-int egv_attn_time_long_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse,
-                                float* ws, int out_fmt, int f16, hipStream_t s) {
-  if (T <= 16 || T > 64 || (long)B * n * H > 0x7fffffffL) return EGV_ERR_ARG;
-  if (T <= 32) return launch_fwd<2>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-  if (T <= 48) return launch_fwd<3>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-  return launch_fwd<4>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
+// A pick (attn_dispatch.h att_pick_time: NT = ceil(T / 16) tiles per location, one workgroup of NT waves per (clip, location, head)) to
+// its instance.  fp16 operands: three-product forward, one-product backward.
+int egv_attn_time_long_fwd(const AttPick& p, const AttTimeFwd& a, hipStream_t s) {
+  return att_instance<2, 3, 4>(p, [&](auto nt, auto passes, auto f16) -> int {
+    constexpr int NT = nt, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 3)
+      return att_launch(attn_time_long_fwd_kernel<PASSES, NT, F16>, p, s, a.qh, a.ql, a.B, a.T, a.n, a.H, a.oh, a.ol, a.lse, a.ws, a.out_fmt);
+    else
+      return EGV_ERR_ARG;
+  });
 }
 
-int egv_attn_time_long_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
-                                const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16,
-                                hipStream_t s) {
-  if (T <= 16 || T > 64 || (long)B * n * H > 0x7fffffffL) return EGV_ERR_ARG;
-  if (T <= 32) return launch_bwd<2>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-  if (T <= 48) return launch_bwd<3>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-  return launch_bwd<4>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
+int egv_attn_time_long_bwd(const AttPick& p, const AttTimeBwd& a, hipStream_t s) {
+  return att_instance<2, 3, 4>(p, [&](auto nt, auto passes, auto f16) -> int {
+    constexpr int NT = nt, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 1)
+      return att_launch(attn_time_long_bwd_kernel<PASSES, NT, F16>, p, s, a.qh, a.ql, a.doh, a.dol, a.lse, a.delta, a.B, a.T, a.n, a.H, a.gh,
+                        a.gl, a.dcls, a.gfmt);
+    else
+      return EGV_ERR_ARG;
+  });
 }

@@ -480,52 +480,27 @@ __global__ __launch_bounds__(64 * WPB) void attn_time_mfma_bwd_kernel(const bf16
 
 }  // namespace
 
-template <int TP>
-static int launch_fwd(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse, float* ws,
-                      int out_fmt, int f16, hipStream_t s) {
-  constexpr int LOCS = 16 / TP;
-  const long waves = (long)B * ((n + LOCS - 1) / LOCS) * H;
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  if (f16) {
-    if (!ql) return EGV_ERR_ARG;        // the fp16 forward is the three-product one
-    EGV_LAUNCH((attn_time_mfma_fwd_kernel<3, TP, true>), grid, dim3(256), 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt);
-  } else if (ql)
-    EGV_LAUNCH((attn_time_mfma_fwd_kernel<3, TP>), grid, dim3(256), 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt);
-  else
-    EGV_LAUNCH((attn_time_mfma_fwd_kernel<1, TP>), grid, dim3(256), 0, s, qh, ql, B, T, n, H, oh, ol, lse, ws, 0);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
+// A pick (attn_dispatch.h att_pick_time: TP rows per location, the grid over waves / over WPB units of a (clip, head)) to its
+// instance.  fp16 operands: three-product forward, one-product backward.
+int egv_attn_time_tile_fwd(const AttPick& p, const AttTimeFwd& a, hipStream_t s) {
+  return att_instance<4, 8, 16>(p, [&](auto tp, auto passes, auto f16) -> int {
+    constexpr int TP = tp, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 3)
+      return att_launch(attn_time_mfma_fwd_kernel<PASSES, TP, F16>, p, s, a.qh, a.ql, a.B, a.T, a.n, a.H, a.oh, a.ol, a.lse, a.ws, a.out_fmt);
+    else
+      return EGV_ERR_ARG;
+  });
 }
 
-template <int TP>
-static int launch_bwd(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse, const float* delta, int B,
-                      int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16, hipStream_t s) {
-  constexpr int LOCS = 16 / TP;
-  const int units = (n + LOCS - 1) / LOCS;
-  if (f16)
-    EGV_LAUNCH((attn_time_mfma_bwd_kernel<1, 4, TP, true>), dim3((unsigned)((long)B * H * ((units + 3) / 4))), dim3(256), 0, s, qh, nullptr, doh,
-               nullptr, lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  else if (ql && dol)
-    EGV_LAUNCH((attn_time_mfma_bwd_kernel<3, 2, TP>), dim3((unsigned)((long)B * H * ((units + 1) / 2))), dim3(128), 0, s, qh, ql, doh, dol,
-               lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  else
-    EGV_LAUNCH((attn_time_mfma_bwd_kernel<1, 4, TP>), dim3((unsigned)((long)B * H * ((units + 3) / 4))), dim3(256), 0, s, qh, nullptr, doh,
-               nullptr, lse, delta, B, T, n, H, gh, gl, dcls, gfmt);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
-int egv_attn_time_mfma_fwd_impl(const bf16_t* qh, const bf16_t* ql, int B, int T, int n, int H, bf16_t* oh, bf16_t* ol, float* lse,
-                                float* ws, int out_fmt, int f16, hipStream_t s) {
-  if (T <= 4) return launch_fwd<4>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-  if (T <= 8) return launch_fwd<8>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-  return launch_fwd<16>(qh, ql, B, T, n, H, oh, ol, lse, ws, out_fmt, f16, s);
-}
-
-int egv_attn_time_mfma_bwd_impl(const bf16_t* qh, const bf16_t* ql, const bf16_t* doh, const bf16_t* dol, const float* lse,
-                                const float* delta, int B, int T, int n, int H, bf16_t* gh, bf16_t* gl, float* dcls, int gfmt, int f16,
-                                hipStream_t s) {
-  if (T <= 4) return launch_bwd<4>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-  if (T <= 8) return launch_bwd<8>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
-  return launch_bwd<16>(qh, ql, doh, dol, lse, delta, B, T, n, H, gh, gl, dcls, gfmt, f16, s);
+int egv_attn_time_tile_bwd(const AttPick& p, const AttTimeBwd& a, hipStream_t s) {
+  return att_instance<4, 8, 16>(p, [&](auto tp, auto passes, auto f16) -> int {
+    constexpr int TP = tp, PASSES = passes;
+    constexpr bool F16 = f16;
+    if constexpr (!F16 || PASSES == 1)
+      return att_launch(attn_time_mfma_bwd_kernel<PASSES, PASSES == 3 ? 2 : 4, TP, F16>, p, s, a.qh, a.ql, a.doh, a.dol, a.lse, a.delta, a.B,
+                        a.T, a.n, a.H, a.gh, a.gl, a.dcls, a.gfmt);
+    else
+      return EGV_ERR_ARG;
+  });
 }

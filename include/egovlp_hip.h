@@ -398,7 +398,8 @@ int64_t egv_divided_attn_fwd_work_floats(int32_t B, int32_t T, int32_t n, int32_
  * `work`: egv_divided_attn_bwd_work_floats(...) floats.
  * mode: bit 0 = time; bits 1-2 = the format the forward wrote out_* in (as above: delta = rowsum(dO o O) decodes it; formats 1-3
  * take out_lo = NULL); bit 3 (passes == 1 only) = dqkv_hi receives ONE plane of UN-CLAMPED fp16 instead of bf16 (the fp16 backward;
- * q / k / v / dO are still read as bf16 planes).                                                                        */
+ * q / k / v / dO are still read as bf16 planes); bit 4 (with bit 3 and passes == 1 only) = q / k / v (qkv_hi: the first plane of an
+ * fp16-split qkv) and dO (dout_hi) are fp16 planes: fp16 MFMA products throughout.  A refused call (EGV_ERR_ARG) enqueues nothing. */
 int egv_divided_attn_bwd(const egv_bf16* qkv_hi, const egv_bf16* qkv_lo, const egv_bf16* out_hi, const egv_bf16* out_lo,
                          const egv_bf16* dout_hi, const egv_bf16* dout_lo, const float* lse, int32_t B, int32_t T,
                          int32_t n, int32_t H, int32_t mode, int32_t passes, egv_bf16* dqkv_hi, egv_bf16* dqkv_lo,
