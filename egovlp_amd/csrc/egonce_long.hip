@@ -3,6 +3,8 @@
 // MFMA (v_mfma_f32_16x16x4_f32: bit for bit an fp32 fma chain, so the numerics are those of the fp32 short head), the EgoNCE
 // mask comes from bit-packed noun / verb rows, and the row statistics are kept online while the column tiles stream through
 // LDS.  All arithmetic fp32; every reduction runs in a fixed order (no float atomics), so a call is deterministic.
+// The pieces the sigmoid head (sigmoid_head.hip) shares -- prep, the LDS tile, the mask tile, the X^T product, the split and finish --
+// live in egonce_tile.h.
 //
 //   prep    one workgroup per row: |t|, |v|, the normalised rows tn / vn zero-padded from D to Dp (64 or 256), and the
 //           noun / verb rows packed into bit words (bit = entry > 0; each part padded to a multiple of 4 words).  Rows
@@ -33,34 +35,18 @@
 // only permutes the order of the fma chain.  The second product uses the same trick on the OUTPUT column: MFMA t of a 64-wide
 // chunk produces d = 64 c + 4 (lane & 15) + t, so a lane ends with four consecutive d and stores 16 bytes.
 #include "common.h"
+#include "egonce_tile.h"
 #include "egovlp_hip.h"
 
 namespace {
 
-constexpr int EGL_TILE = 64;          // rows per tile (A rows per workgroup, B rows per LDS tile)
 constexpr int EGL_STAT_WGS = 512;     // column ranges are chosen so that a launch has about this many workgroups (2 per CU)
-constexpr int EGL_GRAD_WGS = 256;     // the gradient's partials cost memory and a pass: half as many
 constexpr float EGL_NEG = -3e38f;
-
-__device__ __forceinline__ float egl_block_sum(float v, float* sh) {  // 256 threads
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 
 struct EglLayout {
   int np, Dp, wn, W, ntiles, tps_s, ns_s, tps_g, ns_g;
   long tn, vn, words, norms, flags, spart, stat, gpart, lpart, total;   // offsets in floats
 };
-
-inline void egl_split(int ntiles, int target, int& tps, int& ns) {
-  int want = (target + ntiles - 1) / ntiles;
-  if (want > ntiles) want = ntiles;
-  tps = (ntiles + want - 1) / want;
-  ns = (ntiles + tps - 1) / tps;       // no empty range
-}
 
 inline EglLayout egl_layout(int n, int D, int dn, int dv) {
   EglLayout L;
@@ -84,146 +70,6 @@ inline EglLayout egl_layout(int n, int D, int dn, int dv) {
   L.lpart = o;  o += (long)L.ns_g * L.ntiles;          // dL/d(logit scale): one partial per workgroup of the grad walk
   L.total = o;
   return L;
-}
-
-// ------------------------------------------------------------------------------------------------ prep
-__global__ __launch_bounds__(256) void egl_prep_kernel(const float* __restrict__ text, const float* __restrict__ video,
-                                                       const float* __restrict__ noun, const float* __restrict__ verb, int n,
-                                                       int np, int D, int Dp, int dn, int dv, int wn, int W, float eps,
-                                                       float* __restrict__ tn, float* __restrict__ vn,
-                                                       uint32_t* __restrict__ words, float* __restrict__ norms,
-                                                       float* __restrict__ flags) {
-  __shared__ float sh[4];
-  const int i = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (i >= n) {                                       // the padding rows of the last tile
-    for (int d = threadIdx.x; d < Dp; d += 256) {
-      tn[(long)i * Dp + d] = 0.f;
-      vn[(long)i * Dp + d] = 0.f;
-    }
-    for (int w = threadIdx.x; w < W; w += 256) words[(long)i * W + w] = 0u;
-    if (threadIdx.x == 0) {
-      norms[i] = 0.f;
-      norms[np + i] = 0.f;
-      flags[i] = 0.f;
-    }
-    return;
-  }
-  float st = 0.f, sv = 0.f;
-  for (int d = threadIdx.x; d < D; d += 256) {
-    const float a = text[(long)i * D + d], b = video[(long)i * D + d];
-    st += a * a;
-    sv += b * b;
-  }
-  const float nt = sqrtf(egl_block_sum(st, sh));
-  const float nv = sqrtf(egl_block_sum(sv, sh));
-  const float ct = fmaxf(nt, eps), cv = fmaxf(nv, eps);
-  for (int d = threadIdx.x; d < Dp; d += 256) {
-    tn[(long)i * Dp + d] = d < D ? text[(long)i * D + d] / ct : 0.f;
-    vn[(long)i * Dp + d] = d < D ? video[(long)i * D + d] / cv : 0.f;
-  }
-  int bad = 0;
-  if (noun) {
-    // 64 entries per wave and step: the ballot of (entry > 0) is two of the row's words
-    for (int base = wave * 64; base < wn * 32; base += 256) {
-      const int c = base + lane;
-      const float e = c < dn ? noun[(long)i * dn + c] : 0.f;
-      bad |= !(e >= 0.f);
-      const unsigned long long b = __ballot(e > 0.f);
-      if (lane == 0) {
-        words[(long)i * W + base / 32] = (uint32_t)b;
-        words[(long)i * W + base / 32 + 1] = (uint32_t)(b >> 32);
-      }
-    }
-    for (int base = wave * 64; base < (W - wn) * 32; base += 256) {
-      const int c = base + lane;
-      const float e = c < dv ? verb[(long)i * dv + c] : 0.f;
-      bad |= !(e >= 0.f);
-      const unsigned long long b = __ballot(e > 0.f);
-      if (lane == 0) {
-        words[(long)i * W + wn + base / 32] = (uint32_t)b;
-        words[(long)i * W + wn + base / 32 + 1] = (uint32_t)(b >> 32);
-      }
-    }
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) {
-    norms[i] = nt;
-    norms[np + i] = nv;
-    flags[i] = bad ? 1.f : 0.f;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ tile pieces
-// B rows j0 .. j0 + 63 -> LDS image [64][DP + 4] (the 4 floats of padding spread the rows over the banks)
-template <int DP>
-__device__ __forceinline__ void egl_stage_tile(float* bt, const float* __restrict__ B, int j0) {
-  constexpr int LD = DP + 4, C4 = DP / 4;
-  for (int idx = threadIdx.x; idx < EGL_TILE * C4; idx += 256) {
-    const int r = idx / C4, c4 = idx % C4;
-    *(f32x4_t*)(bt + r * LD + 4 * c4) = *(const f32x4_t*)(B + (long)(j0 + r) * DP + 4 * c4);
-  }
-}
-
-// The 64 x 64 mask tile, 16 bits per thread: thread (row i0 + (tid & 63), wave q) covers columns j0 + 16 q .. + 15; the words of
-// a column row are wave-uniform.  mode 0: diagonal only; 1: noun AND verb; 2: noun; 3: verb.  mb: [64][4] words.
-__device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words, int W, int wn, int mode, int i0, int j0,
-                                              uint32_t* mb) {
-  const int il = threadIdx.x & 63;
-  const int jq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int gi = i0 + il, jb = j0 + jq * 16;
-  uint32_t bits = 0u;
-  if (mode != 0) {
-    uint32_t hn[16], hv[16];
-#pragma unroll
-    for (int jj = 0; jj < 16; ++jj) hn[jj] = hv[jj] = 0u;
-    const u32x4_t* wi = (const u32x4_t*)(words + (long)gi * W);
-    const int qn = wn >> 2, qa = W >> 2;
-    if (mode != 3)
-      for (int q = 0; q < qn; ++q) {
-        const u32x4_t a = wi[q];
-#pragma unroll
-        for (int jj = 0; jj < 16; ++jj) {
-          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];      // wave-uniform: scalar loads
-          hn[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
-        }
-      }
-    if (mode != 2)
-      for (int q = qn; q < qa; ++q) {
-        const u32x4_t a = wi[q];
-#pragma unroll
-        for (int jj = 0; jj < 16; ++jj) {
-          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];
-          hv[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
-        }
-      }
-#pragma unroll
-    for (int jj = 0; jj < 16; ++jj) {
-      const bool m = mode == 1 ? (hn[jj] != 0u && hv[jj] != 0u) : (mode == 2 ? hn[jj] != 0u : hv[jj] != 0u);
-      bits |= (m ? 1u : 0u) << jj;
-    }
-  }
-  const int dj = gi - jb;
-  if (dj >= 0 && dj < 16) bits |= 1u << dj;
-  mb[il * 4 + jq] = bits;
-}
-
-// X^T fragments of the wave's 16 rows against the LDS tile: x[jf][r] = <A row (lane & 15), B row 16 jf + 4 (lane >> 4) + r>
-template <int DP>
-__device__ __forceinline__ void egl_xt(const float* bt, const f32x4_t (&a)[DP / 16], int li, int g, f32x4_t (&x)[4]) {
-  constexpr int LD = DP + 4;
-#pragma unroll
-  for (int jf = 0; jf < 4; ++jf) x[jf] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < DP / 16; ++c) {
-    f32x4_t b[4];
-#pragma unroll
-    for (int jf = 0; jf < 4; ++jf) b[jf] = *(const f32x4_t*)(bt + (jf * 16 + li) * LD + 16 * c + 4 * g);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int jf = 0; jf < 4; ++jf) x[jf] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jf][t], a[c][t], x[jf], 0, 0, 0);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ statistics
@@ -449,22 +295,6 @@ __global__ __launch_bounds__(256) void egl_scale_grad_kernel(const float* __rest
   if (threadIdx.x == 0) d_logit_scale[0] = (float)s;
 }
 
-// sum of the column-range partials in a fixed order + the backward of the row normalisation (egonce.hip:281-282)
-__global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict__ gpart, int ns, const float* __restrict__ an,
-                                                         const float* __restrict__ norms, int np, int D, int Dp, float eps,
-                                                         float* __restrict__ out) {
-  __shared__ float sh[4];
-  const int i = blockIdx.x, d = threadIdx.x;
-  float gsum = 0.f, th = 0.f;
-  if (d < Dp) {
-    for (int r = 0; r < ns; ++r) gsum += gpart[((long)r * np + i) * Dp + d];
-    th = an[(long)i * Dp + d];
-  }
-  const float proj = egl_block_sum(th * gsum, sh);
-  const float nrm = norms[i];
-  if (d < D) out[(long)i * D + d] = nrm > eps ? (gsum - th * proj) / nrm : gsum / eps;
-}
-
 template <int DP>
 int egl_launch_stats(const EglLayout& L, const float* A, const float* B, const uint32_t* words, int n, int mode, float inv_tau,
                      const float* logit_scale, float* part, hipStream_t s) {
@@ -491,10 +321,6 @@ int egl_launch_grad(const EglLayout& L, const float* A, const float* B, const ui
 }
 
 #define EGL_BY_DP(fn, ...) (L.Dp == 64 ? fn<64>(__VA_ARGS__) : fn<256>(__VA_ARGS__))
-
-inline bool egl_args_ok(int n, int D, int dn, int dv) {
-  return n >= 1 && n <= 65536 && D >= 4 && D <= 256 && D % 4 == 0 && dn >= 0 && dv >= 0 && dn <= 65536 && dv <= 65536;
-}
 
 }  // namespace
 

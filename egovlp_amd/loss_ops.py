@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the contrastive-head kernels (include/egovlp_hip.h: egv_sim_matrix_*,
-egv_egonce_from_sim, egv_egonce_fwd_bwd and their *_ls variants, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
+egv_egonce_from_sim, egv_egonce_fwd_bwd and their *_ls variants, egv_sigmoid_from_sim, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
 the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
 import torch
 
@@ -58,6 +58,30 @@ def egonce_from_sim(x, sim_v, sim_n, temperature, use_noun, use_verb, want_grad=
     check(_lib.lib().egv_egonce_from_sim(_p(x), _p(sv), _p(sn), n, float(temperature), int(use_noun), int(use_verb),
                                          _p(loss), _p(dx), _p(work), ops._stream()), "egv_egonce_from_sim")
     return loss, dx
+
+
+def sigmoid_from_sim(x, sim_v, sim_n, logit_scale, logit_bias, use_noun, use_verb, want_grad=True, want_param_grads=True):
+    """SigmoidLoss / EgoSigmoidLoss on a given similarity matrix -> (loss[1], dx, d_scale [1], d_bias [1]) -- egv_sigmoid_from_sim.
+    `logit_scale`, `logit_bias`: device tensors of one fp32 each.  want_grad=False: the loss alone; want_param_grads=False: no
+    d_scale / d_bias."""
+    ops._need_cuda(x, sim_v, sim_n)
+    x = x.contiguous()
+    n = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != n:
+        raise ValueError("SigmoidLoss / EgoSigmoidLoss need a square similarity matrix")
+    dev = x.device
+    ls = ops._one_fp32_arg(logit_scale, x, "logit_scale")
+    lb = ops._one_fp32_arg(logit_bias, x, "logit_bias")
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x) if want_grad else None
+    dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grad and want_param_grads else None
+    dlb = torch.empty(1, dtype=torch.float32, device=dev) if want_grad and want_param_grads else None
+    sv = sim_v.contiguous() if sim_v is not None else None
+    sn = sim_n.contiguous() if sim_n is not None else None
+    work = torch.empty(3072, dtype=torch.float32, device=dev)
+    check(_lib.lib().egv_sigmoid_from_sim(_p(x), _p(sv), _p(sn), n, _p(ls), _p(lb), int(use_noun), int(use_verb), _p(loss), _p(dx),
+                                          _p(dls), _p(dlb), _p(work), ops._stream()), "egv_sigmoid_from_sim")
+    return loss, dx, dls, dlb
 
 
 def maxmargin(x, weight, margin, fix_norm, want_grad=True):

@@ -8,6 +8,9 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip):
     egv_egonce_long_fwd_bwd of csrc/egonce_long.hip, which forms no n x n matrix).
 Both losses take `learnable_temperature=True` (not in the reference): the temperature becomes CLIP's learnable logit scale, read on the
 device by the *_ls variants of the same entry points, which also return its gradient (_TemperatureMixin below).
+SigmoidLoss / EgoSigmoidLoss (not in the reference) are the pairwise sigmoid (SigLIP) counterparts of the two softmax losses, with a
+learnable logit scale AND bias (_SigmoidMixin): `forward` over egv_sigmoid_from_sim, `fused` over egv_sigmoid_head_fwd_bwd
+(csrc/sigmoid_head.hip: one tile walk per direction for any n up to 65 536).
 MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EPIC-MIR / Charades fine-tuning heads over the
 same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
 of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR
@@ -164,6 +167,124 @@ class EgoNCE(_TemperatureMixin, nn.Module):
                                            self.verb or not self.noun)
         return _FusedHeadFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.temperature, self.noun,
                                   self.verb or not self.noun)
+
+
+class _SigmoidFromSimFn(torch.autograd.Function):
+    """The sigmoid loss on a given similarity matrix (egv_sigmoid_from_sim): dx, dL/ds and dL/db from one node."""
+
+    @staticmethod
+    def forward(ctx, x, mask_v, mask_n, logit_scale, logit_bias, use_noun, use_verb, learnable):
+        loss, dx, dls, dlb = loss_ops.sigmoid_from_sim(x, mask_v, mask_n, logit_scale, logit_bias, use_noun, use_verb,
+                                                       want_grad=True, want_param_grads=learnable)
+        ctx.learnable = learnable
+        ctx.save_for_backward(*((dx, _over_world(dls), _over_world(dlb)) if learnable else (dx,)))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.learnable:
+            dx, dls, dlb = ctx.saved_tensors
+            return dx * g, None, None, dls * g, dlb * g, None, None, None
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None, None, None, None, None, None
+
+
+class _FusedSigmoidHeadFn(torch.autograd.Function):
+    """The one-call sigmoid head (egv_sigmoid_head_fwd_bwd): all four gradients leave this node times the upstream factor, so they
+    carry the loss scale of an fp16 backward."""
+
+    @staticmethod
+    def forward(ctx, text, video, noun, verb, logit_scale, logit_bias, use_noun, use_verb, learnable):
+        loss, dt, dv, dls, dlb = ops.sigmoid_head_fwd_bwd(text.contiguous(), video.contiguous(),
+                                                          None if noun is None else noun.contiguous().float(),
+                                                          None if verb is None else verb.contiguous().float(),
+                                                          logit_scale, logit_bias, use_noun=use_noun, use_verb=use_verb,
+                                                          want_param_grads=learnable)
+        ctx.learnable = learnable
+        ctx.save_for_backward(*((dt, dv, _over_world(dls), _over_world(dlb)) if learnable else (dt, dv)))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.learnable:
+            dt, dv, dls, dlb = ctx.saved_tensors
+            return dt * g, dv * g, None, None, dls * g, dlb * g, None, None, None
+        dt, dv = ctx.saved_tensors
+        return dt * g, dv * g, None, None, None, None, None, None, None
+
+
+class _SigmoidMixin:
+    """SigLIP's two parameters (Zhai et al. 2023): `logit_scale` = s (u = exp(s) x + b; initial value ln 10) and `logit_bias` = b
+    (initial value -10), fp32 [1] each, read on the device by the head kernels, which return dL/ds and dL/db beside the embedding
+    gradients.  learnable=False: both are held with requires_grad=False and the heads are called without the parameter gradients."""
+
+    def _init_sigmoid(self, logit_scale, logit_bias, learnable, max_logit_scale):
+        self.learnable = bool(learnable)
+        self.learnable_temperature = self.learnable      # what clamp_loss_scale and the trainer's temperature log look at
+        self.max_logit_scale = float(max_logit_scale)
+        # the clamp runs in fp32: its upper bound is the largest fp32 value <= max_logit_scale (fp32(ln 100) itself rounds UP)
+        hi = torch.tensor(self.max_logit_scale, dtype=torch.float32)
+        if float(hi) > self.max_logit_scale:
+            hi = torch.nextafter(hi, torch.tensor(float("-inf")))
+        self._clamp_hi = float(hi)
+        self.logit_scale = nn.Parameter(torch.full((1,), float(logit_scale), dtype=torch.float32), requires_grad=self.learnable)
+        self.logit_bias = nn.Parameter(torch.full((1,), float(logit_bias), dtype=torch.float32), requires_grad=self.learnable)
+
+    def current_temperature(self):
+        """exp(-s) read back from the device (synchronises: logs and tests)."""
+        return math.exp(-float(self.logit_scale.detach().float().cpu()))
+
+    def current_bias(self):
+        """b read back from the device (synchronises: logs and tests)."""
+        return float(self.logit_bias.detach().float().cpu())
+
+    @torch.no_grad()
+    def clamp_logit_scale_(self):
+        """s <- clamp(s, 0, max_logit_scale) in place: one tiny device op, no synchronisation.  The bias is not clamped."""
+        if self.learnable:
+            self.logit_scale.clamp_(0.0, self._clamp_hi)
+        return self
+
+
+class SigmoidLoss(_SigmoidMixin, nn.Module):
+    """Pairwise sigmoid loss (SigLIP) on the diagonal positives: the counterpart of NormSoftmaxLoss (not in the reference).
+    L = (1 / n) sum_ij softplus(-z_ij (exp(s) x_ij + b)), z = +1 on the diagonal, -1 elsewhere."""
+
+    takes_noun_verb = False
+
+    def __init__(self, logit_scale=math.log(10), logit_bias=-10.0, learnable=True, max_logit_scale=math.log(100)):
+        super().__init__()
+        self._init_sigmoid(logit_scale, logit_bias, learnable, max_logit_scale)
+
+    def forward(self, x):
+        "x: similarity matrix N x N in [-1, 1]"
+        return _SigmoidFromSimFn.apply(x, None, None, self.logit_scale, self.logit_bias, True, True, self.learnable)
+
+    def fused(self, text_embeds, video_embeds):
+        return _FusedSigmoidHeadFn.apply(text_embeds, video_embeds, None, None, self.logit_scale, self.logit_bias, True, True,
+                                         self.learnable)
+
+
+class EgoSigmoidLoss(_SigmoidMixin, nn.Module):
+    """The sigmoid loss with EgoNCE's positives: the counterpart of EgoNCE (not in the reference).  z_ij = +1 where rows i and j
+    share a noun and a verb, or i == j (`noun` only: share a noun; neither flag: the reference's else-branch, verb): every pair is
+    its own binary decision, so the set of positives of a row needs no normalisation."""
+
+    takes_noun_verb = True          # trainer/common.py egoclip_head_loss: fused(text, video, noun_vec, verb_vec), forward(x, mask_v, mask_n)
+
+    def __init__(self, logit_scale=math.log(10), logit_bias=-10.0, learnable=True, max_logit_scale=math.log(100), noun=True, verb=True):
+        super().__init__()
+        self.noun = noun
+        self.verb = verb
+        self._init_sigmoid(logit_scale, logit_bias, learnable, max_logit_scale)
+
+    def forward(self, x, mask_v, mask_n):
+        return _SigmoidFromSimFn.apply(x, mask_v, mask_n, self.logit_scale, self.logit_bias, self.noun, self.verb or not self.noun,
+                                       self.learnable)
+
+    def fused(self, text_embeds, video_embeds, noun_vec, verb_vec):
+        return _FusedSigmoidHeadFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.logit_scale, self.logit_bias, self.noun,
+                                         self.verb or not self.noun, self.learnable)
 
 
 class _MaxMarginFn(torch.autograd.Function):

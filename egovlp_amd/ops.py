@@ -1349,6 +1349,41 @@ def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun
     return loss, dt, dvv
 
 
+def _one_fp32_arg(value, like, name):
+    """A head parameter read on the device: one fp32 on the inputs' device."""
+    v = value.detach()
+    if v.dtype != torch.float32 or v.numel() != 1 or v.device != like.device:
+        raise ValueError("%s must be one fp32 value on the device of the embeddings" % name)
+    return v.contiguous()
+
+
+def sigmoid_head_fwd_bwd(text, video, noun, verb, logit_scale, logit_bias, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                         want_param_grads=True):
+    """egv_sigmoid_head_fwd_bwd, the pairwise sigmoid head with EgoNCE's positives (noun / verb None: mask = I, plain SigLIP), for
+    ANY n in [1, 65536] -> (loss[1], d_text, d_video, d_scale[1], d_bias[1]).  `logit_scale` (s) and `logit_bias` (b) are device
+    tensors of one fp32 each: u = exp(s) x + b is formed on the device.  want_grads=False: the loss alone, the four gradients are
+    None; want_param_grads=False (fixed s and b): d_scale and d_bias are None.  noun / verb: non-negative multi-hots (only
+    entry > 0 is used); a negative or NaN entry makes the loss NaN."""
+    _need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    dev = text.device
+    dn = noun.shape[1] if noun is not None else 0
+    dv = verb.shape[1] if verb is not None else 0
+    ls = _one_fp32_arg(logit_scale, text, "logit_scale")
+    lb = _one_fp32_arg(logit_bias, text, "logit_bias")
+    wf = _lib.lib().egv_sigmoid_head_work_floats(n, D, dn, dv)
+    work = torch.empty(wf, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dt = torch.empty_like(text) if want_grads else None
+    dvv = torch.empty_like(video) if want_grads else None
+    dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads and want_param_grads else None
+    dlb = torch.empty(1, dtype=torch.float32, device=dev) if want_grads and want_param_grads else None
+    check(_lib.lib().egv_sigmoid_head_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), _p(lb), float(eps),
+                                              int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(dls), _p(dlb), _p(work),
+                                              _stream(text)), "egv_sigmoid_head_fwd_bwd")
+    return loss, dt, dvv, dls, dlb
+
+
 def grad_nonfinite_multi(grads, state):
     """state[2] |= 1 if any gradient holds an inf / NaN (egv_grad_nonfinite_multi); `state`: the int32[8] device block of a LossScaler."""
     n = len(grads)

@@ -38,15 +38,17 @@ def step_epilogue(loss, ec, optimizer, grad_sync, scaler):
 
 
 def clamp_loss_scale(loss_fn):
-    """After optimizer.step of the EgoClip steps: a loss with a learnable temperature clamps its logit scale (one tiny device op, no
-    synchronisation); any other loss: nothing is called."""
+    """After optimizer.step of the EgoClip steps: a loss with a learnable temperature (EgoNCE / NormSoftmaxLoss with
+    `learnable_temperature=True`; SigmoidLoss / EgoSigmoidLoss with `learnable=True`, which set the same attribute) clamps its logit
+    scale (one tiny device op, no synchronisation); any other loss: nothing is called."""
     if getattr(loss_fn, 'learnable_temperature', False):
         loss_fn.clamp_logit_scale_()
 
 
 def register_loss_parameters(optimizer, loss_fn, lr=None):
     """The reference builds its optimizer from `model.parameters()` only (run/train_egoclip.py:72-73); a loss with parameters of its
-    own (EgoNCE / NormSoftmaxLoss with `learnable_temperature=True`: the logit scale) gets ONE more parameter group here:
+    own (EgoNCE / NormSoftmaxLoss with `learnable_temperature=True`: the logit scale; SigmoidLoss / EgoSigmoidLoss: the logit scale and
+    the logit bias, both in the one group) gets ONE more parameter group here:
     weight_decay 0, `lr` defaulting to the first group's.  Parameters the optimizer already holds are left where they are (calling
     this twice adds nothing).  -> the new group, or None when there was nothing to add."""
     if not hasattr(loss_fn, 'parameters'):
@@ -65,7 +67,8 @@ def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fu
     """Similarity + loss of the EgoClip step on the (gathered) global batch, trainer/trainer_egoclip.py:130-137 -- shared by
     `egoclip_step` and `egoclip_step_cached`."""
     from ..model.model import sim_matrix
-    is_ego = type(loss_fn).__name__ == 'EgoNCE'
+    # EgoNCE, and any loss that says so (EgoSigmoidLoss), takes the noun / verb vectors; the others the embeddings alone
+    is_ego = type(loss_fn).__name__ == 'EgoNCE' or bool(getattr(loss_fn, 'takes_noun_verb', False))
     n, D = text_embeds.shape
     # the one-call head covers global batches up to 65 536 rows of <= 256 features: the latency-bound kernels up to 1 024 rows, the
     # tiled fp32-MFMA ones beyond (ops.egonce_fwd_bwd switches); anything else, or fused_head=False, takes the API-compatible
@@ -224,6 +227,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 self.writer.add_scalar(f'Loss_training/loss_{dl_idx}', float(loss), (epoch - 1) * total + current)   # :143-148
                 if getattr(getattr(self, 'loss', None), 'learnable_temperature', False):   # float(loss) has just synchronised: the read-back is free
                     self.writer.add_scalar(f'Loss_training/temperature_{dl_idx}', self.loss.current_temperature(), (epoch - 1) * total + current)
+                if hasattr(getattr(self, 'loss', None), 'current_bias'):                    # the sigmoid losses: their second parameter
+                    self.writer.add_scalar(f'Loss_training/bias_{dl_idx}', self.loss.current_bias(), (epoch - 1) * total + current)
                 # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has
                 # just synchronised anyway (off: nothing is computed, nothing is read)
                 if getattr(self.optimizer, 'max_grad_norm', None) is not None:

@@ -546,6 +546,27 @@ int egv_egonce_long_fwd_bwd_ls(const float* text, const float* video, const floa
 int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const float* sim_n, int32_t n, const float* logit_scale,
                            int32_t use_noun, int32_t use_verb, float* loss, float* dx, float* d_logit_scale,
                            float* work /* n*n + 7n floats */, void* stream);
+/* Pairwise sigmoid head (SigLIP) with EgoNCE's positives, for ANY n in [1, 65536] (D <= 256, D % 4 == 0; noun and verb both given or
+ * both NULL: mask = I, plain SigLIP), csrc/sigmoid_head.hip.  With tn / vn the normalised rows (sim_matrix's rule, `eps`),
+ *   x_ij = tn_i . vn_j,  u_ij = exp(s) x_ij + b,  z_ij = +1 where m_ij else -1,  loss = (1 / n) sum_ij softplus(-z_ij u_ij),
+ * m the mask of egv_egonce_long_fwd_bwd (same data contract: only (entry > 0) of noun / verb is used; a negative or NaN entry makes the
+ * loss NaN through a device-side flag).  `logit_scale` (s) and `logit_bias` (b) point to one fp32 each on the DEVICE and are never read
+ * on the host.  No n x n buffer: the similarity tiles are formed on the fp32-input MFMA and streamed, loss and gradient in ONE walk per
+ * direction; the workspace (egv_sigmoid_head_work_floats floats; 0 for bad sizes) is linear in n plus a bounded number of partial tiles.
+ * Outputs: loss[1]; optionally d_text and d_video [n, D] (both or neither); optionally, with them, d_scale[1] = dL/ds = sum_ij G_ij x_ij
+ * and d_bias[1] = dL/db (both or neither), G = dL/dx.  No gradient pointer: the loss alone (evaluation).  No float atomics: two calls
+ * give the same bits.  Arguments are checked before any launch: a bad one returns 1 and launches nothing. */
+int egv_sigmoid_head_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
+                             int32_t n, int32_t D, int32_t dn, int32_t dv, const float* logit_scale, const float* logit_bias,
+                             float eps, int32_t use_noun, int32_t use_verb,
+                             float* loss, float* d_text, float* d_video, float* d_scale, float* d_bias, float* work, void* stream);
+int64_t egv_sigmoid_head_work_floats(int32_t n, int32_t D, int32_t dn, int32_t dv);
+/* The same loss on a given similarity matrix x [n, n] (n <= 4096, as egv_egonce_from_sim; sim_v / sim_n NULL => mask = I; otherwise
+ * mask = sim_v * sim_n + I > 0, `use_noun` only: sim_n + I, else sim_v + I): loss[1], optionally dx [n, n], optionally with dx
+ * d_scale[1] and d_bias[1] (both or neither).  One element-wise pass with block partials and a fixed-order final sum. */
+int egv_sigmoid_from_sim(const float* x, const float* sim_v, const float* sim_n, int32_t n, const float* logit_scale,
+                         const float* logit_bias, int32_t use_noun, int32_t use_verb, float* loss, float* dx,
+                         float* d_scale, float* d_bias, float* work /* 3072 floats */, void* stream);
 
 /* Max-margin ranking losses of the fine-tuning heads (model/loss.py:55-133) on a square similarity matrix x [n, n]:
  *   loss = mean_{kept (i,j)} relu(w_i m - x_ii + x_ij) + relu(w_i m - x_ii + x_ji),   w = NULL: MaxMarginRankingLoss (w_i = 1),
