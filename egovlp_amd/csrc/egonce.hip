@@ -1,6 +1,9 @@
 // Contrastive head: sim_matrix (x3) + EgoNCE / NormSoftmaxLoss, forward AND analytic backward.
 //   model/model.py:189-197 (sim_matrix), model/loss.py:13-25 (NormSoftmaxLoss), :34-53 (EgoNCE),
 //   trainer/trainer_egoclip.py:130-137 (the three sim_matrix calls feeding the loss).
+// This file holds the short head (egv_egonce_fwd_bwd), EgoNCE on a given similarity matrix (egv_egonce_from_sim) and the generic
+// sim_matrix forward / backward (egv_sim_matrix_*).  The ranking losses are in maxmargin_head.hip, the cross-entropy in
+// cls_head.hip, the dual-softmax rescaling in retrieval.hip.
 // The whole problem is n = W*B <= 1024 rows (256 at 8 GPUs x 32): latency-bound, not throughput-bound,
 // so the design goal is few launches and no host round trip: 5 small kernels replace the ~40 ATen
 // launches + autograd graph of the reference, and the gradient w.r.t. both embeddings comes out of
@@ -11,27 +14,13 @@
 //            -1/n sum_i [log sum_j m_ij a_ji - log sum_j a_ji]
 // Learnable temperature (the *_ls entry points): 1 / tau = exp(s) is read from the device, and with G = dL/dx
 //   dL/ds  = sum_ij G_ij x_ij                                       s = log(1 / tau)
-// falls out of the gradient kernel, which holds x_ij and G_ij: one block_sum per row into n partials, then one
+// falls out of the gradient kernel, which holds x_ij and G_ij: one block sum per row into n partials, then one
 // workgroup adds them in a fixed order in double.  No float atomics: two calls give the same bits.
-#include "common.h"
+#define EGV_SCALE_GRAD_KERNEL
+#include "head_common.h"
 #include "egovlp_hip.h"
 
 namespace {
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {  // 256 threads
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
 
 // A: per row i: clamped norms + normalised text / video rows
 __global__ __launch_bounds__(256) void egonce_norm_kernel(const float* __restrict__ text, const float* __restrict__ video,
@@ -57,10 +46,10 @@ __global__ __launch_bounds__(256) void egonce_norm_kernel(const float* __restric
       const float a = verb[(long)i * dv + d];
       sb += a * a;
     }
-  const float nt = sqrtf(block_sum(st, sh));
-  const float nv = sqrtf(block_sum(sv, sh));
-  const float nno = sqrtf(block_sum(sn, sh));
-  const float nve = sqrtf(block_sum(sb, sh));
+  const float nt = sqrtf(egv_block_sum_256(st, sh));
+  const float nv = sqrtf(egv_block_sum_256(sv, sh));
+  const float nno = sqrtf(egv_block_sum_256(sn, sh));
+  const float nve = sqrtf(egv_block_sum_256(sb, sh));
   const float ct = fmaxf(nt, eps), cv = fmaxf(nv, eps);
   for (int d = threadIdx.x; d < D; d += 256) {
     tn[(long)i * D + d] = text[(long)i * D + d] / ct;
@@ -74,15 +63,13 @@ __global__ __launch_bounds__(256) void egonce_norm_kernel(const float* __restric
   }
 }
 
-// B: row i of x and of the mask; row statistics rmax_i, Z_i, P_i
+// B: row i of x and of the mask
 __global__ __launch_bounds__(256) void egonce_rows_kernel(const float* __restrict__ tn, const float* __restrict__ vn,
                                                           const float* __restrict__ noun, const float* __restrict__ verb,
                                                           const float* __restrict__ stats, int n, int D, int dn, int dv,
-                                                          float inv_tau, int use_noun, int use_verb,
-                                                          float* __restrict__ x, float* __restrict__ mask,
-                                                          float* __restrict__ rstat /* [3][n] */) {
+                                                          int use_noun, int use_verb, float* __restrict__ x,
+                                                          float* __restrict__ mask) {
   extern __shared__ float rowbuf[];  // [D + dn + dv]
-  __shared__ float sh[4];
   const int i = blockIdx.x;
   float* ti = rowbuf;
   float* ni = rowbuf + D;
@@ -93,7 +80,6 @@ __global__ __launch_bounds__(256) void egonce_rows_kernel(const float* __restric
   if (verb)
     for (int d = threadIdx.x; d < dv; d += 256) bi[d] = verb[(long)i * dv + d];
   __syncthreads();
-  float lmax = -3e38f;
   for (int j = threadIdx.x; j < n; j += 256) {
     float acc = 0.f;
     const float* vj = vn + (long)j * D;
@@ -122,7 +108,6 @@ __global__ __launch_bounds__(256) void egonce_rows_kernel(const float* __restric
     }
     x[(long)i * n + j] = acc;
     mask[(long)i * n + j] = m;
-    lmax = fmaxf(lmax, acc);
   }
 }
 
@@ -135,15 +120,15 @@ __global__ __launch_bounds__(256) void egonce_rowstat_kernel(const float* __rest
   inv_tau = egv_inv_tau(inv_tau, logit_scale);
   float lmax = -3e38f;
   for (int j = threadIdx.x; j < n; j += 256) lmax = fmaxf(lmax, x[(long)i * n + j]);
-  const float rmax = block_max(lmax, sh);
+  const float rmax = egv_block_max_256(lmax, sh);
   float z = 0.f, p = 0.f;
   for (int j = threadIdx.x; j < n; j += 256) {
     const float a = __expf((x[(long)i * n + j] - rmax) * inv_tau);
     z += a;
     p += a * mask[(long)i * n + j];
   }
-  z = block_sum(z, sh);
-  p = block_sum(p, sh);
+  z = egv_block_sum_256(z, sh);
+  p = egv_block_sum_256(p, sh);
   if (threadIdx.x == 0) {
     rstat[0 * n + i] = rmax;
     rstat[1 * n + i] = z;
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
     const float v = a[(long)i * D + d];
     s += v * v;
   }
-  const float nrm = sqrtf(block_sum(s, sh));
+  const float nrm = sqrtf(egv_block_sum_256(s, sh));
   const float c = fmaxf(nrm, eps);
   for (int d = threadIdx.x; d < D; d += 256) an[(long)i * D + d] = a[(long)i * D + d] / c;
   if (threadIdx.x == 0) norms[i] = nrm;
@@ -213,10 +198,10 @@ __global__ __launch_bounds__(256) void sim_bwd_kernel(const float* __restrict__ 
     da[(long)i * D + d] = g;  // stash the raw gradient w.r.t. the normalised row
     proj += g * an[(long)i * D + d];
   }
-  proj = block_sum(proj, sh);
+  proj = egv_block_sum_256(proj, sh);
   for (int d = threadIdx.x; d < D; d += 256) {
     const float g = da[(long)i * D + d];
-    da[(long)i * D + d] = nrm > eps ? (g - an[(long)i * D + d] * proj) / nrm : g / eps;
+    da[(long)i * D + d] = egv_norm_bwd(g, an[(long)i * D + d], proj, nrm, eps);
   }
 }
 
@@ -229,15 +214,15 @@ __global__ __launch_bounds__(256) void egonce_cols_kernel(const float* __restric
   inv_tau = egv_inv_tau(inv_tau, logit_scale);
   float lmax = -3e38f;
   for (int r = threadIdx.x; r < n; r += 256) lmax = fmaxf(lmax, x[(long)r * n + c]);
-  const float cmax = block_max(lmax, sh);
+  const float cmax = egv_block_max_256(lmax, sh);
   float s = 0.f, q = 0.f;
   for (int r = threadIdx.x; r < n; r += 256) {
     const float a = __expf((x[(long)r * n + c] - cmax) * inv_tau);
     s += a;
     q += a * mask[(long)c * n + r];
   }
-  s = block_sum(s, sh);
-  q = block_sum(q, sh);
+  s = egv_block_sum_256(s, sh);
+  q = egv_block_sum_256(q, sh);
   if (threadIdx.x == 0) {
     cstat[0 * n + c] = cmax;
     cstat[1 * n + c] = s;
@@ -267,47 +252,33 @@ __global__ __launch_bounds__(256) void egonce_grad_kernel(const float* __restric
     gx += g * xv;
   }
   if (ls_part) {                                                  // uniform over the workgroup
-    gx = block_sum(gx, sh);
+    gx = egv_block_sum_256(gx, sh);
     if (threadIdx.x == 0) ls_part[i] = gx;
   }
 }
 
-// dL/d(logit scale) = sum of the n row partials; one workgroup, double, fixed order
-__global__ __launch_bounds__(256) void egonce_scale_grad_kernel(const float* __restrict__ ls_part, int n,
-                                                                float* __restrict__ d_logit_scale) {
-  __shared__ double red[256];
-  const double s = egv_sum_partials_256(ls_part, n, red);
-  if (threadIdx.x == 0) d_logit_scale[0] = (float)s;
-}
-
-// E: loss scalar + embedding gradients.  Block i, thread d.
+// E: embedding gradients.  Block i, thread d: the host enforces D <= 256, one feature per thread.
 __global__ __launch_bounds__(256) void egonce_embgrad_kernel(const float* __restrict__ G, const float* __restrict__ tn,
                                                              const float* __restrict__ vn,
                                                              const float* __restrict__ stats, int n, int D, float eps,
                                                              float* __restrict__ d_text, float* __restrict__ d_video) {
   __shared__ float sh[4];
-  const int i = blockIdx.x;
+  const int i = blockIdx.x, d = threadIdx.x;
   const float nt = stats[i], nv = stats[n + i];
-  for (int d0 = 0; d0 < D; d0 += 256) {
-    const int d = d0 + threadIdx.x;
-    float gt = 0.f, gv = 0.f;
-    if (d < D) {
-      for (int j = 0; j < n; ++j) {
-        gt += G[(long)i * n + j] * vn[(long)j * D + d];
-        gv += G[(long)j * n + i] * tn[(long)j * D + d];
-      }
+  float gt = 0.f, gv = 0.f;
+  if (d < D) {
+    for (int j = 0; j < n; ++j) {
+      gt += G[(long)i * n + j] * vn[(long)j * D + d];
+      gv += G[(long)j * n + i] * tn[(long)j * D + d];
     }
-    // D <= 256 in the hot path; for larger D the projection term needs a full-row dot, handled below
-    if (D <= 256) {
-      const float th = d < D ? tn[(long)i * D + d] : 0.f;
-      const float vh = d < D ? vn[(long)i * D + d] : 0.f;
-      const float pt = block_sum(th * gt, sh);
-      const float pv = block_sum(vh * gv, sh);
-      if (d < D) {
-        if (d_text) d_text[(long)i * D + d] = nt > eps ? (gt - th * pt) / nt : gt / eps;
-        if (d_video) d_video[(long)i * D + d] = nv > eps ? (gv - vh * pv) / nv : gv / eps;
-      }
-    }
+  }
+  const float th = d < D ? tn[(long)i * D + d] : 0.f;
+  const float vh = d < D ? vn[(long)i * D + d] : 0.f;
+  const float pt = egv_block_sum_256(th * gt, sh);
+  const float pv = egv_block_sum_256(vh * gv, sh);
+  if (d < D) {
+    if (d_text) d_text[(long)i * D + d] = egv_norm_bwd(gt, th, pt, nt, eps);
+    if (d_video) d_video[(long)i * D + d] = egv_norm_bwd(gv, vh, pv, nv, eps);
   }
 }
 
@@ -317,7 +288,7 @@ __global__ __launch_bounds__(256) void egonce_loss_kernel(const float* __restric
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256)
     s += (__logf(rstat[2 * n + i]) - __logf(rstat[n + i])) + (__logf(cstat[2 * n + i]) - __logf(cstat[n + i]));
-  s = block_sum(s, sh);
+  s = egv_block_sum_256(s, sh);
   if (threadIdx.x == 0) loss[0] = -s / (float)n;
 }
 
@@ -348,8 +319,8 @@ static int egonce_head(const float* text, const float* video, const float* noun,
                      stats);
   EGV_CHECK_LAUNCH();
   const size_t lds = (size_t)(D + (noun ? dn + dv : 0)) * sizeof(float);
-  EGV_LAUNCH(egonce_rows_kernel, dim3(n), dim3(256), lds, s, tn, vn, noun, verb, stats, n, D, dn, dv, inv_tau,
-                     use_noun, use_verb, x, mask, rstat);
+  EGV_LAUNCH(egonce_rows_kernel, dim3(n), dim3(256), lds, s, tn, vn, noun, verb, stats, n, D, dn, dv, use_noun, use_verb, x,
+             mask);
   EGV_CHECK_LAUNCH();
   EGV_LAUNCH(egonce_rowstat_kernel, dim3(n), dim3(256), 0, s, x, mask, n, inv_tau, logit_scale, rstat);
   EGV_CHECK_LAUNCH();
@@ -362,7 +333,7 @@ static int egonce_head(const float* text, const float* video, const float* noun,
                d_logit_scale ? ls_part : nullptr);
     EGV_CHECK_LAUNCH();
     if (d_logit_scale) {
-      EGV_LAUNCH(egonce_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
+      EGV_LAUNCH(egv_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
       EGV_CHECK_LAUNCH();
     }
     EGV_LAUNCH(egonce_embgrad_kernel, dim3(n), dim3(256), 0, s, G, tn, vn, stats, n, D, eps, d_text, d_video);
@@ -442,7 +413,7 @@ static int egonce_from_sim(const float* x, const float* sim_v, const float* sim_
                d_logit_scale ? ls_part : nullptr);
     EGV_CHECK_LAUNCH();
     if (d_logit_scale) {
-      EGV_LAUNCH(egonce_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
+      EGV_LAUNCH(egv_scale_grad_kernel, dim3(1), dim3(256), 0, s, ls_part, n, d_logit_scale);
       EGV_CHECK_LAUNCH();
     }
   }
@@ -461,176 +432,4 @@ extern "C" int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const 
   if (!logit_scale || (dx && !d_logit_scale)) return EGV_ERR_ARG;
   return egonce_from_sim(x, sim_v, sim_n, n, 0.f, logit_scale, use_noun, use_verb, loss, dx, dx ? d_logit_scale : nullptr, work,
                          stream);
-}
-
-// ---- max-margin ranking losses (model/loss.py:55-133; the EPIC-MIR / Charades fine-tuning heads on the same similarity
-// matrix) ----------------------------------------------------------------------------------------------------------------
-//   loss = mean over the kept (i, j) of  relu(w_i m - x_ii + x_ij) + relu(w_i m - x_ii + x_ji)
-// (w_i = 1: MaxMarginRankingLoss; w_i = weight[i]: AdaptiveMaxMarginRankingLoss); fix_norm drops the diagonal pairs, so the
-// mean runs over 2 n (n - 1) terms instead of 2 n^2.  The gradient is local in x:
-//   d x_ab (a != b) = ( [w_a m - x_aa + x_ab > 0] + [w_b m - x_bb + x_ab > 0] ) / count
-//   d x_aa          = - sum_{j != a} ( [w_a m - x_aa + x_aj > 0] + [w_a m - x_aa + x_ja > 0] ) / count
-// One workgroup per row a; the loss is accumulated with one atomicAdd per row into a zeroed scalar.
-namespace {
-__global__ __launch_bounds__(256) void maxmargin_kernel(const float* __restrict__ x, const float* __restrict__ w, int n,
-                                                        float margin, int fix_norm, float inv_count,
-                                                        float* __restrict__ loss, float* __restrict__ dx) {
-  const int a = blockIdx.x;
-  const float xaa = x[(long)a * n + a];
-  const float ma = (w ? w[a] : 1.0f) * margin;
-  float lsum = 0.f, dsum = 0.f;
-  for (int j = threadIdx.x; j < n; j += blockDim.x) {
-    const float xaj = x[(long)a * n + j], xja = x[(long)j * n + a];
-    const float t1 = ma - xaa + xaj, t2 = ma - xaa + xja;
-    if (j != a) {
-      lsum += fmaxf(t1, 0.f) + fmaxf(t2, 0.f);
-      const float i1 = t1 > 0.f ? 1.f : 0.f, i2 = t2 > 0.f ? 1.f : 0.f;
-      dsum += i1 + i2;
-      if (dx) {
-        const float mj = (w ? w[j] : 1.0f) * margin;
-        const float t3 = mj - x[(long)j * n + j] + xaj;        // the column-direction term of row j that contains x_aj
-        dx[(long)a * n + j] = (i1 + (t3 > 0.f ? 1.f : 0.f)) * inv_count;
-      }
-    } else if (!fix_norm) {
-      lsum += 2.f * fmaxf(ma, 0.f);                             // x_aa cancels: constant terms, no gradient
-    }
-  }
-  __shared__ float red[2][4];
-  lsum = wave_sum(lsum);
-  dsum = wave_sum(dsum);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = lsum;
-    red[1][threadIdx.x >> 6] = dsum;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(loss, (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * inv_count);
-    if (dx) dx[(long)a * n + a] = -(red[1][0] + red[1][1] + red[1][2] + red[1][3]) * inv_count;
-  }
-}
-}  // namespace
-
-// ---- dual-softmax re-scaling of a retrieval similarity matrix (run/test_epic.py:137-143) ------------------------------------
-//   y = softmax(x / temp, dim = 1) * x        (row-wise prior: one wave per row, the row is streamed three times from L2)
-//   z = softmax(y, dim = 0)                   (column-wise: a workgroup owns 64 columns; lanes walk the rows coalesced)
-namespace {
-__global__ __launch_bounds__(256) void dual_softmax_rows_kernel(const float* __restrict__ x, int n, int m, float inv_temp,
-                                                                float* __restrict__ y) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float* xr = x + (long)row * m;
-  float mx = -3.0e38f;
-  for (int j = lane; j < m; j += 64) mx = fmaxf(mx, xr[j] * inv_temp);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < m; j += 64) sum += __expf(xr[j] * inv_temp - mx);
-  sum = wave_sum(sum);
-  const float inv = 1.0f / sum;
-  float* yr = y + (long)row * m;
-  for (int j = lane; j < m; j += 64) yr[j] = __expf(xr[j] * inv_temp - mx) * inv * xr[j];
-}
-
-__global__ __launch_bounds__(256) void dual_softmax_cols_kernel(const float* __restrict__ y, int n, int m, float* __restrict__ z) {
-  __shared__ float red[4][64];
-  const int col = blockIdx.x * 64 + (threadIdx.x & 63), part = threadIdx.x >> 6;
-  const bool live = col < m;
-  float mx = -3.0e38f;
-  for (int i = part; i < n; i += 4) if (live) mx = fmaxf(mx, y[(long)i * m + col]);
-  red[part][threadIdx.x & 63] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0][threadIdx.x & 63], red[1][threadIdx.x & 63]), fmaxf(red[2][threadIdx.x & 63], red[3][threadIdx.x & 63]));
-  __syncthreads();
-  float sum = 0.f;
-  for (int i = part; i < n; i += 4) if (live) sum += __expf(y[(long)i * m + col] - mx);
-  red[part][threadIdx.x & 63] = sum;
-  __syncthreads();
-  sum = red[0][threadIdx.x & 63] + red[1][threadIdx.x & 63] + red[2][threadIdx.x & 63] + red[3][threadIdx.x & 63];
-  const float inv = 1.0f / sum;
-  for (int i = part; i < n; i += 4) if (live) z[(long)i * m + col] = __expf(y[(long)i * m + col] - mx) * inv;
-}
-}  // namespace
-
-extern "C" int egv_dual_softmax(const float* x, int32_t n, int32_t m, float temp, float* work, float* out, void* stream) {
-  if (!x || !work || !out || n <= 0 || m <= 0 || !(temp > 0.f)) return EGV_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  EGV_LAUNCH(dual_softmax_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x, n, m, 1.0f / temp, work);
-  EGV_CHECK_LAUNCH();
-  EGV_LAUNCH(dual_softmax_cols_kernel, dim3((m + 63) / 64), dim3(256), 0, s, work, n, m, out);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
-extern "C" int egv_maxmargin_fwd_bwd(const float* x, const float* weight, int32_t n, float margin, int32_t fix_norm,
-                                     float* loss, float* dx, void* stream) {
-  if (!x || !loss || n <= 0 || n > 4096 || (fix_norm && n < 2)) return EGV_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) return EGV_ERR_LAUNCH;
-  const double count = fix_norm ? 2.0 * n * (n - 1.0) : 2.0 * n * (double)n;
-  EGV_LAUNCH(maxmargin_kernel, dim3(n), dim3(256), 0, s, x, weight, n, margin, fix_norm, (float)(1.0 / count), loss, dx);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
-}
-
-
-// ---- softmax cross-entropy of the classification fine-tunes (OSCC / PNR: model/loss.py:135-141 = nn.CrossEntropyLoss with its
-// defaults, mean over the targets != ignore_index; trainer/trainer_oscc.py:335-338 feeds it the [B, 2] / [B, 17] scores of
-// FrozenInTime(video_only=True) and int64 labels).  One workgroup: a wave per row (log-sum-exp by wave shuffles), the row losses
-// are summed in a fixed order through LDS, so the result is deterministic; d_logits = (softmax - onehot) / #valid.
-namespace {
-__global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits, long ld, const long long* __restrict__ target,
-                                                            int rows, int cols, long long ignore_index, float* __restrict__ loss,
-                                                            float* __restrict__ dlogits, long ldd) {
-  __shared__ float part[4];
-  __shared__ int cnt[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // pass 1: number of valid rows (the gradient scale), then pass 2: losses and gradients
-  // A label outside [0, cols) that is not ignore_index is an ERROR (torch raises a device assert): it must neither be skipped
-  // silently nor inflate the mean's denominator -- the loss comes back NaN (and the gradient of every row with it).
-  __shared__ int bad[4];
-  int nvalid = 0, nbad = 0;
-  for (int r = threadIdx.x; r < rows; r += 256) {
-    const long long t = target[r];
-    nvalid += (t != ignore_index);
-    nbad += (t != ignore_index && (t < 0 || t >= cols));
-  }
-  nvalid = (int)wave_sum((float)nvalid);
-  nbad = (int)wave_sum((float)nbad);
-  if (lane == 0) { cnt[wave] = nvalid; bad[wave] = nbad; }
-  __syncthreads();
-  const int valid = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-  const bool any_bad = (bad[0] + bad[1] + bad[2] + bad[3]) > 0;
-  const float inv = valid > 0 ? 1.0f / (float)valid : 0.f;
-  float acc = 0.f;
-  for (int r = wave; r < rows; r += 4) {
-    const float* x = logits + (long)r * ld;
-    const long long t = target[r];
-    const bool on = t != ignore_index && t >= 0 && t < cols;
-    float m = -3.0e38f;
-    for (int c = lane; c < cols; c += 64) m = fmaxf(m, x[c]);
-    m = wave_max(m);
-    float se = 0.f;
-    for (int c = lane; c < cols; c += 64) se += __expf(x[c] - m);
-    se = wave_sum(se);
-    const float lse = m + __logf(se);
-    if (on) acc += lse - x[t];
-    if (dlogits) {
-      float* d = dlogits + (long)r * ldd;
-      for (int c = lane; c < cols; c += 64)
-        d[c] = any_bad ? __builtin_nanf("") : (on ? (__expf(x[c] - lse) - (c == (int)t ? 1.f : 0.f)) * inv : 0.f);
-    }
-  }
-  if (lane == 0) part[wave] = acc;      // every lane of a wave holds the same acc
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = (valid > 0 && !any_bad) ? (part[0] + part[1] + part[2] + part[3]) * inv : __builtin_nanf("");
-}
-}  // namespace
-
-extern "C" int egv_cross_entropy_fwd_bwd(const float* logits, int64_t ld, const int64_t* target, int32_t rows, int32_t cols,
-                                         int64_t ignore_index, float* loss, float* dlogits, int64_t ldd, void* stream) {
-  if (!logits || !target || !loss || rows <= 0 || cols <= 0 || rows > (1 << 20) || cols > 65536 || ld < cols) return EGV_ERR_ARG;
-  if (dlogits && ldd < cols) return EGV_ERR_ARG;
-  EGV_LAUNCH(cross_entropy_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, (const long long*)target, rows, cols,
-             (long long)ignore_index, loss, dlogits, (long)ldd);
-  EGV_CHECK_LAUNCH();
-  return EGV_OK;
 }

@@ -1,6 +1,6 @@
 // Contrastive head for global batches past the 1 024 rows of egonce.hip: the same loss and the same gradients
-// (egonce.hip:8-11), with nothing of size n x n in memory.  The similarity tile X = A_I . B_J^T is formed on the fp32-input
-// MFMA (v_mfma_f32_16x16x4_f32: bit for bit an fp32 fma chain, so the numerics are those of the fp32 short head), the EgoNCE
+// (the formulas at the top of egonce.hip), with nothing of size n x n in memory.  The similarity tile X = A_I . B_J^T is formed on
+// the fp32-input MFMA (v_mfma_f32_16x16x4_f32: bit for bit an fp32 fma chain, so the numerics are those of the fp32 short head), the EgoNCE
 // mask comes from bit-packed noun / verb rows, and the row statistics are kept online while the column tiles stream through
 // LDS.  All arithmetic fp32; every reduction runs in a fixed order (no float atomics), so a call is deterministic.
 // The pieces the sigmoid head (sigmoid_head.hip) shares -- prep, the LDS tile, the mask tile, the X^T product, the split and finish --
@@ -23,7 +23,7 @@
 //           so dA_I += G_IJ . B_J runs on the same MFMA with B_J read from the LDS tile.  Launched twice with the roles
 //           swapped; raw partials per column range go to the workspace.
 //   finish  one workgroup per row: sums the partials in a fixed order and applies the backward of the normalisation
-//           (egonce.hip:281-282).
+//           (egv_norm_bwd).
 //   scale   learnable temperature only (egv_egonce_long_fwd_bwd_ls: 1 / tau = exp(s) read from the device by every kernel above):
 //           dL/ds = sum_ij G_ij X_ij.  In the grad walk with roles (tn, vn) the X^T fragment and G_IJ sit in the same registers, so
 //           each lane accumulates G X (masked exactly like G), the workgroup reduces and stores ONE partial per (row tile, column
@@ -34,7 +34,7 @@
 // and feeds element t to MFMA t, so MFMA t of chunk c sums k = 16 c + 4 (lane >> 4) + t; both operands use the same map, which
 // only permutes the order of the fma chain.  The second product uses the same trick on the OUTPUT column: MFMA t of a 64-wide
 // chunk produces d = 64 c + 4 (lane & 15) + t, so a lane ends with four consecutive d and stores 16 bytes.
-#include "common.h"
+#define EGV_SCALE_GRAD_KERNEL
 #include "egonce_tile.h"
 #include "egovlp_hip.h"
 
@@ -43,27 +43,17 @@ namespace {
 constexpr int EGL_STAT_WGS = 512;     // column ranges are chosen so that a launch has about this many workgroups (2 per CU)
 constexpr float EGL_NEG = -3e38f;
 
-struct EglLayout {
-  int np, Dp, wn, W, ntiles, tps_s, ns_s, tps_g, ns_g;
-  long tn, vn, words, norms, flags, spart, stat, gpart, lpart, total;   // offsets in floats
+struct EglLayout : EglPrepLayout {
+  int tps_s, ns_s, tps_g, ns_g;
+  long spart, stat, gpart, lpart;   // offsets in floats, behind the prep outputs
 };
 
 inline EglLayout egl_layout(int n, int D, int dn, int dv) {
-  EglLayout L;
-  L.np = (n + EGL_TILE - 1) / EGL_TILE * EGL_TILE;
-  L.Dp = D <= 64 ? 64 : 256;                         // the two widths the tile kernels are compiled for
-  L.wn = ((dn + 31) / 32 + 3) / 4 * 4;
-  L.W = L.wn + ((dv + 31) / 32 + 3) / 4 * 4;
-  L.ntiles = L.np / EGL_TILE;
+  EglLayout L{egl_prep_layout(n, D, dn, dv)};
   egl_split(L.ntiles, EGL_STAT_WGS, L.tps_s, L.ns_s);
   egl_split(L.ntiles, EGL_GRAD_WGS, L.tps_g, L.ns_g);
   const long np = L.np;
-  long o = 0;
-  L.tn = o;     o += np * L.Dp;
-  L.vn = o;     o += np * L.Dp;
-  L.words = o;  o += np * L.W;
-  L.norms = o;  o += 2 * np;
-  L.flags = o;  o += np;
+  long o = L.total;
   L.spart = o;  o += 2L * L.ns_s * 3 * np;
   L.stat = o;   o += 6 * np;
   L.gpart = o;  o += (long)L.ns_g * np * L.Dp;
@@ -282,17 +272,9 @@ __global__ __launch_bounds__(256, 2) void egl_grad_kernel(const float* __restric
     for (int rr = 0; rr < 4; ++rr)
       *(f32x4_t*)(out + (long)rr * DP + 64 * c) = (f32x4_t){acc[c][0][rr], acc[c][1][rr], acc[c][2][rr], acc[c][3][rr]};
   if (lpart) {                                        // uniform over the workgroup
-    gx = egl_block_sum(gx, sh);
+    gx = egv_block_sum_256(gx, sh);
     if (threadIdx.x == 0) lpart[(long)blockIdx.y * ntiles + blockIdx.x] = gx;
   }
-}
-
-// dL/d(logit scale): the grad walk's partials, one workgroup, double, fixed order
-__global__ __launch_bounds__(256) void egl_scale_grad_kernel(const float* __restrict__ lpart, int count,
-                                                             float* __restrict__ d_logit_scale) {
-  __shared__ double red[256];
-  const double s = egv_sum_partials_256(lpart, count, red);
-  if (threadIdx.x == 0) d_logit_scale[0] = (float)s;
 }
 
 template <int DP>
@@ -320,8 +302,6 @@ int egl_launch_grad(const EglLayout& L, const float* A, const float* B, const ui
   return EGV_OK;
 }
 
-#define EGL_BY_DP(fn, ...) (L.Dp == 64 ? fn<64>(__VA_ARGS__) : fn<256>(__VA_ARGS__))
-
 }  // namespace
 
 extern "C" int64_t egv_egonce_long_work_floats(int32_t n, int32_t D, int32_t dn, int32_t dv) {
@@ -341,21 +321,19 @@ static int egl_head(const float* text, const float* video, const float* noun, co
   const EglLayout L = egl_layout(n, D, dn, dv);
   float* tn = work + L.tn;
   float* vn = work + L.vn;
-  uint32_t* words = (uint32_t*)(work + L.words);
-  float* norms = work + L.norms;
-  float* flags = work + L.flags;
+  const uint32_t* words = (const uint32_t*)(work + L.words);
+  const float* norms = work + L.norms;
+  const float* flags = work + L.flags;
   float* spart = work + L.spart;
   float* stat = work + L.stat;
   float* gpart = work + L.gpart;
   float* lpart = d_logit_scale ? work + L.lpart : nullptr;
-  // the mode of egonce_rows_kernel: noun and verb, noun only, else verb (the reference's else-branch)
-  const int mode = !noun ? 0 : (use_noun && use_verb) ? 1 : use_noun ? 2 : 3;
+  const int mode = egl_mask_mode(noun, use_noun, use_verb);
   const long np = L.np;
 
-  EGV_LAUNCH(egl_prep_kernel, dim3(L.np), dim3(256), 0, s, text, video, noun, verb, n, L.np, D, L.Dp, dn, dv, L.wn, L.W, eps, tn,
-             vn, words, norms, flags);
-  EGV_CHECK_LAUNCH();
-  int rc = EGL_BY_DP(egl_launch_stats, L, tn, vn, words, n, mode, inv_tau, logit_scale, spart, s);
+  int rc = egl_launch_prep(L, text, video, noun, verb, n, D, dn, dv, eps, work, s);
+  if (rc != EGV_OK) return rc;
+  rc = EGL_BY_DP(egl_launch_stats, L, tn, vn, words, n, mode, inv_tau, logit_scale, spart, s);
   if (rc != EGV_OK) return rc;
   rc = EGL_BY_DP(egl_launch_stats, L, vn, tn, words, n, mode, inv_tau, logit_scale,
                   spart + (long)L.ns_s * 3 * np, s);
@@ -366,7 +344,7 @@ static int egl_head(const float* text, const float* video, const float* noun, co
     rc = EGL_BY_DP(egl_launch_grad, L, tn, vn, words, stat, stat + 3 * np, n, mode, inv_tau, logit_scale, gpart, lpart, s);
     if (rc != EGV_OK) return rc;
     if (lpart) {
-      EGV_LAUNCH(egl_scale_grad_kernel, dim3(1), dim3(256), 0, s, lpart, L.ns_g * L.ntiles, d_logit_scale);
+      EGV_LAUNCH(egv_scale_grad_kernel, dim3(1), dim3(256), 0, s, lpart, L.ns_g * L.ntiles, d_logit_scale);
       EGV_CHECK_LAUNCH();
     }
     EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns_g, tn, norms, L.np, D, L.Dp, eps, d_text);

@@ -3,20 +3,12 @@
 // X^T fragment product on the fp32-input MFMA, the column-range split and the finish kernel (sum of the partials + the backward
 // of the row normalisation).  The k order of the two products is described at the top of egonce_long.hip.
 #pragma once
-#include "common.h"
+#include "head_common.h"
 
 namespace {
 
 constexpr int EGL_TILE = 64;          // rows per tile (A rows per workgroup, B rows per LDS tile)
 constexpr int EGL_GRAD_WGS = 256;     // the gradient walks aim at this many workgroups: their partials cost memory and a pass
-
-__device__ __forceinline__ float egl_block_sum(float v, float* sh) {  // 256 threads
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 
 inline void egl_split(int ntiles, int target, int& tps, int& ns) {
   int want = (target + ntiles - 1) / ntiles;
@@ -26,6 +18,38 @@ inline void egl_split(int ntiles, int target, int& tps, int& ns) {
 }
 
 // ------------------------------------------------------------------------------------------------ prep
+// What the prep kernel writes, at the front of a tiled head's workspace; the head's own partial buffers follow from `total` on.
+struct EglPrepLayout {
+  int np, Dp, wn, W, ntiles;
+  long tn, vn, words, norms, flags, total;   // offsets in floats
+};
+
+inline EglPrepLayout egl_prep_layout(int n, int D, int dn, int dv) {
+  EglPrepLayout L;
+  L.np = (n + EGL_TILE - 1) / EGL_TILE * EGL_TILE;
+  L.Dp = D <= 64 ? 64 : 256;                         // the two widths the tile kernels are compiled for
+  L.wn = ((dn + 31) / 32 + 3) / 4 * 4;
+  L.W = L.wn + ((dv + 31) / 32 + 3) / 4 * 4;
+  L.ntiles = L.np / EGL_TILE;
+  const long np = L.np;
+  long o = 0;
+  L.tn = o;     o += np * L.Dp;
+  L.vn = o;     o += np * L.Dp;
+  L.words = o;  o += np * L.W;
+  L.norms = o;  o += 2 * np;
+  L.flags = o;  o += np;
+  L.total = o;
+  return L;
+}
+
+// the kernel of a launcher template fn<DP>, by the layout L in scope
+#define EGL_BY_DP(fn, ...) (L.Dp == 64 ? fn<64>(__VA_ARGS__) : fn<256>(__VA_ARGS__))
+
+// the mask mode of egl_mask_tile, as egonce_rows_kernel picks it: noun and verb, noun only, else verb (the reference's else-branch)
+inline int egl_mask_mode(const float* noun, int use_noun, int use_verb) {
+  return !noun ? 0 : (use_noun && use_verb) ? 1 : use_noun ? 2 : 3;
+}
+
 __global__ __launch_bounds__(256) void egl_prep_kernel(const float* __restrict__ text, const float* __restrict__ video,
                                                        const float* __restrict__ noun, const float* __restrict__ verb, int n,
                                                        int np, int D, int Dp, int dn, int dv, int wn, int W, float eps,
@@ -54,8 +78,8 @@ __global__ __launch_bounds__(256) void egl_prep_kernel(const float* __restrict__
     st += a * a;
     sv += b * b;
   }
-  const float nt = sqrtf(egl_block_sum(st, sh));
-  const float nv = sqrtf(egl_block_sum(sv, sh));
+  const float nt = sqrtf(egv_block_sum_256(st, sh));
+  const float nv = sqrtf(egv_block_sum_256(sv, sh));
   const float ct = fmaxf(nt, eps), cv = fmaxf(nv, eps);
   for (int d = threadIdx.x; d < Dp; d += 256) {
     tn[(long)i * Dp + d] = d < D ? text[(long)i * D + d] / ct : 0.f;
@@ -91,6 +115,14 @@ __global__ __launch_bounds__(256) void egl_prep_kernel(const float* __restrict__
     norms[np + i] = nv;
     flags[i] = bad ? 1.f : 0.f;
   }
+}
+
+inline int egl_launch_prep(const EglPrepLayout& L, const float* text, const float* video, const float* noun, const float* verb,
+                           int n, int D, int dn, int dv, float eps, float* work, hipStream_t s) {
+  EGV_LAUNCH(egl_prep_kernel, dim3(L.np), dim3(256), 0, s, text, video, noun, verb, n, L.np, D, L.Dp, dn, dv, L.wn, L.W, eps,
+             work + L.tn, work + L.vn, (uint32_t*)(work + L.words), work + L.norms, work + L.flags);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ tile pieces
@@ -165,7 +197,7 @@ __device__ __forceinline__ void egl_xt(const float* bt, const f32x4_t (&a)[DP / 
   }
 }
 
-// sum of the column-range partials in a fixed order + the backward of the row normalisation (egonce.hip:281-282)
+// sum of the column-range partials in a fixed order + the backward of the row normalisation (egv_norm_bwd)
 __global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict__ gpart, int ns, const float* __restrict__ an,
                                                          const float* __restrict__ norms, int np, int D, int Dp, float eps,
                                                          float* __restrict__ out) {
@@ -176,9 +208,9 @@ __global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict
     for (int r = 0; r < ns; ++r) gsum += gpart[((long)r * np + i) * Dp + d];
     th = an[(long)i * Dp + d];
   }
-  const float proj = egl_block_sum(th * gsum, sh);
+  const float proj = egv_block_sum_256(th * gsum, sh);
   const float nrm = norms[i];
-  if (d < D) out[(long)i * D + d] = nrm > eps ? (gsum - th * proj) / nrm : gsum / eps;
+  if (d < D) out[(long)i * D + d] = egv_norm_bwd(gsum, th, proj, nrm, eps);
 }
 
 inline bool egl_args_ok(int n, int D, int dn, int dv) {

@@ -18,18 +18,11 @@
 //   C  mmh_loss_kernel   the per-row partial losses, summed in a fixed order.
 // Deterministic: no floating-point atomics, every sum has a fixed order (lane-xor trees inside a wave, waves 0..3 in LDS, rows by
 // index).  fp32 throughout, wave64, launch arguments only (capture-safe), no host synchronisation.
-#include "common.h"
+// The same losses on a GIVEN similarity matrix (egv_maxmargin_fwd_bwd, the API-compatible path) are at the end of the file.
+#include "head_common.h"
 #include "egovlp_hip.h"
 
 namespace {
-
-__device__ __forceinline__ float mmh_block_sum(float v, float* sh) {  // 256 threads, fixed order
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 
 __device__ __forceinline__ float dot4(const f32x4_t a, const f32x4_t b) {
   return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
@@ -44,14 +37,14 @@ __global__ __launch_bounds__(256) void mmh_norm_kernel(const float* __restrict__
   const int d = threadIdx.x;                  // D <= 256: one feature per thread
   const float a = d < D ? text[(long)i * D + d] : 0.f;
   const float b = d < D ? video[(long)i * D + d] : 0.f;
-  const float nt = sqrtf(mmh_block_sum(a * a, sh));
-  const float nv = sqrtf(mmh_block_sum(b * b, sh));
+  const float nt = sqrtf(egv_block_sum_256(a * a, sh));
+  const float nv = sqrtf(egv_block_sum_256(b * b, sh));
   const float ta = a / fmaxf(nt, eps), vb = b / fmaxf(nv, eps);
   if (d < D) {
     tn[(long)i * D + d] = ta;
     vn[(long)i * D + d] = vb;
   }
-  const float xii = mmh_block_sum(ta * vb, sh);
+  const float xii = egv_block_sum_256(ta * vb, sh);
   if (threadIdx.x == 0) {
     stats[i] = nt;
     stats[n + i] = nv;
@@ -114,13 +107,13 @@ __global__ __launch_bounds__(256) void mmh_rows_kernel(const float* __restrict__
   const float gaa = -dsum * inv_count;                   // G[a, a]
   g_t += gaa * va;
   g_v += gaa * ta;
-  // through t / max(|t|, eps): (g - tn <tn, g>) / |t| above the clamp, g / eps below it
+  // through t / max(|t|, eps)
   const float pt = wave_sum(dot4(ta, g_t));
   const float pv = wave_sum(dot4(va, g_v));
   const float nt = stats[a], nv = stats[n + a];
   if (on) {
-    if (d_text) *(f32x4_t*)(d_text + (long)a * D + d) = nt > eps ? (g_t - ta * pt) / nt : g_t / eps;
-    if (d_video) *(f32x4_t*)(d_video + (long)a * D + d) = nv > eps ? (g_v - va * pv) / nv : g_v / eps;
+    if (d_text) *(f32x4_t*)(d_text + (long)a * D + d) = egv_norm_bwd(g_t, ta, pt, nt, eps);
+    if (d_video) *(f32x4_t*)(d_video + (long)a * D + d) = egv_norm_bwd(g_v, va, pv, nv, eps);
   }
   if (lane == 0) rowloss[a] = (lsum + (fix_norm ? 0.f : 2.f * fmaxf(ma, 0.f))) * inv_count;
 }
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(256) void mmh_loss_kernel(const float* __restrict__
   __shared__ float sh[4];
   float s = 0.f;
   for (int a = threadIdx.x; a < n; a += 256) s += rowloss[a];
-  s = mmh_block_sum(s, sh);
+  s = egv_block_sum_256(s, sh);
   if (threadIdx.x == 0) loss[0] = s;
 }
 
@@ -159,6 +152,64 @@ extern "C" int egv_maxmargin_head_fwd_bwd(const float* text, const float* video,
              d_video, rowloss);
   EGV_CHECK_LAUNCH();
   EGV_LAUNCH(mmh_loss_kernel, dim3(1), dim3(256), 0, s, rowloss, n, loss);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+// ---- max-margin ranking losses (model/loss.py:55-133; the EPIC-MIR / Charades fine-tuning heads on the same similarity
+// matrix) ----------------------------------------------------------------------------------------------------------------
+//   loss = mean over the kept (i, j) of  relu(w_i m - x_ii + x_ij) + relu(w_i m - x_ii + x_ji)
+// (w_i = 1: MaxMarginRankingLoss; w_i = weight[i]: AdaptiveMaxMarginRankingLoss); fix_norm drops the diagonal pairs, so the
+// mean runs over 2 n (n - 1) terms instead of 2 n^2.  The gradient is local in x:
+//   d x_ab (a != b) = ( [w_a m - x_aa + x_ab > 0] + [w_b m - x_bb + x_ab > 0] ) / count
+//   d x_aa          = - sum_{j != a} ( [w_a m - x_aa + x_aj > 0] + [w_a m - x_aa + x_ja > 0] ) / count
+// One workgroup per row a; the loss is accumulated with one atomicAdd per row into a zeroed scalar.
+namespace {
+__global__ __launch_bounds__(256) void maxmargin_kernel(const float* __restrict__ x, const float* __restrict__ w, int n,
+                                                        float margin, int fix_norm, float inv_count,
+                                                        float* __restrict__ loss, float* __restrict__ dx) {
+  const int a = blockIdx.x;
+  const float xaa = x[(long)a * n + a];
+  const float ma = (w ? w[a] : 1.0f) * margin;
+  float lsum = 0.f, dsum = 0.f;
+  for (int j = threadIdx.x; j < n; j += blockDim.x) {
+    const float xaj = x[(long)a * n + j], xja = x[(long)j * n + a];
+    const float t1 = ma - xaa + xaj, t2 = ma - xaa + xja;
+    if (j != a) {
+      lsum += fmaxf(t1, 0.f) + fmaxf(t2, 0.f);
+      const float i1 = t1 > 0.f ? 1.f : 0.f, i2 = t2 > 0.f ? 1.f : 0.f;
+      dsum += i1 + i2;
+      if (dx) {
+        const float mj = (w ? w[j] : 1.0f) * margin;
+        const float t3 = mj - x[(long)j * n + j] + xaj;        // the column-direction term of row j that contains x_aj
+        dx[(long)a * n + j] = (i1 + (t3 > 0.f ? 1.f : 0.f)) * inv_count;
+      }
+    } else if (!fix_norm) {
+      lsum += 2.f * fmaxf(ma, 0.f);                             // x_aa cancels: constant terms, no gradient
+    }
+  }
+  __shared__ float red[2][4];
+  lsum = wave_sum(lsum);
+  dsum = wave_sum(dsum);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = lsum;
+    red[1][threadIdx.x >> 6] = dsum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(loss, (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * inv_count);
+    if (dx) dx[(long)a * n + a] = -(red[1][0] + red[1][1] + red[1][2] + red[1][3]) * inv_count;
+  }
+}
+}  // namespace
+
+extern "C" int egv_maxmargin_fwd_bwd(const float* x, const float* weight, int32_t n, float margin, int32_t fix_norm,
+                                     float* loss, float* dx, void* stream) {
+  if (!x || !loss || n <= 0 || n > 4096 || (fix_norm && n < 2)) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) return EGV_ERR_LAUNCH;
+  const double count = fix_norm ? 2.0 * n * (n - 1.0) : 2.0 * n * (double)n;
+  EGV_LAUNCH(maxmargin_kernel, dim3(n), dim3(256), 0, s, x, weight, n, margin, fix_norm, (float)(1.0 / count), loss, dx);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }

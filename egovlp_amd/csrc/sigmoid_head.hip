@@ -1,8 +1,8 @@
 // Pairwise sigmoid contrastive head (SigLIP: Zhai et al. 2023) with EgoNCE's positives, for any n in [1, 65 536]:
 //   tn_i = text_i / max(|text_i|, eps), vn_j likewise;   x_ij = tn_i . vn_j;   t = exp(s);   u_ij = t x_ij + b
 //   z_ij = +1 where m_ij, else -1;   L = (1 / n) sum_ij softplus(-z_ij u_ij)
-// with m the mask of the EgoNCE heads (egonce_long.hip:14-16; no noun / verb vectors: m = I, plain SigLIP), s the logit scale and
-// b the logit bias, both read from the DEVICE.  With p_ij = sigmoid(-z_ij u_ij):
+// with m the mask of the EgoNCE heads (the stats step at the top of egonce_long.hip; no noun / verb vectors: m = I, plain SigLIP),
+// s the logit scale and b the logit bias, both read from the DEVICE.  With p_ij = sigmoid(-z_ij u_ij):
 //   G_ij = dL/dx_ij = -(t / n) z_ij p_ij;   d tn = G vn,  d vn = G^T tn (+ the backward of the normalisation)
 //   dL/ds = sum_ij G_ij x_ij;   dL/db = -(1 / n) sum_ij z_ij p_ij
 // Every pair is its own binary decision, so there are no row or column statistics: loss and gradient come out of ONE walk of the
@@ -21,7 +21,6 @@
 //
 // egv_sigmoid_from_sim is the same loss on a GIVEN similarity matrix (mask = sim_v * sim_n + I > 0, as egv_egonce_from_sim forms it):
 // one element-wise pass with block partials and the same reduce.
-#include "common.h"
 #include "egonce_tile.h"
 #include "egovlp_hip.h"
 
@@ -31,26 +30,16 @@ constexpr int SIG_WALK_WGS = 512;      // column ranges are chosen so that a wal
                                        // what its registers allow (the gradient partials of 512 workgroups are 32 MB at 4 096 rows)
 constexpr int SIG_SIM_BLOCKS = 1024;    // from_sim: at most this many blocks, each with one partial of the three sums
 
-struct SigLayout {
-  int np, Dp, wn, W, ntiles, tps, ns;
-  long tn, vn, words, norms, flags, gpart, lpart, total;   // offsets in floats
+struct SigLayout : EglPrepLayout {
+  int tps, ns;
+  long gpart, lpart;   // offsets in floats, behind the prep outputs
 };
 
 inline SigLayout sig_layout(int n, int D, int dn, int dv) {
-  SigLayout L;
-  L.np = (n + EGL_TILE - 1) / EGL_TILE * EGL_TILE;
-  L.Dp = D <= 64 ? 64 : 256;                         // the two widths the tile kernels are compiled for
-  L.wn = ((dn + 31) / 32 + 3) / 4 * 4;
-  L.W = L.wn + ((dv + 31) / 32 + 3) / 4 * 4;
-  L.ntiles = L.np / EGL_TILE;
+  SigLayout L{egl_prep_layout(n, D, dn, dv)};
   egl_split(L.ntiles, SIG_WALK_WGS, L.tps, L.ns);
   const long np = L.np;
-  long o = 0;
-  L.tn = o;     o += np * L.Dp;
-  L.vn = o;     o += np * L.Dp;
-  L.words = o;  o += np * L.W;
-  L.norms = o;  o += 2 * np;
-  L.flags = o;  o += np;
+  long o = L.total;
   L.gpart = o;  o += (long)L.ns * np * L.Dp;
   L.lpart = o;  o += 3L * L.ns * L.ntiles;           // loss, sum G x, sum z p: one partial of each per workgroup of the walk
   L.total = o;
@@ -155,9 +144,9 @@ __global__ __launch_bounds__(256, 2) void sig_walk_kernel(const float* __restric
   }
   if constexpr (SUMS) {
     const long cnt = (long)gridDim.y * ntiles, at = (long)blockIdx.y * ntiles + blockIdx.x;
-    ls = egl_block_sum(ls, sh);
-    gx = egl_block_sum(gx, sh);
-    zs = egl_block_sum(zs, sh);
+    ls = egv_block_sum_256(ls, sh);
+    gx = egv_block_sum_256(gx, sh);
+    zs = egv_block_sum_256(zs, sh);
     if (threadIdx.x == 0) {
       lpart[at] = ls;
       lpart[cnt + at] = gx;
@@ -218,9 +207,9 @@ __global__ __launch_bounds__(256) void sig_from_sim_kernel(const float* __restri
     zs += zp;
     if (dx) dx[i] = gv;
   }
-  ls = egl_block_sum(ls, sh);
-  gx = egl_block_sum(gx, sh);
-  zs = egl_block_sum(zs, sh);
+  ls = egv_block_sum_256(ls, sh);
+  gx = egv_block_sum_256(gx, sh);
+  zs = egv_block_sum_256(zs, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = ls;
     part[gridDim.x + blockIdx.x] = gx;
@@ -228,23 +217,18 @@ __global__ __launch_bounds__(256) void sig_from_sim_kernel(const float* __restri
   }
 }
 
-template <int DP, bool GRAD, bool SUMS>
-int sig_launch_walk(const SigLayout& L, const float* A, const float* B, const uint32_t* words, int n, int mode,
+// grad: with the second product (gpart); sums: with the loss, scale and bias partials (lpart).  A walk with neither has no output.
+template <int DP>
+int sig_launch_walk(const SigLayout& L, bool grad, bool sums, const float* A, const float* B, const uint32_t* words, int n, int mode,
                     const float* logit_scale, const float* logit_bias, float* gpart, float* lpart, hipStream_t s) {
   constexpr int lds = EGL_TILE * (DP + 4) * 4 + EGL_TILE * 4 * 4;
-  auto k = sig_walk_kernel<DP, GRAD, SUMS>;
+  if (!grad && !sums) return EGV_ERR_ARG;
+  auto k = !grad ? sig_walk_kernel<DP, false, true> : sums ? sig_walk_kernel<DP, true, true> : sig_walk_kernel<DP, true, false>;
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   EGV_LAUNCH(k, dim3(L.ntiles, L.ns), dim3(256), lds, s, A, B, words, n, L.np, L.W, L.wn, mode, logit_scale, logit_bias, L.tps,
              gpart, lpart);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
-}
-
-template <bool GRAD, bool SUMS>
-int sig_walk(const SigLayout& L, const float* A, const float* B, const uint32_t* words, int n, int mode, const float* logit_scale,
-             const float* logit_bias, float* gpart, float* lpart, hipStream_t s) {
-  return L.Dp == 64 ? sig_launch_walk<64, GRAD, SUMS>(L, A, B, words, n, mode, logit_scale, logit_bias, gpart, lpart, s)
-                    : sig_launch_walk<256, GRAD, SUMS>(L, A, B, words, n, mode, logit_scale, logit_bias, gpart, lpart, s);
 }
 
 }  // namespace
@@ -269,26 +253,24 @@ extern "C" int egv_sigmoid_head_fwd_bwd(const float* text, const float* video, c
   const SigLayout L = sig_layout(n, D, dn, dv);
   float* tn = work + L.tn;
   float* vn = work + L.vn;
-  uint32_t* words = (uint32_t*)(work + L.words);
-  float* norms = work + L.norms;
-  float* flags = work + L.flags;
+  const uint32_t* words = (const uint32_t*)(work + L.words);
+  const float* norms = work + L.norms;
+  const float* flags = work + L.flags;
   float* gpart = work + L.gpart;
   float* lpart = work + L.lpart;
-  // the mode of the EgoNCE heads: noun and verb, noun only, else verb (the reference's else-branch)
-  const int mode = !noun ? 0 : (use_noun && use_verb) ? 1 : use_noun ? 2 : 3;
+  const int mode = egl_mask_mode(noun, use_noun, use_verb);
 
-  EGV_LAUNCH(egl_prep_kernel, dim3(L.np), dim3(256), 0, s, text, video, noun, verb, n, L.np, D, L.Dp, dn, dv, L.wn, L.W, eps, tn,
-             vn, words, norms, flags);
-  EGV_CHECK_LAUNCH();
-  int rc = d_text ? sig_walk<true, true>(L, tn, vn, words, n, mode, logit_scale, logit_bias, gpart, lpart, s)
-                  : sig_walk<false, true>(L, tn, vn, words, n, mode, logit_scale, logit_bias, nullptr, lpart, s);
+  int rc = egl_launch_prep(L, text, video, noun, verb, n, D, dn, dv, eps, work, s);
+  if (rc != EGV_OK) return rc;
+  rc = EGL_BY_DP(sig_launch_walk, L, d_text != nullptr, true, tn, vn, words, n, mode, logit_scale, logit_bias,
+                 d_text ? gpart : nullptr, lpart, s);
   if (rc != EGV_OK) return rc;
   EGV_LAUNCH(sig_reduce_kernel, dim3(1), dim3(256), 0, s, lpart, L.ns * L.ntiles, n, flags, loss, d_scale, d_bias);
   EGV_CHECK_LAUNCH();
   if (d_text) {
     EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns, tn, norms, L.np, D, L.Dp, eps, d_text);
     EGV_CHECK_LAUNCH();
-    rc = sig_walk<true, false>(L, vn, tn, words, n, mode, logit_scale, logit_bias, gpart, nullptr, s);
+    rc = EGL_BY_DP(sig_launch_walk, L, true, false, vn, tn, words, n, mode, logit_scale, logit_bias, gpart, nullptr, s);
     if (rc != EGV_OK) return rc;
     EGV_LAUNCH(egl_finish_kernel, dim3(n), dim3(256), 0, s, gpart, L.ns, vn, norms + L.np, L.np, D, L.Dp, eps, d_video);
     EGV_CHECK_LAUNCH();

@@ -1,11 +1,107 @@
-"""Tensor-level wrappers of the contrastive-head kernels (include/egovlp_hip.h: egv_sim_matrix_*,
-egv_egonce_from_sim, egv_egonce_fwd_bwd and their *_ls variants, egv_sigmoid_from_sim, egv_maxmargin_fwd_bwd, egv_maxmargin_head_fwd_bwd) and of the classification head of
-the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
+"""Tensor-level wrappers of the loss heads (include/egovlp_hip.h): the one-call heads egv_egonce_fwd_bwd, egv_egonce_long_fwd_bwd
+(and their *_ls variants), egv_sigmoid_head_fwd_bwd and egv_maxmargin_head_fwd_bwd; the API-compatible pieces egv_sim_matrix_*,
+egv_egonce_from_sim(_ls), egv_sigmoid_from_sim, egv_maxmargin_fwd_bwd, egv_dual_softmax, egv_cross_entropy_fwd_bwd; and the
+classification head of the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
 import torch
 
 from . import _lib, ops
 from ._lib import check
 from .ops import _p
+
+
+def _one_fp32_arg(value, like, name):
+    """A head parameter read on the device (the logit scale s = log(1 / tau), the logit bias): one fp32 on the inputs' device.
+    Returns a view of `value` (one element is always contiguous): its address stays valid as long as the caller's tensor."""
+    v = value.detach()
+    if v.dtype != torch.float32 or v.numel() != 1 or v.device != like.device:
+        raise ValueError("%s must be one fp32 value on the device of the embeddings" % name)
+    return v
+
+
+def _head_buffers(text, video, work_floats, want_grads, param_grads=0, want_param_grads=True):
+    """What every one-call head writes: loss[1], its workspace, d_text / d_video and a list of `param_grads` parameter gradients
+    of [1] each; the gradients are None without want_grads, those of the parameters also without want_param_grads."""
+    dev = text.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    work = torch.empty(work_floats, dtype=torch.float32, device=dev)
+    dt = torch.empty_like(text) if want_grads else None
+    dv = torch.empty_like(video) if want_grads else None
+    want_param_grads = want_grads and want_param_grads
+    return loss, work, dt, dv, [torch.empty(1, dtype=torch.float32, device=dev) if want_param_grads else None
+                                for _ in range(param_grads)]
+
+
+def _nv_widths(noun, verb):
+    return (noun.shape[1] if noun is not None else 0), (verb.shape[1] if verb is not None else 0)
+
+
+EGONCE_SHORT_MAX = 1024      # rows of egv_egonce_fwd_bwd; egonce_fwd_bwd switches to the long head past it
+EGONCE_LONG_MAX = 65536      # rows of egv_egonce_long_fwd_bwd
+
+
+def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                   want_sim=False, logit_scale=None):
+    """The contrastive head in one call -> (loss[1], sim or None, d_text, d_video).  Up to EGONCE_SHORT_MAX rows: the latency-bound
+    kernels of csrc/egonce.hip; beyond: egonce_long_fwd_bwd (no n x n matrix exists there, so `want_sim` is refused).
+    `logit_scale` (a device tensor holding s = log(1 / tau); `temperature` is then unused): the kernels form 1 / tau = exp(s) on the
+    device and the call returns a fifth value, d_logit_scale [1] = dL/ds (None without want_grads) -- egv_egonce_fwd_bwd_ls."""
+    ops._need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    if n > EGONCE_SHORT_MAX:
+        if want_sim:
+            raise ValueError("egonce_fwd_bwd: want_sim needs n <= %d (the long head materialises no n x n matrix), got n = %d"
+                             % (EGONCE_SHORT_MAX, n))
+        out = egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=eps, use_noun=use_noun, use_verb=use_verb,
+                                  want_grads=want_grads, logit_scale=logit_scale)
+        return (out[0], None) + tuple(out[1:])
+    dn, dv = _nv_widths(noun, verb)
+    learn = logit_scale is not None
+    entry = "egv_egonce_fwd_bwd_ls" if learn else "egv_egonce_fwd_bwd"
+    tau = _p(_one_fp32_arg(logit_scale, text, "logit_scale")) if learn else float(temperature)
+    loss, work, dt, dvv, dls = _head_buffers(text, video, _lib.lib().egv_egonce_work_floats(n, D), want_grads, int(learn))
+    sim = torch.empty((n, n), dtype=torch.float32, device=text.device) if want_sim else None
+    check(getattr(_lib.lib(), entry)(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, tau, float(eps), int(use_noun),
+                                     int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv), *map(_p, dls), _p(work),
+                                     ops._stream(text)), entry)
+    return (loss, sim, dt, dvv, *dls)
+
+
+def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                        logit_scale=None):
+    """egv_egonce_long_fwd_bwd for ANY n in [1, 65536] -> (loss[1], d_text, d_video): the tiled fp32-MFMA head with a workspace
+    linear in n.  noun / verb: non-negative multi-hots (only entry > 0 is used); a negative or NaN entry makes the loss NaN.
+    `logit_scale`: as in egonce_fwd_bwd -> (loss[1], d_text, d_video, d_logit_scale [1]) -- egv_egonce_long_fwd_bwd_ls."""
+    ops._need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    dn, dv = _nv_widths(noun, verb)
+    learn = logit_scale is not None
+    entry = "egv_egonce_long_fwd_bwd_ls" if learn else "egv_egonce_long_fwd_bwd"
+    tau = _p(_one_fp32_arg(logit_scale, text, "logit_scale")) if learn else float(temperature)
+    loss, work, dt, dvv, dls = _head_buffers(text, video, _lib.lib().egv_egonce_long_work_floats(n, D, dn, dv), want_grads,
+                                             int(learn))
+    check(getattr(_lib.lib(), entry)(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, tau, float(eps), int(use_noun),
+                                     int(use_verb), _p(loss), _p(dt), _p(dvv), *map(_p, dls), _p(work), ops._stream(text)), entry)
+    return (loss, dt, dvv, *dls)
+
+
+def sigmoid_head_fwd_bwd(text, video, noun, verb, logit_scale, logit_bias, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                         want_param_grads=True):
+    """egv_sigmoid_head_fwd_bwd, the pairwise sigmoid head with EgoNCE's positives (noun / verb None: mask = I, plain SigLIP), for
+    ANY n in [1, 65536] -> (loss[1], d_text, d_video, d_scale[1], d_bias[1]).  `logit_scale` (s) and `logit_bias` (b) are device
+    tensors of one fp32 each: u = exp(s) x + b is formed on the device.  want_grads=False: the loss alone, the four gradients are
+    None; want_param_grads=False (fixed s and b): d_scale and d_bias are None.  noun / verb: non-negative multi-hots (only
+    entry > 0 is used); a negative or NaN entry makes the loss NaN."""
+    ops._need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    dn, dv = _nv_widths(noun, verb)
+    ls = _one_fp32_arg(logit_scale, text, "logit_scale")
+    lb = _one_fp32_arg(logit_bias, text, "logit_bias")
+    loss, work, dt, dvv, (dls, dlb) = _head_buffers(text, video, _lib.lib().egv_sigmoid_head_work_floats(n, D, dn, dv),
+                                                    want_grads, 2, want_param_grads)
+    check(_lib.lib().egv_sigmoid_head_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), _p(lb), float(eps),
+                                              int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(dls), _p(dlb), _p(work),
+                                              ops._stream(text)), "egv_sigmoid_head_fwd_bwd")
+    return loss, dt, dvv, dls, dlb
 
 
 def sim_fwd(a, b, eps):
@@ -47,17 +143,14 @@ def egonce_from_sim(x, sim_v, sim_n, temperature, use_noun, use_verb, want_grad=
     dx = torch.empty_like(x) if want_grad else None
     sv = sim_v.contiguous() if sim_v is not None else None
     sn = sim_n.contiguous() if sim_n is not None else None
-    if logit_scale is not None:
-        ls = ops._logit_scale_arg(logit_scale, x)
-        work = torch.empty(n * n + 7 * n, dtype=torch.float32, device=dev)
-        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
-        check(_lib.lib().egv_egonce_from_sim_ls(_p(x), _p(sv), _p(sn), n, _p(ls), int(use_noun), int(use_verb), _p(loss), _p(dx),
-                                                _p(dls), _p(work), ops._stream()), "egv_egonce_from_sim_ls")
-        return loss, dx, dls
-    work = torch.empty(n * n + 6 * n, dtype=torch.float32, device=dev)
-    check(_lib.lib().egv_egonce_from_sim(_p(x), _p(sv), _p(sn), n, float(temperature), int(use_noun), int(use_verb),
-                                         _p(loss), _p(dx), _p(work), ops._stream()), "egv_egonce_from_sim")
-    return loss, dx
+    learn = logit_scale is not None
+    entry = "egv_egonce_from_sim_ls" if learn else "egv_egonce_from_sim"
+    tau = _p(_one_fp32_arg(logit_scale, x, "logit_scale")) if learn else float(temperature)
+    work = torch.empty(n * n + (7 if learn else 6) * n, dtype=torch.float32, device=dev)
+    dls = [torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None] if learn else []
+    check(getattr(_lib.lib(), entry)(_p(x), _p(sv), _p(sn), n, tau, int(use_noun), int(use_verb), _p(loss), _p(dx), *map(_p, dls),
+                                     _p(work), ops._stream()), entry)
+    return (loss, dx, *dls)
 
 
 def sigmoid_from_sim(x, sim_v, sim_n, logit_scale, logit_bias, use_noun, use_verb, want_grad=True, want_param_grads=True):
@@ -70,8 +163,8 @@ def sigmoid_from_sim(x, sim_v, sim_n, logit_scale, logit_bias, use_noun, use_ver
     if x.dim() != 2 or x.shape[1] != n:
         raise ValueError("SigmoidLoss / EgoSigmoidLoss need a square similarity matrix")
     dev = x.device
-    ls = ops._one_fp32_arg(logit_scale, x, "logit_scale")
-    lb = ops._one_fp32_arg(logit_bias, x, "logit_bias")
+    ls = _one_fp32_arg(logit_scale, x, "logit_scale")
+    lb = _one_fp32_arg(logit_bias, x, "logit_bias")
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dx = torch.empty_like(x) if want_grad else None
     dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grad and want_param_grads else None

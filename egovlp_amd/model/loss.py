@@ -1,6 +1,6 @@
 """EgoNCE / NormSoftmaxLoss -- drop-in for the reference's model/loss.py:7-53.
 
-Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip):
+Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip, through the wrappers of egovlp_amd/loss_ops.py):
   * the reference's own call shape  `loss(sim_matrix(text, video), sim_v, sim_n)`  (model/loss.py:34,
     trainer/trainer_egoclip.py:130-137): `forward` below, an autograd node over egv_egonce_from_sim;
   * the fused hot path  `loss.fused(text, video, noun, verb)`: ONE call computes the three similarity
@@ -13,122 +13,112 @@ learnable logit scale AND bias (_SigmoidMixin): `forward` over egv_sigmoid_from_
 (csrc/sigmoid_head.hip: one tile walk per direction for any n up to 65 536).
 MaxMarginRankingLoss (:55-90) and AdaptiveMaxMarginRankingLoss (:92-133), the EPIC-MIR / Charades fine-tuning heads over the
 same similarity matrix, run on egv_maxmargin_fwd_bwd; their `fused(text, video[, weight])` is the one-call head
-of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic).  CrossEntropy (:135-141), the loss of the OSCC / PNR
+of the fine-tuning step (egv_maxmargin_head_fwd_bwd: similarity, loss and both embedding gradients, deterministic; both in
+csrc/maxmargin_head.hip).  CrossEntropy (:135-141), the loss of the OSCC / PNR
 classification fine-tunes on the [B, classes] scores of FrozenInTime(video_only=True) (trainer/trainer_oscc.py:335-338), runs on
-egv_cross_entropy_fwd_bwd; its `fused(feats, weight, bias, target[, state])` is the whole head of those steps on ONE autograd
-node: the narrow projection (egv_cls_head_fwd), one packed collective, loss and backward (egv_cls_head_loss_bwd).
+egv_cross_entropy_fwd_bwd (csrc/cls_head.hip); its `fused(feats, weight, bias, target[, state])` is the whole head of those steps
+on an autograd node of its own: the narrow projection (egv_cls_head_fwd), one packed collective, loss and backward
+(egv_cls_head_loss_bwd).
+Every other loss here runs on ONE generic node, _KernelLossFn: the kernels return the gradients with the loss.
 """
 import math
 
 import torch
 from torch import nn
 
-from .. import gather, loss_ops, ops
+from .. import gather, loss_ops
 
 
-class _LossFromSimFn(torch.autograd.Function):
+class _KernelLossFn(torch.autograd.Function):
+    """The one autograd node of the losses whose kernel returns its own gradients: `call(*tensors)` -> (loss[1], then one gradient
+    or None per tensor) runs in forward; backward hands each saved gradient out times the upstream factor, so they carry the loss
+    scale of an fp16 backward.  Everything that is not differentiable lives in `call`'s closure."""
+
     @staticmethod
-    def forward(ctx, x, mask_v, mask_n, temperature, use_noun, use_verb):
-        loss, dx = loss_ops.egonce_from_sim(x, mask_v, mask_n, temperature, use_noun, use_verb, want_grad=True)
-        ctx.save_for_backward(dx)
+    def forward(ctx, call, *tensors):
+        loss, *grads = call(*tensors)
+        ctx.given = [g is not None for g in grads]
+        ctx.save_for_backward(*(g for g in grads if g is not None))
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        (dx,) = ctx.saved_tensors
-        return dx * g, None, None, None, None, None
+        saved = iter(ctx.saved_tensors)
+        return (None,) + tuple(next(saved) * g if given else None for given in ctx.given)
 
 
-class _FusedHeadFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, text, video, noun, verb, temperature, use_noun, use_verb):
-        loss, _, dt, dv = ops.egonce_fwd_bwd(text.contiguous(), video.contiguous(),
-                                             None if noun is None else noun.contiguous().float(),
-                                             None if verb is None else verb.contiguous().float(),
-                                             temperature, use_noun=use_noun, use_verb=use_verb)
-        ctx.save_for_backward(dt, dv)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        dt, dv = ctx.saved_tensors
-        return dt * g, dv * g, None, None, None, None, None
-
-
-class _LossFromSimScaleFn(torch.autograd.Function):
-    """_LossFromSimFn with the temperature read from the device parameter `logit_scale`; also returns dL/d(logit_scale)."""
-
-    @staticmethod
-    def forward(ctx, x, mask_v, mask_n, logit_scale, use_noun, use_verb):
-        loss, dx, dls = loss_ops.egonce_from_sim(x, mask_v, mask_n, None, use_noun, use_verb, want_grad=True, logit_scale=logit_scale)
-        ctx.save_for_backward(dx, _over_world(dls))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        dx, dls = ctx.saved_tensors
-        return dx * g, None, None, dls * g, None, None
-
-
-class _FusedHeadScaleFn(torch.autograd.Function):
-    """_FusedHeadFn with the temperature read from the device parameter `logit_scale`; also returns dL/d(logit_scale)."""
-
-    @staticmethod
-    def forward(ctx, text, video, noun, verb, logit_scale, use_noun, use_verb):
-        loss, _, dt, dv, dls = ops.egonce_fwd_bwd(text.contiguous(), video.contiguous(),
-                                                  None if noun is None else noun.contiguous().float(),
-                                                  None if verb is None else verb.contiguous().float(),
-                                                  None, use_noun=use_noun, use_verb=use_verb, logit_scale=logit_scale)
-        ctx.save_for_backward(dt, dv, _over_world(dls))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        dt, dv, dls = ctx.saved_tensors
-        return dt * g, dv * g, None, None, dls * g, None, None
+def _f32(t):
+    return None if t is None else t.contiguous().float()
 
 
 def _over_world(dls):
     """Every rank runs the head on the same gathered batch with deterministic kernels, so dL/ds is bit-identical everywhere and
     is NOT exchanged (it is no part of Bf16GradSync).  The model's gradients leave the exchange as (1 / W) grad L_global
     (egovlp_amd/gather.py); the scale's is stored with the same factor, so that the optimizer -- and its global-norm clipping -- sees
-    one consistent gradient vector."""
+    one consistent gradient vector.  None (a gradient the kernel was not asked for) stays None."""
     W = gather._world()
-    return dls if W == 1 else dls / W
+    return dls if W == 1 or dls is None else dls / W
 
 
-class _TemperatureMixin:
-    """temperature = 0.05 of the reference (model/loss.py:8-11,28-32), fixed -- or, `learnable_temperature=True`, CLIP's learnable
-    logit scale: `self.logit_scale` = s = log(1 / tau), one fp32 parameter initialised to log(1 / temperature); the head kernels
-    read it on the device and return dL/ds.  Off (the default) the module has no parameter and makes the calls it always made."""
+class _LogitScaleMixin:
+    """What the losses with a logit scale s = log(1 / tau) share: the fp32 clamp bound, the clamp and the read-back."""
 
-    def _init_temperature(self, temperature, learnable_temperature, max_logit_scale):
-        self.temperature = temperature
-        self.learnable_temperature = bool(learnable_temperature)
+    def _init_clamp(self, learnable, max_logit_scale):
+        self.learnable_temperature = bool(learnable)     # what the steps' clamp and the trainer's temperature log look at
         self.max_logit_scale = float(max_logit_scale)
         # the clamp runs in fp32: its upper bound is the largest fp32 value <= max_logit_scale (fp32(ln 100) itself rounds UP)
         hi = torch.tensor(self.max_logit_scale, dtype=torch.float32)
         if float(hi) > self.max_logit_scale:
             hi = torch.nextafter(hi, torch.tensor(float("-inf")))
         self._clamp_hi = float(hi)
-        if self.learnable_temperature:
-            if not temperature > 0:
-                raise ValueError("learnable_temperature: the initial temperature must be positive")
-            self.logit_scale = nn.Parameter(torch.full((1,), math.log(1.0 / temperature), dtype=torch.float32))
 
     def current_temperature(self):
-        """tau = exp(-s) read back from the device (synchronises: logs and tests); the fixed value when not learnable."""
-        if not self.learnable_temperature:
+        """tau = exp(-s) read back from the device (synchronises: logs and tests); the fixed value of a module without the parameter."""
+        if getattr(self, "logit_scale", None) is None:
             return float(self.temperature)
         return math.exp(-float(self.logit_scale.detach().float().cpu()))
 
     @torch.no_grad()
     def clamp_logit_scale_(self):
         """s <- clamp(s, 0, max_logit_scale) in place (CLIP: max ln 100): one tiny device op, no synchronisation.  The steps call it
-        after optimizer.step."""
+        after optimizer.step.  A logit bias is not clamped."""
         if self.learnable_temperature:
             self.logit_scale.clamp_(0.0, self._clamp_hi)
         return self
+
+
+class _TemperatureMixin(_LogitScaleMixin):
+    """temperature = 0.05 of the reference (model/loss.py:8-11,28-32), fixed -- or, `learnable_temperature=True`, CLIP's learnable
+    logit scale: `self.logit_scale` = s = log(1 / tau), one fp32 parameter initialised to log(1 / temperature); the head kernels
+    read it on the device and return dL/ds.  Off (the default) the module has no parameter and makes the calls it always made."""
+
+    def _init_temperature(self, temperature, learnable_temperature, max_logit_scale):
+        self.temperature = temperature
+        self._init_clamp(learnable_temperature, max_logit_scale)
+        if self.learnable_temperature:
+            if not temperature > 0:
+                raise ValueError("learnable_temperature: the initial temperature must be positive")
+            self.logit_scale = nn.Parameter(torch.full((1,), math.log(1.0 / temperature), dtype=torch.float32))
+
+    def _scale(self):
+        return (self.logit_scale,) if self.learnable_temperature else ()
+
+    def _from_sim(self, x, mask_v, mask_n, use_noun, use_verb):
+        "an autograd node over egv_egonce_from_sim (learnable: _ls, which also returns dL/d(logit_scale))"
+        def call(x, logit_scale=None):
+            loss, dx, *dls = loss_ops.egonce_from_sim(x, mask_v, mask_n, self.temperature, use_noun, use_verb, want_grad=True,
+                                                      logit_scale=logit_scale)
+            return (loss, dx, *map(_over_world, dls))
+        return _KernelLossFn.apply(call, x, *self._scale())
+
+    def _fused(self, text, video, noun, verb, use_noun, use_verb):
+        "an autograd node over egv_egonce_fwd_bwd / egv_egonce_long_fwd_bwd (learnable: their _ls variants)"
+        def call(text, video, logit_scale=None):
+            loss, _, dt, dv, *dls = loss_ops.egonce_fwd_bwd(text.contiguous(), video.contiguous(), _f32(noun), _f32(verb),
+                                                            self.temperature, use_noun=use_noun, use_verb=use_verb,
+                                                            logit_scale=logit_scale)
+            return (loss, dt, dv, *map(_over_world, dls))
+        return _KernelLossFn.apply(call, text, video, *self._scale())
 
 
 class NormSoftmaxLoss(_TemperatureMixin, nn.Module):
@@ -138,14 +128,10 @@ class NormSoftmaxLoss(_TemperatureMixin, nn.Module):
 
     def forward(self, x):
         "x: similarity matrix N x N in [-1, 1] (model/loss.py:13-25)"
-        if self.learnable_temperature:
-            return _LossFromSimScaleFn.apply(x, None, None, self.logit_scale, True, True)
-        return _LossFromSimFn.apply(x, None, None, self.temperature, True, True)
+        return self._from_sim(x, None, None, True, True)
 
     def fused(self, text_embeds, video_embeds):
-        if self.learnable_temperature:
-            return _FusedHeadScaleFn.apply(text_embeds, video_embeds, None, None, self.logit_scale, True, True)
-        return _FusedHeadFn.apply(text_embeds, video_embeds, None, None, self.temperature, True, True)
+        return self._fused(text_embeds, video_embeds, None, None, True, True)
 
 
 class EgoNCE(_TemperatureMixin, nn.Module):
@@ -157,93 +143,43 @@ class EgoNCE(_TemperatureMixin, nn.Module):
 
     def forward(self, x, mask_v, mask_n):
         # noun=False, verb=False falls into the reference's else-branch (mask_v), model/loss.py:40-41
-        if self.learnable_temperature:
-            return _LossFromSimScaleFn.apply(x, mask_v, mask_n, self.logit_scale, self.noun, self.verb or not self.noun)
-        return _LossFromSimFn.apply(x, mask_v, mask_n, self.temperature, self.noun, self.verb or not self.noun)
+        return self._from_sim(x, mask_v, mask_n, self.noun, self.verb or not self.noun)
 
     def fused(self, text_embeds, video_embeds, noun_vec, verb_vec):
-        if self.learnable_temperature:
-            return _FusedHeadScaleFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.logit_scale, self.noun,
-                                           self.verb or not self.noun)
-        return _FusedHeadFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.temperature, self.noun,
-                                  self.verb or not self.noun)
+        return self._fused(text_embeds, video_embeds, noun_vec, verb_vec, self.noun, self.verb or not self.noun)
 
 
-class _SigmoidFromSimFn(torch.autograd.Function):
-    """The sigmoid loss on a given similarity matrix (egv_sigmoid_from_sim): dx, dL/ds and dL/db from one node."""
-
-    @staticmethod
-    def forward(ctx, x, mask_v, mask_n, logit_scale, logit_bias, use_noun, use_verb, learnable):
-        loss, dx, dls, dlb = loss_ops.sigmoid_from_sim(x, mask_v, mask_n, logit_scale, logit_bias, use_noun, use_verb,
-                                                       want_grad=True, want_param_grads=learnable)
-        ctx.learnable = learnable
-        ctx.save_for_backward(*((dx, _over_world(dls), _over_world(dlb)) if learnable else (dx,)))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.learnable:
-            dx, dls, dlb = ctx.saved_tensors
-            return dx * g, None, None, dls * g, dlb * g, None, None, None
-        (dx,) = ctx.saved_tensors
-        return dx * g, None, None, None, None, None, None, None
-
-
-class _FusedSigmoidHeadFn(torch.autograd.Function):
-    """The one-call sigmoid head (egv_sigmoid_head_fwd_bwd): all four gradients leave this node times the upstream factor, so they
-    carry the loss scale of an fp16 backward."""
-
-    @staticmethod
-    def forward(ctx, text, video, noun, verb, logit_scale, logit_bias, use_noun, use_verb, learnable):
-        loss, dt, dv, dls, dlb = ops.sigmoid_head_fwd_bwd(text.contiguous(), video.contiguous(),
-                                                          None if noun is None else noun.contiguous().float(),
-                                                          None if verb is None else verb.contiguous().float(),
-                                                          logit_scale, logit_bias, use_noun=use_noun, use_verb=use_verb,
-                                                          want_param_grads=learnable)
-        ctx.learnable = learnable
-        ctx.save_for_backward(*((dt, dv, _over_world(dls), _over_world(dlb)) if learnable else (dt, dv)))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.learnable:
-            dt, dv, dls, dlb = ctx.saved_tensors
-            return dt * g, dv * g, None, None, dls * g, dlb * g, None, None, None
-        dt, dv = ctx.saved_tensors
-        return dt * g, dv * g, None, None, None, None, None, None, None
-
-
-class _SigmoidMixin:
+class _SigmoidMixin(_LogitScaleMixin):
     """SigLIP's two parameters (Zhai et al. 2023): `logit_scale` = s (u = exp(s) x + b; initial value ln 10) and `logit_bias` = b
     (initial value -10), fp32 [1] each, read on the device by the head kernels, which return dL/ds and dL/db beside the embedding
     gradients.  learnable=False: both are held with requires_grad=False and the heads are called without the parameter gradients."""
 
     def _init_sigmoid(self, logit_scale, logit_bias, learnable, max_logit_scale):
         self.learnable = bool(learnable)
-        self.learnable_temperature = self.learnable      # what clamp_loss_scale and the trainer's temperature log look at
-        self.max_logit_scale = float(max_logit_scale)
-        # the clamp runs in fp32: its upper bound is the largest fp32 value <= max_logit_scale (fp32(ln 100) itself rounds UP)
-        hi = torch.tensor(self.max_logit_scale, dtype=torch.float32)
-        if float(hi) > self.max_logit_scale:
-            hi = torch.nextafter(hi, torch.tensor(float("-inf")))
-        self._clamp_hi = float(hi)
+        self._init_clamp(learnable, max_logit_scale)
         self.logit_scale = nn.Parameter(torch.full((1,), float(logit_scale), dtype=torch.float32), requires_grad=self.learnable)
         self.logit_bias = nn.Parameter(torch.full((1,), float(logit_bias), dtype=torch.float32), requires_grad=self.learnable)
-
-    def current_temperature(self):
-        """exp(-s) read back from the device (synchronises: logs and tests)."""
-        return math.exp(-float(self.logit_scale.detach().float().cpu()))
 
     def current_bias(self):
         """b read back from the device (synchronises: logs and tests)."""
         return float(self.logit_bias.detach().float().cpu())
 
-    @torch.no_grad()
-    def clamp_logit_scale_(self):
-        """s <- clamp(s, 0, max_logit_scale) in place: one tiny device op, no synchronisation.  The bias is not clamped."""
-        if self.learnable:
-            self.logit_scale.clamp_(0.0, self._clamp_hi)
-        return self
+    def _from_sim(self, x, mask_v, mask_n, use_noun, use_verb):
+        "an autograd node over egv_sigmoid_from_sim: dx, dL/ds and dL/db"
+        def call(x, logit_scale, logit_bias):
+            loss, dx, dls, dlb = loss_ops.sigmoid_from_sim(x, mask_v, mask_n, logit_scale, logit_bias, use_noun, use_verb,
+                                                           want_grad=True, want_param_grads=self.learnable)
+            return loss, dx, _over_world(dls), _over_world(dlb)
+        return _KernelLossFn.apply(call, x, self.logit_scale, self.logit_bias)
+
+    def _fused(self, text, video, noun, verb, use_noun, use_verb):
+        "an autograd node over the one-call sigmoid head (egv_sigmoid_head_fwd_bwd): all four gradients"
+        def call(text, video, logit_scale, logit_bias):
+            loss, dt, dv, dls, dlb = loss_ops.sigmoid_head_fwd_bwd(text.contiguous(), video.contiguous(), _f32(noun), _f32(verb),
+                                                                   logit_scale, logit_bias, use_noun=use_noun, use_verb=use_verb,
+                                                                   want_param_grads=self.learnable)
+            return loss, dt, dv, _over_world(dls), _over_world(dlb)
+        return _KernelLossFn.apply(call, text, video, self.logit_scale, self.logit_bias)
 
 
 class SigmoidLoss(_SigmoidMixin, nn.Module):
@@ -258,11 +194,10 @@ class SigmoidLoss(_SigmoidMixin, nn.Module):
 
     def forward(self, x):
         "x: similarity matrix N x N in [-1, 1]"
-        return _SigmoidFromSimFn.apply(x, None, None, self.logit_scale, self.logit_bias, True, True, self.learnable)
+        return self._from_sim(x, None, None, True, True)
 
     def fused(self, text_embeds, video_embeds):
-        return _FusedSigmoidHeadFn.apply(text_embeds, video_embeds, None, None, self.logit_scale, self.logit_bias, True, True,
-                                         self.learnable)
+        return self._fused(text_embeds, video_embeds, None, None, True, True)
 
 
 class EgoSigmoidLoss(_SigmoidMixin, nn.Module):
@@ -279,38 +214,21 @@ class EgoSigmoidLoss(_SigmoidMixin, nn.Module):
         self._init_sigmoid(logit_scale, logit_bias, learnable, max_logit_scale)
 
     def forward(self, x, mask_v, mask_n):
-        return _SigmoidFromSimFn.apply(x, mask_v, mask_n, self.logit_scale, self.logit_bias, self.noun, self.verb or not self.noun,
-                                       self.learnable)
+        return self._from_sim(x, mask_v, mask_n, self.noun, self.verb or not self.noun)
 
     def fused(self, text_embeds, video_embeds, noun_vec, verb_vec):
-        return _FusedSigmoidHeadFn.apply(text_embeds, video_embeds, noun_vec, verb_vec, self.logit_scale, self.logit_bias, self.noun,
-                                         self.verb or not self.noun, self.learnable)
+        return self._fused(text_embeds, video_embeds, noun_vec, verb_vec, self.noun, self.verb or not self.noun)
 
 
-class _MaxMarginFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, margin, fix_norm):
-        loss, dx = loss_ops.maxmargin(x, weight, margin, fix_norm, want_grad=True)
-        ctx.save_for_backward(dx)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx,) = ctx.saved_tensors
-        return dx * g, None, None, None
+def _maxmargin(x, weight, margin, fix_norm):
+    return _KernelLossFn.apply(lambda x: loss_ops.maxmargin(x, weight, margin, fix_norm, want_grad=True), x)
 
 
-class _FusedMaxMarginFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, text, video, weight, margin, fix_norm):
+def _maxmargin_fused(text, video, weight, margin, fix_norm):
+    def call(text, video):
         loss, _, dt, dv = loss_ops.maxmargin_head(text, video, weight, margin, fix_norm)
-        ctx.save_for_backward(dt, dv)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        dt, dv = ctx.saved_tensors
-        return dt * g, dv * g, None, None, None
+        return loss, dt, dv
+    return _KernelLossFn.apply(call, text, video)
 
 
 class MaxMarginRankingLoss(nn.Module):
@@ -322,11 +240,11 @@ class MaxMarginRankingLoss(nn.Module):
         self.margin = margin
 
     def forward(self, x, weight=None):
-        return _MaxMarginFn.apply(x, None, self.margin, self.fix_norm)
+        return _maxmargin(x, None, self.margin, self.fix_norm)
 
     def fused(self, text_embeds, video_embeds, weight=None):
         "loss(sim_matrix(text_embeds, video_embeds)) in one call (`weight` ignored, as in forward)"
-        return _FusedMaxMarginFn.apply(text_embeds, video_embeds, None, self.margin, self.fix_norm)
+        return _maxmargin_fused(text_embeds, video_embeds, None, self.margin, self.fix_norm)
 
 
 class AdaptiveMaxMarginRankingLoss(nn.Module):
@@ -340,26 +258,13 @@ class AdaptiveMaxMarginRankingLoss(nn.Module):
     def forward(self, x, weight=None):
         if weight is None:
             raise TypeError("AdaptiveMaxMarginRankingLoss needs the per-row weight (model/loss.py:109)")
-        return _MaxMarginFn.apply(x, weight, self.margin, self.fix_norm)
+        return _maxmargin(x, weight, self.margin, self.fix_norm)
 
     def fused(self, text_embeds, video_embeds, weight=None):
         "loss(sim_matrix(text_embeds, video_embeds), weight) in one call"
         if weight is None:
             raise TypeError("AdaptiveMaxMarginRankingLoss needs the per-row weight (model/loss.py:109)")
-        return _FusedMaxMarginFn.apply(text_embeds, video_embeds, weight, self.margin, self.fix_norm)
-
-
-class _CrossEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, output, target):
-        loss, dx = loss_ops.cross_entropy(output, target, want_grad=True)
-        ctx.save_for_backward(dx)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx,) = ctx.saved_tensors
-        return dx * g, None
+        return _maxmargin_fused(text_embeds, video_embeds, weight, self.margin, self.fix_norm)
 
 
 class CrossEntropy(nn.Module):
@@ -370,7 +275,7 @@ class CrossEntropy(nn.Module):
         super().__init__()
 
     def forward(self, output, target):
-        return _CrossEntropyFn.apply(output, target)
+        return _KernelLossFn.apply(lambda output: loss_ops.cross_entropy(output, target, want_grad=True), output)
 
     def fused(self, feats, weight, bias, target, state=None, world_size=1, rank=0, ec=None):
         """The classification head of the OSCC / PNR step in one node, from the video tower's features [B, K]:

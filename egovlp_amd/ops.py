@@ -1272,116 +1272,20 @@ def embed_bwd(ids, d_e, word_shape, pos_shape, pad_id=-1):
 
 
 # ------------------------------------------------------------------------------------------- loss / optim
-def _logit_scale_arg(logit_scale, like):
-    """The learnable heads read s = log(1 / tau) from the device: one fp32 on the inputs' device."""
-    ls = logit_scale.detach()
-    if ls.dtype != torch.float32 or ls.numel() != 1 or ls.device != like.device:
-        raise ValueError("logit_scale must be one fp32 value on the device of the embeddings")
-    return ls.contiguous()
+# the one-call heads live in loss_ops.py; these three names forward there for callers that still bind them here
+def egonce_fwd_bwd(*args, **kw):
+    from . import loss_ops
+    return loss_ops.egonce_fwd_bwd(*args, **kw)
 
 
-def egonce_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
-                   want_sim=False, logit_scale=None):
-    """The contrastive head in one call -> (loss[1], sim or None, d_text, d_video).  Up to EGONCE_SHORT_MAX rows: the latency-bound
-    kernels of csrc/egonce.hip; beyond: egonce_long_fwd_bwd (no n x n matrix exists there, so `want_sim` is refused).
-    `logit_scale` (a device tensor holding s = log(1 / tau); `temperature` is then unused): the kernels form 1 / tau = exp(s) on the
-    device and the call returns a fifth value, d_logit_scale [1] = dL/ds (None without want_grads) -- egv_egonce_fwd_bwd_ls."""
-    _need_cuda(text, video, noun, verb)
-    n, D = text.shape
-    if n > EGONCE_SHORT_MAX:
-        if want_sim:
-            raise ValueError("egonce_fwd_bwd: want_sim needs n <= %d (the long head materialises no n x n matrix), got n = %d"
-                             % (EGONCE_SHORT_MAX, n))
-        out = egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=eps, use_noun=use_noun, use_verb=use_verb,
-                                  want_grads=want_grads, logit_scale=logit_scale)
-        return (out[0], None) + tuple(out[1:])
-    dev = text.device
-    dn = noun.shape[1] if noun is not None else 0
-    dv = verb.shape[1] if verb is not None else 0
-    wf = _lib.lib().egv_egonce_work_floats(n, D)
-    work = torch.empty(wf, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    sim = torch.empty((n, n), dtype=torch.float32, device=dev) if want_sim else None
-    dt = torch.empty_like(text) if want_grads else None
-    dvv = torch.empty_like(video) if want_grads else None
-    if logit_scale is not None:
-        ls = _logit_scale_arg(logit_scale, text)
-        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads else None
-        check(_lib.lib().egv_egonce_fwd_bwd_ls(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), float(eps),
-                                               int(use_noun), int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv), _p(dls),
-                                               _p(work), _stream(text)), "egv_egonce_fwd_bwd_ls")
-        return loss, sim, dt, dvv, dls
-    check(_lib.lib().egv_egonce_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, float(temperature),
-                                        float(eps), int(use_noun), int(use_verb), _p(loss), _p(sim), _p(dt), _p(dvv),
-                                        _p(work), _stream(text)), "egv_egonce_fwd_bwd")
-    return loss, sim, dt, dvv
+def egonce_long_fwd_bwd(*args, **kw):
+    from . import loss_ops
+    return loss_ops.egonce_long_fwd_bwd(*args, **kw)
 
 
-EGONCE_SHORT_MAX = 1024      # rows of egv_egonce_fwd_bwd; egonce_fwd_bwd switches to the long head past it
-EGONCE_LONG_MAX = 65536      # rows of egv_egonce_long_fwd_bwd
-
-
-def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
-                        logit_scale=None):
-    """egv_egonce_long_fwd_bwd for ANY n in [1, 65536] -> (loss[1], d_text, d_video): the tiled fp32-MFMA head with a workspace
-    linear in n.  noun / verb: non-negative multi-hots (only entry > 0 is used); a negative or NaN entry makes the loss NaN.
-    `logit_scale`: as in egonce_fwd_bwd -> (loss[1], d_text, d_video, d_logit_scale [1]) -- egv_egonce_long_fwd_bwd_ls."""
-    _need_cuda(text, video, noun, verb)
-    n, D = text.shape
-    dev = text.device
-    dn = noun.shape[1] if noun is not None else 0
-    dv = verb.shape[1] if verb is not None else 0
-    wf = _lib.lib().egv_egonce_long_work_floats(n, D, dn, dv)
-    work = torch.empty(wf, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    dt = torch.empty_like(text) if want_grads else None
-    dvv = torch.empty_like(video) if want_grads else None
-    if logit_scale is not None:
-        ls = _logit_scale_arg(logit_scale, text)
-        dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads else None
-        check(_lib.lib().egv_egonce_long_fwd_bwd_ls(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), float(eps),
-                                                    int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(dls), _p(work),
-                                                    _stream(text)), "egv_egonce_long_fwd_bwd_ls")
-        return loss, dt, dvv, dls
-    check(_lib.lib().egv_egonce_long_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, float(temperature),
-                                             float(eps), int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(work),
-                                             _stream(text)), "egv_egonce_long_fwd_bwd")
-    return loss, dt, dvv
-
-
-def _one_fp32_arg(value, like, name):
-    """A head parameter read on the device: one fp32 on the inputs' device."""
-    v = value.detach()
-    if v.dtype != torch.float32 or v.numel() != 1 or v.device != like.device:
-        raise ValueError("%s must be one fp32 value on the device of the embeddings" % name)
-    return v.contiguous()
-
-
-def sigmoid_head_fwd_bwd(text, video, noun, verb, logit_scale, logit_bias, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
-                         want_param_grads=True):
-    """egv_sigmoid_head_fwd_bwd, the pairwise sigmoid head with EgoNCE's positives (noun / verb None: mask = I, plain SigLIP), for
-    ANY n in [1, 65536] -> (loss[1], d_text, d_video, d_scale[1], d_bias[1]).  `logit_scale` (s) and `logit_bias` (b) are device
-    tensors of one fp32 each: u = exp(s) x + b is formed on the device.  want_grads=False: the loss alone, the four gradients are
-    None; want_param_grads=False (fixed s and b): d_scale and d_bias are None.  noun / verb: non-negative multi-hots (only
-    entry > 0 is used); a negative or NaN entry makes the loss NaN."""
-    _need_cuda(text, video, noun, verb)
-    n, D = text.shape
-    dev = text.device
-    dn = noun.shape[1] if noun is not None else 0
-    dv = verb.shape[1] if verb is not None else 0
-    ls = _one_fp32_arg(logit_scale, text, "logit_scale")
-    lb = _one_fp32_arg(logit_bias, text, "logit_bias")
-    wf = _lib.lib().egv_sigmoid_head_work_floats(n, D, dn, dv)
-    work = torch.empty(wf, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    dt = torch.empty_like(text) if want_grads else None
-    dvv = torch.empty_like(video) if want_grads else None
-    dls = torch.empty(1, dtype=torch.float32, device=dev) if want_grads and want_param_grads else None
-    dlb = torch.empty(1, dtype=torch.float32, device=dev) if want_grads and want_param_grads else None
-    check(_lib.lib().egv_sigmoid_head_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(ls), _p(lb), float(eps),
-                                              int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv), _p(dls), _p(dlb), _p(work),
-                                              _stream(text)), "egv_sigmoid_head_fwd_bwd")
-    return loss, dt, dvv, dls, dlb
+def sigmoid_head_fwd_bwd(*args, **kw):
+    from . import loss_ops
+    return loss_ops.sigmoid_head_fwd_bwd(*args, **kw)
 
 
 def grad_nonfinite_multi(grads, state):

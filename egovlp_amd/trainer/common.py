@@ -71,7 +71,7 @@ def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fu
     is_ego = type(loss_fn).__name__ == 'EgoNCE' or bool(getattr(loss_fn, 'takes_noun_verb', False))
     n, D = text_embeds.shape
     # the one-call head covers global batches up to 65 536 rows of <= 256 features: the latency-bound kernels up to 1 024 rows, the
-    # tiled fp32-MFMA ones beyond (ops.egonce_fwd_bwd switches); anything else, or fused_head=False, takes the API-compatible
+    # tiled fp32-MFMA ones beyond (loss_ops.egonce_fwd_bwd switches); anything else, or fused_head=False, takes the API-compatible
     # sim_matrix + loss.forward path (n <= 4096)
     if fused_head and hasattr(loss_fn, 'fused') and n <= 65536 and D <= 256 and D % 4 == 0:
         return loss_fn.fused(text_embeds, video_embeds, n_embeds, v_embeds) if is_ego \

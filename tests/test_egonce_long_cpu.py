@@ -80,7 +80,7 @@ def test_head_loss_dispatch(n, entry):
 
 
 def test_want_sim_is_refused_past_the_cap():
-    from egovlp_amd import ops
+    from egovlp_amd import loss_ops as ops
     with mock_hip():
         loss, sim, dt, dv = ops.egonce_fwd_bwd(torch.randn(1024, 8), torch.randn(1024, 8), None, None, 0.05, want_sim=True)
         assert sim.shape == (1024, 1024)

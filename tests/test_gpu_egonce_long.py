@@ -23,7 +23,7 @@ GRAD_BAR = 1e-4
 
 @pytest.fixture(scope="module")
 def ops():
-    from egovlp_amd import ops as _ops
+    from egovlp_amd import loss_ops as _ops
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
     return _ops
 

@@ -27,7 +27,7 @@ KINDS = {"ego": (True, True), "noun": (True, False), "verb": (False, True), "nsl
 
 @pytest.fixture(scope="module")
 def ops():
-    from egovlp_amd import ops as _ops
+    from egovlp_amd import loss_ops as _ops
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
     return _ops
 

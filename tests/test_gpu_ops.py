@@ -338,15 +338,28 @@ def test_text_attention_fwd_bwd(ops, passes, L):
 # ---------------------------------------------------------------------------------------- contrastive head
 @pytest.mark.parametrize("n", [4, 48, 256])
 def test_egonce_fused_matches_oracle(ops, n):
+    egonce_fused_against_oracle(n, 256)
+
+
+@pytest.mark.parametrize("D", [4, 68, 252])
+@pytest.mark.parametrize("n", [1, 5, 65])
+def test_egonce_fused_matches_oracle_at_narrow_widths(ops, n, D):
+    """The smallest legal width, a width just above one wave's worth and the largest that leaves threads of the 256-thread
+    workgroups idle (the block sums and the one-feature-per-thread gradient kernel); one row, a few, and more than one wave of rows."""
+    egonce_fused_against_oracle(n, D)
+
+
+def egonce_fused_against_oracle(n, D):
+    from egovlp_amd import loss_ops
     from egovlp_amd.synth import synth_batch
     g = torch.Generator().manual_seed(n)
-    t, v = torch.randn(n, 256, generator=g), torch.randn(n, 256, generator=g)
+    t, v = torch.randn(n, D, generator=g), torch.randn(n, D, generator=g)
     b = synth_batch(n, T=1, L=4, res=2, seed=77)
     noun, verb = b["noun_vec"], b["verb_vec"]
     td, vd = t.double().requires_grad_(True), v.double().requires_grad_(True)
     ref, sim = O.egoclip_loss(td, vd, noun.double(), verb.double())
     ref.backward()
-    loss, s, dt, dv = ops.egonce_fwd_bwd(t.cuda(), v.cuda(), noun.cuda(), verb.cuda(), 0.05, want_sim=True)
+    loss, s, dt, dv = loss_ops.egonce_fwd_bwd(t.cuda(), v.cuda(), noun.cuda(), verb.cuda(), 0.05, want_sim=True)
     assert abs(float(loss) - float(ref)) < 1e-4 * max(1.0, abs(float(ref)))
     assert rel(s, sim) < 1e-5
     assert rel(dt, td.grad) < 1e-4 and rel(dv, vd.grad) < 1e-4
@@ -354,7 +367,7 @@ def test_egonce_fused_matches_oracle(ops, n):
     td.grad = None; vd.grad = None
     ref2 = O.norm_softmax_loss(O.sim_matrix(td, vd))
     ref2.backward()
-    loss2, _, dt2, dv2 = ops.egonce_fwd_bwd(t.cuda(), v.cuda(), None, None, 0.05)
+    loss2, _, dt2, dv2 = loss_ops.egonce_fwd_bwd(t.cuda(), v.cuda(), None, None, 0.05)
     assert abs(float(loss2) - float(ref2)) < 1e-4 * max(1.0, abs(float(ref2)))
     assert rel(dt2, td.grad) < 1e-4
 

@@ -31,7 +31,7 @@ SIZES = [(1, 256), (2, 64), (5, 64), (63, 256), (64, 256), (65, 256), (130, 252)
 
 @pytest.fixture(scope="module")
 def ops():
-    from egovlp_amd import ops as _ops
+    from egovlp_amd import loss_ops as _ops
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
     return _ops
 

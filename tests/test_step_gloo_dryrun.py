@@ -104,7 +104,7 @@ def _worker(rank, world, port, out, exchange, tiny=False, B=2, precision=("bf16x
     steps = []
     gathered = []
     if tiny:    # what the loss sees after the fused gather: record the shapes egv_egonce_fwd_bwd is called with
-        from egovlp_amd import ops as _ops
+        from egovlp_amd import loss_ops as _ops
         _orig = _ops.egonce_fwd_bwd
 
         def spy(text, video, noun, verb, *a, **k):
@@ -112,8 +112,8 @@ def _worker(rank, world, port, out, exchange, tiny=False, B=2, precision=("bf16x
             return _orig(text, video, noun, verb, *a, **k)
         _ops.egonce_fwd_bwd = spy
         import egovlp_amd.model.loss as _loss_mod
-        if hasattr(_loss_mod, "ops"):
-            _loss_mod.ops.egonce_fwd_bwd = spy
+        if hasattr(_loss_mod, "loss_ops"):
+            _loss_mod.loss_ops.egonce_fwd_bwd = spy
     with mock_hip() as calls:
         for step in range(2):
             calls.clear()

@@ -31,7 +31,7 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_egonce_long: needs an MI355X (there is no CPU measurement path)")
-    from egovlp_amd import ops
+    from egovlp_amd import loss_ops
     from egovlp_amd.model.loss import EgoNCE
     from egovlp_amd.trainer.common import egoclip_head_loss
 
@@ -59,14 +59,14 @@ def main():
         verb[:, :4] = (torch.rand(n, 4, generator=g) < 0.25).float()
         noun, verb = noun.cuda(), verb.cuda()
         row = {}
-        t_long = events(lambda: ops.egonce_long_fwd_bwd(text, video, noun, verb, 0.05))
+        t_long = events(lambda: loss_ops.egonce_long_fwd_bwd(text, video, noun, verb, 0.05))
         flop = 6.0 * 2.0 * n * n * D
         row["long_us"] = round(t_long, 1)
         row["floor_us"] = round(flop / PEAK_F32_MFMA * 1e6, 1)
         row["floor_frac"] = round(flop / PEAK_F32_MFMA * 1e6 / t_long, 3)
-        row["loss"] = float(ops.egonce_long_fwd_bwd(text, video, noun, verb, 0.05)[0])
-        if n <= ops.EGONCE_SHORT_MAX:
-            row["short_us"] = round(events(lambda: ops.egonce_fwd_bwd(text, video, noun, verb, 0.05)), 1)
+        row["loss"] = float(loss_ops.egonce_long_fwd_bwd(text, video, noun, verb, 0.05)[0])
+        if n <= loss_ops.EGONCE_SHORT_MAX:
+            row["short_us"] = round(events(lambda: loss_ops.egonce_fwd_bwd(text, video, noun, verb, 0.05)), 1)
         if n <= 4096:
             loss_fn = EgoNCE()
 

@@ -34,7 +34,7 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_learnable_temperature: needs an MI355X (there is no CPU measurement path)")
-    from egovlp_amd import ops
+    from egovlp_amd import loss_ops
 
     def per_call_us(fn, iters):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -48,8 +48,8 @@ def main():
     D = 256
     scale = torch.tensor([math.log(1.0 / 0.05)], dtype=torch.float32, device="cuda")
     out = {"D": D, "iters": args.iters, "warmup": args.warmup, "rounds": args.rounds, "heads": {}}
-    for name, n, call, iters in (("short", args.short_n, ops.egonce_fwd_bwd, args.iters),
-                                 ("long", args.long_n, ops.egonce_long_fwd_bwd, max(args.iters // 4, 1))):
+    for name, n, call, iters in (("short", args.short_n, loss_ops.egonce_fwd_bwd, args.iters),
+                                 ("long", args.long_n, loss_ops.egonce_long_fwd_bwd, max(args.iters // 4, 1))):
         g = torch.Generator().manual_seed(n)
         text, video = torch.randn(n, D, generator=g).cuda(), torch.randn(n, D, generator=g).cuda()
         noun, verb = torch.zeros(n, 582), torch.zeros(n, 118)

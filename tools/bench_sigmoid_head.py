@@ -3,8 +3,8 @@
     python tools/bench_sigmoid_head.py [--iters 200] [--warmup 10] [--rounds 5] [--sizes 256,1024,4096,16384]
 
 n = 256, 1 024, 4 096 and 16 384 rows of D = 256 (582 nouns / 118 verbs, the inputs of tools/bench_learnable_temperature.py).  Per
-size: `ops.sigmoid_head_fwd_bwd` (s = ln 10, b = -10: loss, both embedding gradients, d_scale, d_bias; ONE tile walk per direction at
-every n) and `ops.egonce_fwd_bwd` with `logit_scale` (up to 1 024 rows the SHORT head of csrc/egonce.hip, latency-sized kernels over an
+size: `loss_ops.sigmoid_head_fwd_bwd` (s = ln 10, b = -10: loss, both embedding gradients, d_scale, d_bias; ONE tile walk per direction at
+every n) and `loss_ops.egonce_fwd_bwd` with `logit_scale` (up to 1 024 rows the SHORT head of csrc/egonce.hip, latency-sized kernels over an
 n x n buffer; past it the LONG head of csrc/egonce_long.hip, which walks the tile grid for statistics and again for gradients), and
 the sigmoid head's loss-only call.  The variants ALTERNATE round by round in the same process; a round times back-to-back calls
 between two HIP events and reports the time per call.  Reported: the median over the rounds, the spread (min .. max) of each variant,
@@ -33,7 +33,7 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_sigmoid_head: needs an MI355X (there is no CPU measurement path)")
-    from egovlp_amd import ops
+    from egovlp_amd import loss_ops
 
     def per_call_us(fn, iters):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -58,9 +58,9 @@ def main():
         noun[:, :8] = (torch.rand(n, 8, generator=g) < 0.19).float()
         verb[:, :4] = (torch.rand(n, 4, generator=g) < 0.25).float()
         noun, verb = noun.cuda(), verb.cuda()
-        sig = lambda: ops.sigmoid_head_fwd_bwd(text, video, noun, verb, s, b)
-        sig_loss = lambda: ops.sigmoid_head_fwd_bwd(text, video, noun, verb, s, b, want_grads=False)
-        ego = lambda: ops.egonce_fwd_bwd(text, video, noun, verb, None, logit_scale=temp_scale)
+        sig = lambda: loss_ops.sigmoid_head_fwd_bwd(text, video, noun, verb, s, b)
+        sig_loss = lambda: loss_ops.sigmoid_head_fwd_bwd(text, video, noun, verb, s, b, want_grads=False)
+        ego = lambda: loss_ops.egonce_fwd_bwd(text, video, noun, verb, None, logit_scale=temp_scale)
         for _ in range(min(args.warmup, iters)):
             sig()
             sig_loss()
@@ -87,7 +87,7 @@ def main():
             del loss_fn, tc, vc, ref
         med = statistics.median
         out["sizes"].append({
-            "n": n, "calls_per_round": iters, "egonce_head": "short" if n <= ops.EGONCE_SHORT_MAX else "long",
+            "n": n, "calls_per_round": iters, "egonce_head": "short" if n <= loss_ops.EGONCE_SHORT_MAX else "long",
             "sigmoid_us": round(med(ts), 2), "sigmoid_min_max_us": [round(min(ts), 2), round(max(ts), 2)],
             "egonce_us": round(med(te), 2), "egonce_min_max_us": [round(min(te), 2), round(max(te), 2)],
             "sigmoid_over_egonce": round(med(ts) / med(te), 4),
