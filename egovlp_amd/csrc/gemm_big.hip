@@ -54,6 +54,7 @@
 #include "common.h"
 #include "f16x2.h"
 #include "egovlp_hip.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -62,15 +63,7 @@ constexpr int NFW = 8;    // 16-column fragments per wave
 constexpr int BNB = 256;  // block tile columns
 constexpr int NC = 2;     // B fragments per phase
 
-// epilogue flavours (template parameter: each kernel instance carries only its own epilogue code)
-enum { EPI_RAW = 0,      // store the accumulators (split-K partial slab, or plain fp32 output)
-       EPI_LINEAR = 1,   // + bias, + residual -> fp32 and/or planes
-       EPI_GELU = 2,     // + bias, pre-activation -> aux_out, gelu -> fp32 and/or planes
-       EPI_GELU_BWD = 3, // * gelu'(aux_in) -> fp32 and/or planes
-       EPI_GENERIC = 4,  // everything at run time (alpha, ReLU', ...)
-       EPI_GELU_X2 = 5 };// EPI_GELU with the activation written as fp16 operand planes -- out_fmt 1: the f16x2 format (csrc/f16x2.h,
-                         // first-operand role, two planes); out_fmt 2: ONE plane of plain fp16 (the consumer runs a single fp16 product)
-                         // -- [+ bf16 plane for the backward], the saved gelu' as bf16: fc1 forward of the f16x2 mode
+// (the epilogue flavours EPI_*, a template parameter of the kernel: gemm_dispatch.h)
 
 typedef __attribute__((ext_vector_type(4))) short s16x4v;
 typedef __attribute__((ext_vector_type(8))) short s16x8v;
@@ -1248,15 +1241,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const egv_gemm_desc p,
   }
 }
 
-template <int MF, bool TN, int EPI, int PROD = 0, bool MIXED = false>
-int launch_big(const egv_gemm_desc& p, hipStream_t s, int nb5 = 0) {
-  constexpr int BM = MF * 64;
-  constexpr int lds = 2 * (BM * 128 + BNB * 128);
-  int lds_launch = lds;
-  const int bands = MIXED ? nb5 + (p.M - nb5 * 320 + 255) / 256 : (p.M + BM - 1) / BM;
-  const int tiles = bands * ((p.N + BNB - 1) / BNB);
-  const int ks = p.ksplit > 1 ? p.ksplit : 1;
-  const int total = tiles * ks;
+// One launch of the instance, as the pick (gemm_dispatch.h) describes it.
+template <int MF, bool TN, int EPI, int PROD, bool MIXED>
+int launch_big(const GemmPick& g, const egv_gemm_desc& p, hipStream_t s) {
   auto k = gemm_big_kernel<MF, TN, EPI, PROD, MIXED>;
   static bool attr_set = false;   // idempotent; a race only repeats the call
   if (!attr_set) {
@@ -1264,160 +1251,49 @@ int launch_big(const egv_gemm_desc& p, hipStream_t s, int nb5 = 0) {
       return EGV_ERR_LAUNCH + (int)hipGetLastError();
     attr_set = true;
   }
+  int lds_launch = g.lds;
 #ifdef EGV_DIAG
   static const int dbg = getenv("EGV_GEMM_DBG") ? atoi(getenv("EGV_GEMM_DBG")) : 0;
-  if ((dbg & 0x4000) && lds + 16384 <= 163840) lds_launch += 16384;   // stamp area of the hand-over diagnostic
+  if ((dbg & 0x4000) && g.lds + 16384 <= 163840) lds_launch += 16384;   // stamp area of the hand-over diagnostic
 #else
   constexpr int dbg = 0;
 #endif
-  // persistent workgroups: one per CU (144 KiB of LDS each); a grid that is a multiple of 8 keeps v % 8 == blockIdx % 8
-  // (XCD affinity).  p.grid_cap < 256 leaves CUs to the RCCL kernels of an overlapped collective (per launch: no process state).
-  const int cap = p.grid_cap > 0 ? p.grid_cap : 256;
-  const int grid = total < cap ? total : cap;
-  EGV_LAUNCH(k, dim3(grid), dim3(512), lds_launch, s, p, dbg, nb5);
+  EGV_LAUNCH(k, dim3((unsigned)g.grid_x), dim3(g.block), lds_launch, s, p, dbg, g.nb5);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }
 
-// Mixed row bands (see gemm_big_kernel): -> nb5 (number of 320-row bands, the rest are 256 rows), or -1 when the uniform 320-row
-// tiling is at least as good.  Same number of rounds R as the uniform tiling; as many bands as R rounds of `grid` workgroups can
-// take; cost = 5 per round that still contains a 320-row tile + 4 per round of 256-row tiles only.
-int pick_mixed_bands(const egv_gemm_desc& p, int grid) {
-  if (p.M < 640 || grid < 8) return -1;
-  const int tn = (p.N + BNB - 1) / BNB;
-  const int tiles5 = ((p.M + 319) / 320) * tn;
-  const int R = (tiles5 + grid - 1) / grid;
-  if (R < 2) return -1;
-  const int NB = (R * grid) / tn;                             // bands R rounds can hold
-  int nb5 = (p.M - 256 * NB + 63) / 64;                       // 320 nb5 + 256 (NB - nb5) >= M
-  if (nb5 < 0) nb5 = 0;
-  if (nb5 > NB) return -1;
-  const int r5 = (nb5 * tn + grid - 1) / grid;                // rounds that contain a 320-row tile
-  const int cost = 5 * r5 + 4 * (R - r5);
-  return cost < 5 * R ? nb5 : -1;
-}
-
-template <int MF, bool TN, int PROD = 0>
-int launch_epi(const egv_gemm_desc& p, hipStream_t s) {
-  // fp16 operand outputs (fc1 -> fc2 of the forward): GELU epilogue of an fp16 product only, planes only; 1 = f16x2 (two planes), 2 = one plain plane
-  if (p.out_fmt != 0) {
-    if (!(PROD == 1 || PROD == 2) || p.out_fmt < 1 || p.out_fmt > 4) return EGV_ERR_ARG;
-    // fp16 plane outputs: the GELU epilogue (h for fc2: 1 / 2); the plain epilogue as an fp16 split (3: the qkv planes of the fp16
-    // attention); and -- one fp16 product only -- un-clamped gradient planes (4): dZ from the GELU' epilogue, dO from a plain dgrad
-    const bool gelu_fwd = p.act == EGV_ACT_GELU && (p.out_fmt == 1 || p.out_fmt == 2);
-    const bool gelu_bwd16 = PROD == 1 && p.act == EGV_ACT_GELU_BWD && p.out_fmt == 4 && p.aux_in && p.aux_bf16 >= 2 && !p.bias;
-    const bool lin_split = p.act == EGV_ACT_NONE && p.out_fmt == 3 && p.out_lo;
-    const bool lin_grad = PROD == 1 && p.act == EGV_ACT_NONE && p.out_fmt == 4 && !p.bias;
-    if (!(gelu_fwd || gelu_bwd16 || lin_split || lin_grad) || p.alpha != 1.0f || !p.out_hi || (p.out_fmt == 1 && !p.out_lo) || p.residual ||
-        p.out_f32 || (p.aux_out && !p.aux_bf16) || p.ldoh % 8 != 0 || p.ksplit > 1 || TN)
-      return EGV_ERR_ARG;
-  }
-  if (p.aux_bf16 == 3 && PROD != 1 && PROD != 2) return EGV_ERR_ARG;         // fp16 saved gelu': the fp16 instances only
-  if constexpr (PROD == 1) {
-    // ONE fp16 product.  Forward: fc2 / proj (bias + residual -> fp32), qkv (bias -> planes), fc1 (GELU -> fp16 operand planes).  The fp16
-    // backward (scaled gradients): every dgrad (-> fp32 / planes; fc2's with the GELU' epilogue) and, TN, every weight gradient.
-    if constexpr (TN) {
-      return launch_big<4, true, EPI_RAW, 1>(p, s);              // slabs or direct fp32 output, x alpha
-    } else {
-      if (p.ksplit > 1 || p.alpha != 1.0f) return EGV_ERR_ARG;
-      if (p.act == EGV_ACT_NONE) {
-        if (!p.bias && !p.residual && !p.out_hi && p.out_f32) return launch_big<MF, false, EPI_RAW, 1>(p, s);     // dgrad -> fp32 (LayerNorm backward reads it)
-        return launch_big<MF, false, EPI_LINEAR, 1>(p, s);
-      }
-      if (p.act == EGV_ACT_GELU && p.out_fmt != 0) return launch_big<MF, false, EPI_GELU_X2, 1>(p, s);
-      if (p.act == EGV_ACT_GELU_BWD && !p.bias) return launch_big<MF, false, EPI_GELU_BWD, 1>(p, s);
-      return EGV_ERR_ARG;
+// The instance whose gemm_big_id is `id`: every id is visited at compile time and exactly those of gemm_big_instance are instantiated.
+template <int ID = 0>
+int launch_instance(int id, const GemmPick& g, const egv_gemm_desc& p, hipStream_t s) {
+  if constexpr (ID < GEMM_BIG_IDS) {
+    constexpr int MIXED = ID % 2, PROD = ID / 2 % 4, EPI = ID / 8 % 6, TN = ID / 48 % 2, MF = 4 + ID / 96;
+    static_assert(gemm_big_id(MF, TN, EPI, PROD, MIXED) == ID, "");
+    if constexpr (gemm_big_instance(MF, TN, EPI, PROD, MIXED)) {
+      if (id == ID) return launch_big<MF, TN != 0, EPI, PROD, MIXED != 0>(g, p, s);
     }
+    return launch_instance<ID + 1>(id, g, p, s);
   } else {
-    if (p.ksplit > 1 || TN) {
-      if (PROD == 2) return EGV_ERR_ARG;                              // f16x2: forward products only (un-split, NT)
-      return launch_big<MF, TN, EPI_RAW, PROD>(p, s);                 // split-K slab / wgrad: plain fp32 output
-    }
-    if constexpr (PROD != 0 && MF == 5 && !TN) {
-      // the two multi-round forward shapes of the step (qkv: plane outputs; fc1: GELU + planes + saved gelu') with mixed row bands
-      const int cap = p.grid_cap > 0 ? p.grid_cap : 256;
-      const int nb5 = pick_mixed_bands(p, cap);
-      if (nb5 >= 0 && p.alpha == 1.0f) {
-        if (p.act == EGV_ACT_NONE && (p.bias || p.residual || p.out_hi)) return launch_big<5, false, EPI_LINEAR, PROD, true>(p, s, nb5);
-        if (p.act == EGV_ACT_GELU) {
-          if constexpr (PROD == 2) {
-            if (p.out_fmt != 0) return launch_big<5, false, EPI_GELU_X2, 2, true>(p, s, nb5);
-          }
-          return launch_big<5, false, EPI_GELU, PROD, true>(p, s, nb5);
-        }
-      }
-    }
-    if (p.alpha == 1.0f && p.act == EGV_ACT_NONE) {
-      if (!p.bias && !p.residual && !p.out_hi && p.out_f32) return launch_big<MF, false, EPI_RAW, PROD>(p, s);
-      return launch_big<MF, false, EPI_LINEAR, PROD>(p, s);
-    }
-    if (p.alpha == 1.0f && p.act == EGV_ACT_GELU) {
-      if constexpr (PROD == 2) {
-        if (p.out_fmt != 0) return launch_big<MF, false, EPI_GELU_X2, 2>(p, s);
-      }
-      return launch_big<MF, false, EPI_GELU, PROD>(p, s);
-    }
-    if constexpr (PROD == 2) {
-      return EGV_ERR_ARG;                                             // the forward of the step uses nothing else
-    } else {
-      if (p.alpha == 1.0f && p.act == EGV_ACT_GELU_BWD && !p.bias) return launch_big<MF, false, EPI_GELU_BWD, PROD>(p, s);
-      return launch_big<MF, false, EPI_GENERIC, PROD>(p, s);
-    }
+    return EGV_ERR_ARG;
   }
 }
 
 }  // namespace
 
-// Can the big kernel run this problem?  (NT: K % 64 == 0; both: M, N at least one tile, 16-B aligned rows.)
-bool egv_gemm_big_supports(const egv_gemm_desc& p) {
-  if (p.M < 256 || p.N < BNB || p.N % 4 != 0) return false;
-  if (p.lda % 8 != 0 || p.ldb % 8 != 0) return false;
-  if (p.trans)
-    return p.M % 8 == 0 && p.N % 8 == 0 && p.out_f32 != nullptr && p.act == EGV_ACT_NONE && !p.bias && !p.residual &&
-           !p.out_hi;
-  return p.K % KT == 0;
-}
-
-// rows per block tile (256 or 320) that minimise (rounds on 256 CUs) x (tile cost)
-int egv_gemm_big_pick_mf(const egv_gemm_desc& p) {
-  if (p.trans || p.M < 320) return 4;
-  const int ks = p.ksplit > 1 ? p.ksplit : 1;
-  const int tn = (p.N + BNB - 1) / BNB;
-  long best = -1;
-  int best_mf = 4;
-  for (int mf = 4; mf <= 5; ++mf) {
-    const long tiles = (long)((p.M + mf * 64 - 1) / (mf * 64)) * tn * ks;
-    const long cost = ((tiles + 255) / 256) * mf;
-    if (best < 0 || cost < best || (cost == best && mf == 5)) {
-      best = cost;
-      best_mf = mf;
-    }
-  }
-  return best_mf;
-}
-
-// variant: 0 / 3 = auto; 4 / 5 force MF (diagnostics)
-int egv_gemm_big_launch(const egv_gemm_desc& p, hipStream_t s, int variant) {
-  if (p.trans) return p.passes == 4 ? launch_epi<4, true, 1>(p, s) : launch_epi<4, true>(p, s);
-  int mf = (variant % 10 == 4 || variant % 10 == 5) ? variant % 10 : egv_gemm_big_pick_mf(p);
-  if (p.M < mf * 64) mf = 4;
+void egv_gemm_env(int* x2_seg, int* f3) {
+  // f16x2: the fused two-product loop, or -- short contractions -- two k-segments of the plain fp16 loop
+  // (same box, interleaved: proj 75 -> 68 us, fc2 260 -> 221, fc1 306 -> 292, qkv 208 -> 203; step 950 -> 960.5 pairs/s --
+  // profiles/r06g_x2seg_bench.txt, r06h_ab_x2seg_auxbwd.txt; EGV_X2_SEG=0: the fused loop, 1: only K, N <= 768)
   // bf16x3 (parity-grade) NT products run the fused three-product loop; the three-k-segment form of the plain loop stays
   // reachable in the diagnostics build (EGV_GEMM_F3=0) for A/B runs
-  bool f3 = p.passes == 3;
+  static const int seg_env = getenv("EGV_X2_SEG") ? atoi(getenv("EGV_X2_SEG")) : 2;
+  *x2_seg = seg_env, *f3 = 1;
 #ifdef EGV_DIAG
   static const int f3_env = getenv("EGV_GEMM_F3") ? atoi(getenv("EGV_GEMM_F3")) : 1;
-  f3 = f3 && f3_env != 0;
+  *f3 = f3_env != 0;
 #endif
-  if (p.passes == 2) {      // f16x2: the fused two-product loop, or -- short contractions -- two k-segments of the plain fp16 loop
-    // (same box, interleaved: proj 75 -> 68 us, fc2 260 -> 221, fc1 306 -> 292, qkv 208 -> 203; step 950 -> 960.5 pairs/s --
-    // profiles/r06g_x2seg_bench.txt, r06h_ab_x2seg_auxbwd.txt; EGV_X2_SEG=0: the fused loop, 1: only K, N <= 768)
-    static const int seg_env = getenv("EGV_X2_SEG") ? atoi(getenv("EGV_X2_SEG")) : 2;
-    const bool seg = (seg_env & 2) || ((seg_env & 1) && p.K <= 768 && p.N <= 768);
-    if (seg) return mf == 5 ? launch_epi<5, false, 1>(p, s) : launch_epi<4, false, 1>(p, s);
-    return mf == 5 ? launch_epi<5, false, 2>(p, s) : launch_epi<4, false, 2>(p, s);
-  }
-  if (p.passes == 4) return mf == 5 ? launch_epi<5, false, 1>(p, s) : launch_epi<4, false, 1>(p, s);      // one fp16 product
-  if (f3) return mf == 5 ? launch_epi<5, false, 3>(p, s) : launch_epi<4, false, 3>(p, s);
-  if (mf == 5) return launch_epi<5, false>(p, s);
-  return launch_epi<4, false>(p, s);
+}
+
+int egv_gemm_big_launch(const GemmPick& g, const egv_gemm_desc& p, hipStream_t s) {
+  return launch_instance(gemm_big_id(g.mf, g.tn, g.epi, g.prod, g.mixed), g, p, s);
 }

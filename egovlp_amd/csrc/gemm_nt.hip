@@ -1,7 +1,8 @@
-// gemm_nt: C[M,N] = A[M,K] * B[N,K]^T (+ epilogue) on bf16 MFMA, fp32 accumulate, gfx950.
+// gemm_nt: C[M,N] = A[M,K] * B[N,K]^T (+ epilogue) on bf16 MFMA, fp32 accumulate, gfx950: the 128x128 kernel.
 //
-// This one kernel carries ~95 % of the step's FLOPs (qkv / proj / fc1 / fc2 /
-// patch-embed / DistilBERT linears, and -- with pre-transposed operands -- every dgrad and wgrad).
+// The GEMM of the problems the big-tile kernel (gemm_big.hip, ~95 % of the step's FLOPs) does not take: M too small to fill 256-row
+// tiles (DistilBERT's linears, the projections) or K a multiple of 32 but not of 64.  Also
+// here: the split-K reduces of both kernels and egv_gemm_nt itself, the one entry point (which kernel runs: gemm_dispatch.h).
 //
 // Operand format: "split-bf16" planes.  An fp32-grade tensor X is stored as X_hi = bf16(X) and
 // X_lo = bf16(X - X_hi).  PASSES = 1 reads only the hi planes (plain bf16 GEMM); PASSES = 3 reads
@@ -26,6 +27,7 @@
 // the weight panel they all stream, sit in one XCD's L2.
 #include "common.h"
 #include "egovlp_hip.h"
+#include "gemm_dispatch.h"
 #include "multi_tensor.h"
 
 namespace {
@@ -280,9 +282,6 @@ extern "C" int egv_splitk_reduce_multi(int32_t count, const float* const* partia
       });
 }
 
-int egv_gemm_big_launch(const egv_gemm_desc& p, hipStream_t s, int variant);  // gemm_big.hip
-bool egv_gemm_big_supports(const egv_gemm_desc& p);
-
 // Split-K for the small-M NT problems (DistilBERT: M = 1024 -> 48..192 tiles of 128x128 on 256 CUs, 24..96 k-steps each): the
 // k-slices run as separate workgroups and this kernel sums their slabs and applies the FULL fused epilogue (bias, GELU / GELU'
 // / ReLU', residual, fp32 and / or plane outputs), one 4-column piece per thread.
@@ -296,73 +295,33 @@ __global__ __launch_bounds__(256) void splitk_reduce_epilogue_kernel(const egv_g
   nt_epilogue4(p, s, m, n);
 }
 
-// kernel choice: gemm_big (320/256 x 256 tile, k-tile 64) for the token-major GEMMs and every TN (wgrad) problem; the
-// 128x128 two-stage kernel of this file where M is too small to fill big tiles (DistilBERT, projections) or K is not a
-// multiple of 64.  -> 3 = big, 1 = small, -1 = unsupported.
-static int gemm_variant(const egv_gemm_desc& p) {
-  const bool big_ok = egv_gemm_big_supports(p);
-  if (p.trans) return big_ok ? 3 : -1;
-  if (p.passes == 2 || p.passes == 4) return big_ok ? 3 : -1;   // fp16 operands (f16x2 / one plain plane): the big-tile kernel is the only one that multiplies them
-  // big tiles only when there are enough of them to occupy the chip (DistilBERT's M = 1024 GEMMs make 12)
-  const long big_tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * (p.ksplit > 1 ? p.ksplit : 1);
-  if (big_ok && big_tiles >= 128) return 3;
-  return 1;
-}
-
+// check, pick (gemm_dispatch.h), enqueue the kernel, enqueue the reduce
 extern "C" int egv_gemm_nt(const egv_gemm_desc* d, void* stream) {
   const egv_gemm_desc& p = *d;
-  if (!p.a_hi || !p.b_hi) return EGV_ERR_ARG;
-  if (p.passes < 1 || p.passes > 4) return EGV_ERR_ARG;
-  if ((p.passes == 2 || p.passes == 3) && (!p.a_lo || !p.b_lo)) return EGV_ERR_ARG;
-  if (p.out_fmt < 0 || p.out_fmt > 4) return EGV_ERR_ARG;
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return EGV_ERR_ARG;
-  if (p.N % 4 != 0 || p.lda % 8 != 0 || p.ldb % 8 != 0) return EGV_ERR_ARG;
-  if (!p.trans && p.K % BK != 0) return EGV_ERR_ARG;
-  if (p.ksplit > 1 && !p.partial) return EGV_ERR_ARG;
-  if (p.colsum && !p.trans) return EGV_ERR_ARG;
-  if (p.grid_cap != 0 && (p.grid_cap < 8 || p.grid_cap > 256 || p.grid_cap % 8 != 0)) return EGV_ERR_ARG;
-  const int variant = gemm_variant(p);
-  if (variant < 0) return EGV_ERR_ARG;
-  if (p.aux_bf16 < 0 || p.aux_bf16 > 3) return EGV_ERR_ARG;
-  if (p.aux_bf16 && (variant < 3 || p.act == EGV_ACT_RELU_BWD)) return EGV_ERR_ARG;   // 16-bit aux: gemm_big GELU epilogues only
-  if (p.aux_bf16 == 3 && p.passes != 4 && p.passes != 2) return EGV_ERR_ARG;           // fp16 gelu': fp16-product launches only
-  // fp16 operands / outputs (csrc/f16x2.h; passes 2 = f16x2, 4 = one plain fp16 plane): the big-tile kernel only; NT un-split, or
-  // (passes 4) the TN weight gradient of the fp16 backward with its k-slices
-  if ((p.passes == 2 || p.passes == 4 || p.out_fmt != 0) && (variant < 3 || (p.passes != 2 && p.passes != 4))) return EGV_ERR_ARG;
-  if ((p.passes == 2 || p.out_fmt != 0) && (p.trans || p.ksplit > 1)) return EGV_ERR_ARG;
-  if (p.passes == 4 && !p.trans && p.ksplit > 1) return EGV_ERR_ARG;
-  if (p.alpha != 1.0f && p.trans && !(p.alpha > 0.f)) return EGV_ERR_ARG;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  const int ks = p.ksplit > 1 ? p.ksplit : 1;
-  dim3 grid(tiles, ks), block(256);
+  int x2_seg, f3;
+  egv_gemm_env(&x2_seg, &f3);
+  if (gemm_check(p, x2_seg)) return EGV_ERR_ARG;
+  const GemmPick g = gemm_pick(p, x2_seg, f3);
+  const dim3 grid((unsigned)g.grid_x, (unsigned)g.grid_y), block(g.block);
   hipStream_t s = (hipStream_t)stream;
-  if (variant >= 3) {
-    const int rc = egv_gemm_big_launch(p, s, variant);
+  if (g.family == GEMM_BIG) {
+    const int rc = egv_gemm_big_launch(g, p, s);
     if (rc) return rc;
-  } else if (p.passes == 3) {
-    EGV_LAUNCH(gemm_nt_kernel<3>, grid, block, 2 * 4 * PLANE_BYTES, s, p);
+  } else if (g.passes == 3) {
+    EGV_LAUNCH(gemm_nt_kernel<3>, grid, block, g.lds, s, p);
   } else {
-    EGV_LAUNCH(gemm_nt_kernel<1>, grid, block, 2 * 2 * PLANE_BYTES, s, p);
+    EGV_LAUNCH(gemm_nt_kernel<1>, grid, block, g.lds, s, p);
   }
   EGV_CHECK_LAUNCH();
-  if (ks > 1 && !p.trans && variant < 3) {
+  if (g.reduce == GEMM_RED_EPILOGUE) {
     // small-tile NT kernels: slabs -> sum -> fused epilogue (any combination of outputs)
-    if (p.accumulate) return EGV_ERR_ARG;
-    const long mn4 = (long)p.M * p.N / 4;
-    EGV_LAUNCH(splitk_reduce_epilogue_kernel, dim3((int)((mn4 + 255) / 256)), dim3(256), 0, s, p, ks);
+    EGV_LAUNCH(splitk_reduce_epilogue_kernel, dim3((unsigned)g.reduce_grid), dim3(256), 0, s, p, p.ksplit);
     EGV_CHECK_LAUNCH();
-  } else if (ks > 1 && p.accumulate == 2) {
-    // the caller reduces the slabs itself (egv_splitk_reduce_multi: several weight gradients in one launch)
-    if (!p.trans || !p.out_f32 || p.ldo != p.N) return EGV_ERR_ARG;
-  } else if (ks > 1) {
-    if (!p.out_f32 || p.ldo != p.N) return EGV_ERR_ARG;
-    const long mn = (long)p.M * p.N;
-    const int blocks = (int)((mn / 4 + 255) / 256);
+  } else if (g.reduce == GEMM_RED_SLAB) {
     // the ksplit x M column-sum slab (bias gradient) sits behind the ksplit x M x N product slab: one launch reduces both
-    if (p.colsum && p.M % 4 != 0) return EGV_ERR_ARG;
-    const int blocks2 = p.colsum ? (p.M / 4 + 255) / 256 : 0;
-    EGV_LAUNCH(splitk_reduce_kernel, dim3(blocks + blocks2), dim3(256), 0, s, p.partial, p.out_f32, mn, ks, p.accumulate,
-               p.partial + (long)ks * mn, p.colsum, (long)p.M, blocks);
+    const long mn = (long)p.M * p.N;
+    EGV_LAUNCH(splitk_reduce_kernel, dim3((unsigned)g.reduce_grid), dim3(256), 0, s, p.partial, p.out_f32, mn, p.ksplit, p.accumulate,
+               p.partial + (long)p.ksplit * mn, p.colsum, (long)p.M, (int)g.reduce_blocks1);
     EGV_CHECK_LAUNCH();
   }
   return EGV_OK;

@@ -764,15 +764,17 @@ SMALL_SPLITK = int(os.environ.get("EGV_SMALL_SPLITK", "1"))   # 0: off (A/B diag
 
 
 def uses_big_gemm(M, N, K, passes=None):
-    """Mirror of the kernel choice in csrc/gemm_nt.hip (gemm_variant) for NT problems without split-K (fp16 operands, passes = 2 / 4,
-    always take the big-tile kernel when it can run the shape at all)."""
+    """Does an NT problem without split-K run on the big-tile kernel?  gemm_family of csrc/gemm_dispatch.h, restated here because the
+    host dry-run runs without the library (fp16 operands, passes = 2 / 4, always take the big-tile kernel when it can run the shape
+    at all); tests/test_gemm_dispatch_cpu.py holds the two together."""
     if passes in (2, 4):
         return f16x2_gemm_ok(M, N, K)
     return M >= 256 and N >= 256 and K % 64 == 0 and ((M + 255) // 256) * ((N + 255) // 256) >= 128
 
 
 def f16x2_gemm_ok(M, N, K):
-    """Can egv_gemm_nt(passes = 2) run this NT shape?  (one 256 x 256 tile at least, 64-deep k-tiles)"""
+    """Can egv_gemm_nt(passes = 2 / 4) run this NT shape?  (one 256 x 256 tile at least, 64-deep k-tiles: what gemm_check of
+    csrc/gemm_dispatch.h asks of an fp16 NT launch's shape; pinned to it by tests/test_gemm_dispatch_cpu.py)"""
     return M >= 256 and N >= 256 and K % 64 == 0
 
 
