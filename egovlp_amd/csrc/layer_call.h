@@ -1,11 +1,16 @@
 // Host-side scaffolding of the one-C-call-per-layer entry points (block.hip: egv_block_fwd / _bwd, text_layer.hip: egv_text_layer_fwd /
 // _bwd): the workspace-arena allocator, pointers into an arena, the early return on a failed launch, and the GEMM descriptors every
-// such call fills the same way.  Internal to csrc/; no device code.
+// such call fills the same way, the layout of the one gradient buffer.  Internal to csrc/; plain C++ (block_plan.h builds on it and is
+// compiled on its own by tests/test_block_plan_cpu.py).
 #pragma once
 #include <stdint.h>
 
-#include "common.h"
 #include "egovlp_hip.h"
+
+#ifndef EGV_OK
+#define EGV_OK 0
+#define EGV_ERR_ARG 1
+#endif
 
 // bump allocator over one arena: byte offsets, every allocation 256-byte aligned
 struct Bump {
@@ -29,6 +34,17 @@ const T* at(const void* base, int64_t off) { return off < 0 ? nullptr : (const T
     const int rc__ = (call);         \
     if (rc__ != EGV_OK) return rc__; \
   } while (0)
+
+// gradient buffer of a layer with `nw` weights W[N,K] (nk[i] = {N, K}) and `nln` LayerNorm vectors of D floats: [dW x nw][db x nw]
+// [the (dgamma, dbeta) vectors] back to back, offsets in floats (every size is a multiple of 4 floats: D % 32 == 0)
+static inline void layer_grad_layout(const int64_t (*nk)[2], int nw, int64_t D, int nln, int64_t* off, int64_t& total) {
+  int64_t p = 0;
+  auto take = [&](int64_t n) { const int64_t q = p; p += n; return q; };
+  for (int i = 0; i < nw; ++i) off[i] = take(nk[i][0] * nk[i][1]);
+  for (int i = 0; i < nw; ++i) off[nw + i] = take(nk[i][0]);
+  for (int i = 0; i < nln; ++i) off[2 * nw + i] = take(D);
+  total = p;
+}
 
 // an operand the forward saved in its arena, as the backward reads it: the hi plane, the lo plane only in a three-product backward
 static inline void saved_planes(const void* fwd_arena, int bwd_passes, int64_t hi, int64_t lo, const egv_bf16*& ph, const egv_bf16*& pl) {

@@ -6,6 +6,9 @@
 // results are bit-identical (tests/test_gpu_block.py).  Weight index: 0 = q/k/v fused [3D, D], 1 = out_lin, 2 = lin1, 3 = lin2.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
+#include "common.h"
 #include "layer_call.h"
 
 namespace {
@@ -19,14 +22,10 @@ bool geom_ok(const egv_text_geom& g) {
   return true;
 }
 
-// (N, K) of weight i
-void wshape(const egv_text_geom& g, int i, int64_t& N, int64_t& K) {
-  switch (i) {
-    case 0: N = 3 * (int64_t)g.D; K = g.D; break;
-    case 1: N = g.D; K = g.D; break;
-    case 2: N = g.Hd; K = g.D; break;
-    default: N = g.D; K = g.Hd; break;
-  }
+// (N, K) of W[N,K], weight 0 .. 3
+void text_nk(const egv_text_geom& g, int64_t nk[4][2]) {
+  const int64_t D = g.D, Hd = g.Hd, t[4][2] = {{3 * D, D}, {D, D}, {Hd, D}, {D, Hd}};
+  for (int i = 0; i < 4; ++i) { nk[i][0] = t[i][0]; nk[i][1] = t[i][1]; }
 }
 
 struct FwdLayout {
@@ -55,12 +54,10 @@ FwdLayout fwd_layout(const egv_text_geom& g) {
   L.s2 = b.take(M * D * 4);
   L.mean2 = b.take(M * 4); L.rstd2 = b.take(M * 4);
   // split-K slabs of the four forward GEMMs: one region, the GEMMs follow each other on one stream
-  int64_t pmax = 0;
-  for (int i = 0; i < 4; ++i) {
-    int64_t N, K;
-    wshape(g, i, N, K);
-    if (g.nt_ksplit_fwd[i] > 1) pmax = pmax > g.nt_ksplit_fwd[i] * M * N * 4 ? pmax : g.nt_ksplit_fwd[i] * M * N * 4;
-  }
+  int64_t pmax = 0, nk[4][2];
+  text_nk(g, nk);
+  for (int i = 0; i < 4; ++i)
+    if (g.nt_ksplit_fwd[i] > 1) pmax = std::max(pmax, g.nt_ksplit_fwd[i] * M * nk[i][0] * 4);
   L.partial = pmax ? b.take(pmax) : (int64_t)-1;
   L.total = b.off;
   return L;
@@ -94,18 +91,11 @@ BwdLayout bwd_layout(const egv_text_geom& g) {
   L.dqkv_hi = plane(3 * D); L.dqkv_lo = plane_lo(3 * D);
   L.ln_work = b.take(2 * D * (int64_t)egv_layernorm_bwd_parts((int32_t)M) * 4);
   L.attn_work = b.take((int64_t)g.B * g.H * g.L * 4);
-  int64_t pmax = 0;
+  int64_t pmax = 0, nk[4][2];
+  text_nk(g, nk);
   for (int i = 0; i < 4; ++i) {
-    if (g.nt_ksplit_bwd[i] > 1) {
-      const int64_t by = g.nt_ksplit_bwd[i] * M * bwd_nt_cols(g, i) * 4;
-      pmax = pmax > by ? pmax : by;
-    }
-    int64_t N, K;
-    wshape(g, i, N, K);
-    if (g.wgrad_ksplit[i] > 1) {
-      const int64_t by = (int64_t)g.wgrad_ksplit[i] * (N * K + N) * 4;
-      pmax = pmax > by ? pmax : by;
-    }
+    if (g.nt_ksplit_bwd[i] > 1) pmax = std::max(pmax, g.nt_ksplit_bwd[i] * M * bwd_nt_cols(g, i) * 4);
+    if (g.wgrad_ksplit[i] > 1) pmax = std::max(pmax, (int64_t)g.wgrad_ksplit[i] * (nk[i][0] * nk[i][1] + nk[i][0]) * 4);
   }
   L.partial = pmax ? b.take(pmax) : (int64_t)-1;
   L.total = b.off;
@@ -114,12 +104,9 @@ BwdLayout bwd_layout(const egv_text_geom& g) {
 
 // gradient buffer (floats, back to back): dW x 4, db x 4, sa_layer_norm (dgamma, dbeta), output_layer_norm (dgamma, dbeta)
 void grad_layout(const egv_text_geom& g, int64_t off[12], int64_t& total) {
-  int64_t p = 0;
-  auto take = [&](int64_t n) { const int64_t q = p; p += n; return q; };
-  for (int i = 0; i < 4; ++i) { int64_t N, K; wshape(g, i, N, K); off[i] = take(N * K); }
-  for (int i = 0; i < 4; ++i) { int64_t N, K; wshape(g, i, N, K); off[4 + i] = take(N); }
-  for (int i = 0; i < 4; ++i) off[8 + i] = take(g.D);
-  total = p;
+  int64_t nk[4][2];
+  text_nk(g, nk);
+  layer_grad_layout(nk, 4, g.D, 4, off, total);
 }
 
 }  // namespace
@@ -196,8 +183,9 @@ extern "C" int egv_text_layer_bwd(const egv_text_geom* gp, const egv_text_params
   const egv_text_params& p = *pp;
   const FwdLayout F = fwd_layout(g);
   const BwdLayout L = bwd_layout(g);
-  int64_t goff[12], gtot;
+  int64_t goff[12], gtot, nk[4][2];
   grad_layout(g, goff, gtot);
+  text_nk(g, nk);
   const int Pb = g.bwd_passes;
   const int32_t M = g.B * g.L, D = g.D, Hd = g.Hd;
   for (int i = 0; i < 4; ++i)
@@ -216,9 +204,7 @@ extern "C" int egv_text_layer_bwd(const egv_text_geom* gp, const egv_text_params
   // dW[N,K] = dY^T X (TN kernel; the bias gradient from the same pass) of weight i
   auto wgrad = [&](int i, const egv_bf16* dy_hi, const egv_bf16* dy_lo, int64_t lddy, const egv_bf16* a_hi, const egv_bf16* a_lo,
                    int64_t lda) -> int {
-    int64_t N, K;
-    wshape(g, i, N, K);
-    const egv_gemm_desc d = tn_desc(dy_hi, dy_lo, lddy, a_hi, a_lo, lda, N, K, M, Pb, grads + goff[i], grads + goff[4 + i], g.wgrad_ksplit[i],
+    const egv_gemm_desc d = tn_desc(dy_hi, dy_lo, lddy, a_hi, a_lo, lda, nk[i][0], nk[i][1], M, Pb, grads + goff[i], grads + goff[4 + i], g.wgrad_ksplit[i],
                                     part, g.grid_cap);       // every slab in the one shared region: the GEMMs follow each other on one stream
     return egv_gemm_nt(&d, stream);
   };

@@ -6,6 +6,8 @@ workspace sizes and gradient layout, the views of the one gradient buffer.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+from collections import namedtuple
 
 import torch
 
@@ -103,6 +105,46 @@ def gelu_grad_16bit(ec: ExecContext, M, Hd, D, P):
     """Does the fc1 epilogue of a video block save gelu'(z) in 16 bits (bf16; fp16 for the fp16 backward) instead of the fp32
     pre-activation?  When the backward runs a single product anyway and fc1 is on the big-tile kernel, whose epilogue writes it."""
     return ec.bwd_passes in (1, 4) and ops.uses_big_gemm(M, Hd, D, P)
+
+
+# The operand-format plan of a video block: csrc/block_plan.h's BlockPlan, field by field and in its order (tests/test_block_plan_cpu.py
+# pins this to the header, where each field is described).  Tuples of six are per Linear in the order timeattn.qkv, timeattn.proj,
+# attn.qkv, attn.proj, fc1, fc2: `passes` as ops.gemm_nt takes them, `operand` 0 both planes / 1 the first alone / 2 the second alone,
+# `w_fmt` an index into W_FMTS; `attn_fmt` is an index into ATTN_FMTS; `bf`: bf16 copies of the LayerNorm outputs and of h (want_bf).
+class BlockPlan(namedtuple("BlockPlan", "train tail passes operand w_fmt walpha w_lo ln_f16 lnq_lo ln2_lo qkv_lo attn_lo h_lo bf qkv_fmt attn_passes "
+                           "attn_fmt attn_mode_fwd attn_mode_bwd kv_fmt h_fmt z_code z_bytes bwd_passes bwd_lo saved_bf grad_fmt ln_fmt "
+                           "attn_bwd_passes attn_bwd_o_lo cls_dx_mode")):
+    __slots__ = ()
+    W_FMTS = ("bf16", "f16x2")                               # weight-cache format names
+    ATTN_FMTS = ("bf16", "bf16+f16", "f16x2", "f16")         # ops.divided_attn_fwd out_fmt names
+    fp16_bwd = property(lambda self: self.bwd_passes == 4)
+    wt_fmt = property(lambda self: "f16" if self.bwd_passes == 4 else "bf16")      # W^T planes of the backward
+    single = property(lambda self: tuple(p == 4 for p in self.passes))           # Linears whose first operand is ONE plain fp16 plane
+
+
+A1_INV = 1.0 / (1.0 - 2.0 ** -6)          # csrc/f16x2.h: a1 = fp16((1 - 2^-6) x)
+
+
+@functools.lru_cache(maxsize=None)
+def block_plan(P, Pb, single, train, z_bf16=False):
+    """csrc/block_plan.h::block_plan for an accepted (fwd_passes, bwd_passes, f16_single, egv_block_geom.train, z_bf16)."""
+    x2, h16, lo = P == 2, Pb == 4, P != 1
+    one = tuple(bool(single & b) for b in (4, 8, 4, 8, 1, 2))
+    keep, tail = bool(train & 1), bool(train & 2)
+    attn_passes = 3 if x2 else P
+    attn_fmt = (2 if h16 else 0) | (1 if one[1] else 0)
+    # (passes, operand, w_fmt) per Linear; the proj Linears by attention format
+    proj = ((attn_passes, 0), (4, 2), (2, 0), (4, 1))[attn_fmt] + (int(attn_fmt != 0),)
+    passes, operand, w_fmt = zip(*(proj if i in (1, 3) else (4 if one[i] else P, int(one[i]), int(x2)) for i in range(6)))
+    return BlockPlan(
+        train=keep, tail=tail, passes=passes, operand=operand, w_fmt=w_fmt,
+        walpha=tuple(A1_INV if h16 and not one[i] else 1.0 for i in range(6)),
+        w_lo=lo, ln_f16=x2, lnq_lo=lo and not one[0], ln2_lo=lo and not one[4], qkv_lo=lo, attn_lo=lo and attn_fmt != 3,
+        h_lo=lo and not one[5], bf=x2 and keep and not h16, qkv_fmt=3 if h16 else 0, attn_passes=attn_passes, attn_fmt=attn_fmt,
+        attn_mode_fwd=(attn_fmt << 1) | (8 if h16 else 0), attn_mode_bwd=(attn_fmt << 1) | (24 if h16 else 0), kv_fmt=int(h16),
+        h_fmt=(2 if one[5] else 1) if x2 else 0, z_code=(3 if h16 else 2) if z_bf16 else 0, z_bytes=(2 if z_bf16 else 4) if keep else 0,
+        bwd_passes=Pb, bwd_lo=Pb == 3, saved_bf=x2 and not h16, grad_fmt=4 if h16 else 0, ln_fmt=3 if h16 else 0,
+        attn_bwd_passes=1 if h16 else Pb, attn_bwd_o_lo=attn_fmt == 0, cls_dx_mode=2 if h16 else 1)
 
 
 # ---------------------------------------------------------------------------------------------- one C call per layer

@@ -13,7 +13,9 @@ identical to the reference); their own forward is never called.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from functools import partial
+from typing import Any, NamedTuple
 
 import torch
 from torch import nn
@@ -22,7 +24,24 @@ from .. import _lib, ops
 from .._lib import BlockBwdIO, BlockGeom, BlockParams
 from ..ops import ACT_GELU, ACT_GELU_BWD, ExecContext
 from .layer_common import (PLANE_HANDOFF, _attach_grad_planes, _lin_bwd, _take_grad_planes, bwd_arena_bytes,  # noqa: F401  (PLANE_HANDOFF: tests)
-                           gelu_grad_16bit, grad_views, layer_sizes, need_fwd_arena, param_struct)
+                           block_plan, gelu_grad_16bit, grad_views, layer_sizes, need_fwd_arena, param_struct)
+
+
+class BlockCall(NamedTuple):      # the `geom` argument of the two block nodes; their .apply takes it or a plain tuple in this order
+    B: int
+    T: int
+    n: int
+    H: int
+    eps: float
+    single: int = 0       # ops.F16_SINGLE_BITS: Linears of THIS block that run ONE fp16 product (f16x2 mode)
+    drop: Any = None      # stochastic depth of this forward: (p, seed_space, seed_mlp, seed_dev) or None
+    tail: bool = False    # CLS tail (the tower's last block, C calls only): the output is the [B, D] CLS rows
+
+
+# The `geom` argument of _PatchTokensFn.  P: patch size; mean_std: the loader's Normalize; aug = (boxes, out_res[, colour-jitter table]): the
+# train transform inside the gather; eval = (center_crop, out_res, frame table): the val / test transform inside the gather; keep: patch
+# dropout, int32 [B, K] kept positions on the device
+PatchCall = namedtuple("PatchCall", "B T n P D T_model mean_std aug eval keep", defaults=((ops.IMAGENET_MEAN, ops.IMAGENET_STD), None, None, None))
 
 
 def f16x2_block_ok(M, D, Hd, train):
@@ -39,7 +58,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
          t  = timeattn(norm3(x));  tr = x + t
          s  = attn(norm1(tr));     sr = x + s          (residual from x, NOT tr -- :171)
          out = sr + mlp(norm2(sr))
-    With stochastic depth (:155,:171,:175; geom[6] = (p, seed_space, seed_mlp, seed_dev), set by a train-mode block with p > 0):
+    With stochastic depth (:155,:171,:175; geom.drop = (p, seed_space, seed_mlp, seed_dev), set by a train-mode block with p > 0):
          sr = x + s1[b] * attn(..);  out = sr + s2[b] * mlp(..)       s[b] in {0, 1 / (1 - p)} per sample, ops.drop_path_*
     the proj / fc2 Linears then run without their residual and one egv_drop_path_add merges it; the backward scales the two branch
     gradients while it formats them (egv_drop_path_grad) from the seeds of the forward.
@@ -50,9 +69,8 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
                 n3w, n3b, tqkv_w, tqkv_b, tproj_w, tproj_b,
                 n1w, n1b, sqkv_w, sqkv_b, sproj_w, sproj_b,
                 n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b):
-        B, T, n, H, eps = geom[:5]
-        single = geom[5] if len(geom) > 5 else 0     # ops.F16_SINGLE_BITS: Linears of THIS block that run ONE fp16 product (f16x2 mode)
-        dp = geom[6] if len(geom) > 6 else None      # stochastic depth of this forward: (p, seed_space, seed_mlp, seed_dev) or None
+        geom = BlockCall(*geom)
+        B, T, n, H, eps, single, dp = geom[:7]
         S = 1 + T * n
         D = x.shape[-1]
         M = B * S
@@ -66,56 +84,43 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         # 'f16x2': the LayerNorm -> qkv / fc1 and fc1 -> fc2 hand-overs are in the f16x2 operand format (two fp16 products instead of
         # three bf16 ones, big-tile kernel only); attention and the proj Linears keep split-bf16 three-product operands (Pa).  Token
         # counts too small for the big-tile kernel (toy geometries) run the block in bf16x3.
-        if P == 2 and not f16x2_block_ok(M, D, Hd, train):
-            P = 3
-        fx2 = P == 2
-        Pa = 3 if fx2 else P
-        wf = "f16x2" if fx2 else "bf16"
+        fx2 = P == 2 and f16x2_block_ok(M, D, Hd, train)
         if not fx2:
-            single = 0
-        # the fp16 backward (ec.bwd_passes == 4) reads the forward's own fp16 planes: no bf16 copies; the attention output is fp16 planes only
-        # ('f16': one plane for a one-product proj; 'f16x2': the proj runs TWO fp16 products where it ran three bf16 ones)
-        h16 = fx2 and ec.bwd_passes == 4
-        want_bf = train and not h16
-        s_fc1, s_fc2, s_qkv, s_proj = bool(single & 1), bool(single & 2), bool(single & 4), bool(single & 8)
-        P_qkv, P_fc1, P_fc2, P_proj = (4 if s_qkv else P), (4 if s_fc1 else P), (4 if s_fc2 else P), (4 if s_proj else (2 if h16 else Pa))
-        wp = "f16x2" if (s_proj or h16) else "bf16"       # a single-product proj multiplies fp16(W) (plane 1 of the f16x2 encoding)
-        afmt = ("f16" if s_proj else "f16x2") if h16 else ("bf16+f16" if s_proj else "bf16")
+            P, single = ec.fwd_passes_split, 0
+        # every format below is the plan's (csrc/block_plan.h; the backward of a block that fell back to split-bf16 is no fp16 one)
+        pl = block_plan(P, ec.bwd_passes if fx2 else min(ec.bwd_passes_split, P), single, int(train), gelu_grad_16bit(ec, M, Hd, D, P))
+        h16, want_bf, Pa, afmt = pl.fp16_bwd, pl.bf, pl.attn_passes, pl.ATTN_FMTS[pl.attn_fmt]
+        def lin(i, a, w, **kw):        # forward Linear i of the plan on the planes `a`
+            ops.gemm_nt(a, wc.get(w, need_t=False, fmt=pl.W_FMTS[pl.w_fmt[i]])[0], passes=pl.passes[i], ec=ec, **kw)
 
-        def W(p, fmt="bf16"):
-            return wc.get(p, need_t=False, fmt=fmt)[0]
+        def attn_branch(i, time, inp, nw, nb, qkv_w, qkv_b, proj_w, proj_b, residual):
+            # LayerNorm -> qkv (Linear i) -> attention -> proj (Linear i + 1) + residual.  qkv never exists in fp32: the attention kernels
+            # read planes (split-bf16; an fp16 split when the backward is fp16: the attention then multiplies fp16 in both directions)
+            nrm, _, mean, rstd, _ = ops.layernorm_fwd(inp, nw, nb, eps, P, want_bf=want_bf, single=pl.single[i])
+            qkv = ops.empty_planes_f16x2(M, 3 * D, dev, split=True) if h16 else ops.empty_planes(M, 3 * D, Pa, dev)
+            lin(i, nrm, qkv_w, bias=qkv_b, out_planes=qkv)
+            a, lse = ops.divided_attn_fwd(qkv, B, T, n, H, time, Pa, out_fmt=afmt)
+            res = torch.empty((M, D), dtype=torch.float32, device=dev)
+            lin(i + 1, a, proj_w, bias=proj_b, residual=residual, out_f32=res)
+            return nrm, mean, rstd, qkv, a, lse, res
 
-        # ---- temporal attention branch (:166-167)
-        n3, _, mean3, rstd3, _ = ops.layernorm_fwd(x2, n3w, n3b, eps, P, want_bf=want_bf, single=s_qkv)
-        # qkv never exists in fp32: the attention kernels read planes (split-bf16; an fp16 split when the backward is fp16: the attention
-        # then multiplies fp16 in both directions)
-        qkv_t = ops.empty_planes_f16x2(M, 3 * D, dev, split=True) if h16 else ops.empty_planes(M, 3 * D, Pa, dev)
-        ops.gemm_nt(n3, W(tqkv_w, wf), passes=P_qkv, bias=tqkv_b, out_planes=qkv_t, ec=ec)
-        a_t, lse_t = ops.divided_attn_fwd(qkv_t, B, T, n, H, 1, Pa, out_fmt=afmt)
-        tr = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ops.gemm_nt(a_t, W(tproj_w, wp), passes=P_proj, bias=tproj_b, residual=x2, out_f32=tr, ec=ec)
-        # ---- spatial attention branch (:168-171)
-        n1, _, mean1, rstd1, _ = ops.layernorm_fwd(tr, n1w, n1b, eps, P, want_bf=want_bf, single=s_qkv)
-        qkv_s = ops.empty_planes_f16x2(M, 3 * D, dev, split=True) if h16 else ops.empty_planes(M, 3 * D, Pa, dev)
-        ops.gemm_nt(n1, W(sqkv_w, wf), passes=P_qkv, bias=sqkv_b, out_planes=qkv_s, ec=ec)
-        a_s, lse_s = ops.divided_attn_fwd(qkv_s, B, T, n, H, 0, Pa, out_fmt=afmt)
-        sr = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ops.gemm_nt(a_s, W(sproj_w, wp), passes=P_proj, bias=sproj_b, residual=None if dp else x2, out_f32=sr, ec=ec)
+        # ---- temporal (:166-167) and spatial (:168-171) attention branches
+        n3, mean3, rstd3, qkv_t, a_t, lse_t, tr = attn_branch(0, 1, x2, n3w, n3b, tqkv_w, tqkv_b, tproj_w, tproj_b, x2)
+        n1, mean1, rstd1, qkv_s, a_s, lse_s, sr = attn_branch(2, 0, tr, n1w, n1b, sqkv_w, sqkv_b, sproj_w, sproj_b, None if dp else x2)
         if dp:      # sr = x + s1[b] * attn(..), in place on the branch
             ops.drop_path_add(sr, x2, S, dp[0], dp[1], dp[3])
         # ---- MLP (:175, Mlp.forward :46-52), exact-erf GELU fused into the fc1 epilogue
-        n2, _, mean2, rstd2, _ = ops.layernorm_fwd(sr, n2w, n2b, eps, P, want_bf=want_bf, single=s_fc1)
-        h = ops.empty_planes_f16x2(M, Hd, dev, want_bf=want_bf, single=s_fc2) if fx2 else ops.empty_planes(M, Hd, P, dev)
+        n2, _, mean2, rstd2, _ = ops.layernorm_fwd(sr, n2w, n2b, eps, P, want_bf=want_bf, single=pl.single[4])
+        h = ops.empty_planes_f16x2(M, Hd, dev, want_bf=want_bf, single=pl.single[5]) if fx2 else ops.empty_planes(M, Hd, P, dev)
         # saved for backward: the fp32 pre-activation z in the all-bf16x3 parity mode; when backward runs single-pass bf16
         # anyway, gelu'(z) itself as bf16 -- the epilogue has Phi(z) and phi(z) in registers, the buffer is half the bytes,
         # and the fc2-dgrad epilogue becomes one multiply instead of a second erf evaluation over 77 M elements
         # (the fp16 backward keeps gelu' as fp16: bf16's 2^-9 on the derivative would cap dZ's accuracy)
-        z_dtype = torch.float16 if h16 else (torch.bfloat16 if gelu_grad_16bit(ec, M, Hd, D, P) else torch.float32)
+        z_dtype = {0: torch.float32, 2: torch.bfloat16, 3: torch.float16}[pl.z_code]
         z = torch.empty((M, Hd), dtype=z_dtype, device=dev) if train else None
-        ops.gemm_nt(n2, W(fc1_w, wf), passes=P_fc1, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h,
-                    aux_is_grad=z is not None and z_dtype != torch.float32, ec=ec)
+        lin(4, n2, fc1_w, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h, aux_is_grad=z is not None and pl.z_code != 0)
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
-        ops.gemm_nt(h, W(fc2_w, wf), passes=P_fc2, bias=fc2_b, residual=None if dp else sr, out_f32=out, ec=ec)
+        lin(5, h, fc2_w, bias=fc2_b, residual=None if dp else sr, out_f32=out)
         if dp:      # out = sr + s2[b] * mlp(..)
             ops.drop_path_add(out, sr, S, dp[0], dp[2], dp[3])
 
@@ -131,7 +136,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         (x2, mean3, rstd3, lse_t, tr, mean1, rstd1, lse_s, sr, mean2, rstd2, z,
          n3w, tqkv_w, tproj_w, n1w, sqkv_w, sproj_w, n2w, fc1_w, fc2_w) = ctx.saved_tensors
         n3, a_t, n1, a_s, n2, h, qkv_t, qkv_s = ctx.planes
-        B, T, n, H, eps = ctx.geom[:5]
+        B, T, n, H, eps, _, dp = ctx.geom[:7]          # dp: the forward's stochastic-depth draws
         ec = ctx.ec
         wc = ec.wc
         Pb = ec.bwd_passes
@@ -142,16 +147,14 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
             Pb = min(ec.bwd_passes_split, ctx.P)       # a block too small for the fp16 forward format (toy geometries) ran split-bf16
         if Pb == 3 and ctx.P != 3:
             raise RuntimeError("backward precision bf16x3 needs a bf16x3 forward (the saved activation planes carry no lo part)")
-        h16 = Pb == 4
+        pl = block_plan(ctx.P, Pb, 0, 1)      # (the backward's fields do not depend on which Linears ran one product)
+        h16 = pl.fp16_bwd
         M, D = x2.shape
         G = g_out.contiguous().view(M, D)
 
         def Wt(p):
-            if h16:
-                return wc.get(p, need_t=True, fmt="f16x2", t_fmt="f16")[1]
-            return wc.get(p, need_t=True)[1]
+            return wc.get(p, need_t=True, fmt="f16x2" if h16 else "bf16", t_fmt=pl.wt_fmt)[1]
 
-        dp = ctx.geom[6] if len(ctx.geom) > 6 else None     # the forward's stochastic-depth draws
         S = 1 + T * n
         # ---- MLP backward.  dZ = (G . W2) * gelu'(z) comes out of the fc2-dgrad epilogue already split.
         G_pl = _take_grad_planes(g_out, M, D, Pb)
@@ -165,7 +168,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         ops.gemm_nt(G_pl, Wt(fc2_w), passes=Pb, act=ACT_GELU_BWD, aux_in=z, out_planes=dZ, K=D,
                     aux_is_grad=z.dtype != torch.float32, ec=ec)
         _, d_fc2_w, d_fc2_b = _lin_bwd(G_pl, h, None, Pb, need_dx=False, params=(fc2_w,), ec=ec)
-        ln16 = Pb == 4          # fp16 backward: the dgrads in front of a LayerNorm backward hand it ONE plane of un-clamped fp16 (no fp32 copy)
+        ln16 = pl.grad_fmt != 0          # fp16 backward: the dgrads in front of a LayerNorm backward hand it ONE plane of un-clamped fp16 (no fp32 copy)
         d_n2, d_fc1_w, d_fc1_b = _lin_bwd(dZ, n2, Wt(fc1_w), Pb, dx_planes=ln16, params=(fc1_w,), ec=ec)
         # d_sr = G + LN2'(d_n2)
         if dp:      # the space branch's gradient is s1[b] * d_sr, formatted from the fp32 d_sr
@@ -175,12 +178,12 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
             d_sr, d_n2w, d_n2b, d_sr_pl = ops.layernorm_bwd(d_n2, sr, n2w, mean2, rstd2, add1=G, planes_passes=Pb)
         # ---- spatial attention backward
         d_as, d_sproj_w, d_sproj_b = _lin_bwd(d_sr_pl, a_s, Wt(sproj_w), Pb, dx_planes=True, params=(sproj_w,), ec=ec)
-        d_qkv_s = ops.divided_attn_bwd(qkv_s, a_s, d_as, lse_s, B, T, n, H, 0, 1 if h16 else Pb, grad_f16=h16)
+        d_qkv_s = ops.divided_attn_bwd(qkv_s, a_s, d_as, lse_s, B, T, n, H, 0, pl.attn_bwd_passes, grad_f16=h16)
         d_n1, d_sqkv_w, d_sqkv_b = _lin_bwd(d_qkv_s, n1, Wt(sqkv_w), Pb, dx_planes=ln16, params=(sqkv_w,), ec=ec)
         d_tr, d_n1w, d_n1b, d_tr_pl = ops.layernorm_bwd(d_n1, tr, n1w, mean1, rstd1, planes_passes=Pb)
         # ---- temporal attention backward
         d_at, d_tproj_w, d_tproj_b = _lin_bwd(d_tr_pl, a_t, Wt(tproj_w), Pb, dx_planes=True, params=(tproj_w,), ec=ec)
-        d_qkv_t = ops.divided_attn_bwd(qkv_t, a_t, d_at, lse_t, B, T, n, H, 1, 1 if h16 else Pb, grad_f16=h16)
+        d_qkv_t = ops.divided_attn_bwd(qkv_t, a_t, d_at, lse_t, B, T, n, H, 1, pl.attn_bwd_passes, grad_f16=h16)
         d_n3, d_tqkv_w, d_tqkv_b = _lin_bwd(d_qkv_t, n3, Wt(tqkv_w), Pb, dx_planes=ln16, params=(tqkv_w,), ec=ec)
         # x feeds norm3, the tr residual and the sr residual: dx = d_tr + d_sr + LN3'(d_n3)
         d_x, d_n3w, d_n3b, d_x_pl = ops.layernorm_bwd(d_n3, x2, n3w, mean3, rstd3, add1=d_tr, add2=d_sr,
@@ -226,9 +229,6 @@ def cls_tail_ok(ec: ExecContext, M, D):
     return all(ops.auto_ksplit_nt(*sh) == 1 for sh in ((M, 2 * D, D), (M, D, 2 * D)))
 
 
-_X2_FMTS = ("f16x2", "bf16", "f16x2", "bf16", "f16x2", "f16x2")     # f16x2 mode: qkv / fc1 / fc2 weights in the f16x2 format, proj split-bf16
-
-
 def _tail_params(prm, weights, need_t):
     """egv_block_params of a CLS-tail call: a copy of `prm` in which the fp32 master weights of attn.qkv, attn.proj, fc1, fc2 (read by the
     B-row Linears, csrc/cls_tail.hip) travel in the plane slots of the OTHER direction, which that call does not read -- wt_hi[2..5]
@@ -243,15 +243,13 @@ def _tail_params(prm, weights, need_t):
     return out
 
 
-def _block_params(wc, ln, biases, weights, need_t, x2=False, proj_x2=False, t16=False):
+def _block_params(wc, ln, biases, weights, need_t, pl=block_plan(3, 3, 0, 1)):
     """egv_block_params from the parameter tensors: LayerNorm affine (n3w, n3b, n1w, n1b, n2w, n2b), the six biases and the
     cached operand planes of the six weights (W^T planes too when `need_t`), kept on the model's weight cache, keyed by the block's
     first weight, the direction and the formats (layer_common.param_struct)."""
-    # proj_x2: the proj Linears run one fp16 product in this block -- their forward weights are f16x2 encodings too
-    # t16 (the fp16 backward): the transposed weights are single fp16 planes (wt_lo unused)
-    fmts = [("f16x2" if (proj_x2 and i in (1, 3)) else _X2_FMTS[i]) if x2 else "bf16" for i in range(6)]
-    pls = [wc.get(w, need_t=need_t, fmt=fmts[i], t_fmt="f16" if t16 else "bf16") for i, w in enumerate(weights)]
-    return param_struct(wc, BlockParams, (id(weights[0]), need_t, x2, proj_x2, t16), need_t, ln, biases, pls)
+    # `pl`: the block's plan -- the format of each weight's forward planes and of the W^T planes (default: split-bf16 everywhere)
+    pls = [wc.get(w, need_t=need_t, fmt=pl.W_FMTS[pl.w_fmt[i]], t_fmt=pl.wt_fmt) for i, w in enumerate(weights)]
+    return param_struct(wc, BlockParams, (id(weights[0]), need_t, pl.w_fmt, pl.wt_fmt), need_t, ln, biases, pls)
 
 
 class _SpaceTimeBlockCFn(torch.autograd.Function):
@@ -262,18 +260,19 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
                 n3w, n3b, tqkv_w, tqkv_b, tproj_w, tproj_b,
                 n1w, n1b, sqkv_w, sqkv_b, sproj_w, sproj_b,
                 n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b):
+        geom = BlockCall(*geom)
         B, T, n, H, eps = geom[:5]
         S = 1 + T * n
         D = x.shape[-1]
         M = B * S
         Hd = fc1_w.shape[0]
         P, Pb = ec.fwd_passes, ec.bwd_passes
-        single = (geom[5] if len(geom) > 5 else 0) if P == 2 else 0     # ops.F16_SINGLE_BITS of this block
+        single = geom.single if P == 2 else 0
         dev = x.device
         x2 = x.contiguous().view(M, D)
         save = any(ctx.needs_input_grad)
         train = ec.forward_is_train(ctx)
-        tail = len(geom) > 7 and bool(geom[7])      # CLS tail (the tower's last block): the output is the [B, D] CLS rows
+        tail = bool(geom.tail)
         key = (B, T, n, H, D, Hd, P, Pb, train, gelu_grad_16bit(ec, M, Hd, D, P), single)
         g = _block_geom(*key, eps, ec.gemm_grid, tail)
         ent = layer_sizes("egv_block", key + (tail,), g, 18)
@@ -282,7 +281,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         ln = (n3w, n3b, n1w, n1b, n2w, n2b)
         biases = (tqkv_b, tproj_b, sqkv_b, sproj_b, fc1_b, fc2_b)
         weights = (tqkv_w, tproj_w, sqkv_w, sproj_w, fc1_w, fc2_w)
-        prm = _block_params(ec.wc, ln, biases, weights, need_t=False, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4)
+        prm = _block_params(ec.wc, ln, biases, weights, False, block_plan(P, Pb, single, int(train)))
         if tail:
             prm = _tail_params(prm, weights, need_t=False)
         _lib.check(_lib.lib().egv_block_fwd(C.byref(g), C.byref(prm), x2.data_ptr(), out.data_ptr(), arena.data_ptr(), ops._stream(x2)),
@@ -299,6 +298,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         need_fwd_arena(ctx.arena, "block")
         B, T, n, H, D, Hd, P, Pb, train, z_bf16, single = ctx.key
         ec = ctx.ec
+        pl = block_plan(P, Pb, single, int(train))
         ec.poll_backward()              # gradients of the blocks behind this one are final: the data-parallel exchange may start
         Pb_now = ec.bwd_passes
         if Pb_now != Pb:
@@ -333,7 +333,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         _, goff, gtot = ctx.sizes
         grads = torch.empty(gtot, dtype=torch.float32, device=dev)
         d_x = torch.empty((M, D), dtype=torch.float32, device=dev)
-        dx_pl = ops.empty_planes_f16x2(M, D, dev, single=True) if Pb == 4 else ops.empty_planes(M, D, Pb, dev)
+        dx_pl = ops.empty_planes_f16x2(M, D, dev, single=True) if pl.grad_fmt else ops.empty_planes(M, D, Pb, dev)
         used = {s_ for s_ in streams if s_ is not None}          # the side streams read / write these allocations of the main stream
         if used:
             # held until the side streams are joined (end of backward) instead of record_stream-ed: the multi-GB arenas (see
@@ -342,7 +342,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
             # stream with the caching allocator, which polls every outstanding event on every allocation: with 24 blocks and a host
             # that runs two steps ahead that was ~10 ms of host time per ViT-L/14 step (host_enqueue 26 ms against 16 from idle).
             ec.hold_until_join(ctx.arena, barena, grads, *((g_pl.hi, g_pl.lo) if g_pl is not None else ()))
-        prm = _block_params(ec.wc, ln, biases, weights, need_t=True, x2=P == 2, proj_x2=bool(single & 8) or Pb == 4, t16=Pb == 4)
+        prm = _block_params(ec.wc, ln, biases, weights, True, pl)
         if tail:
             prm = _tail_params(prm, weights, need_t=True)
         P6 = C.c_void_p * 6
@@ -365,18 +365,15 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
 
 class _PatchTokensFn(torch.autograd.Function):
     """VideoPatchEmbed (:72-77) + flatten/CLS/pos/temporal (:305-320): patch gather -> MFMA GEMM (+bias)
-    -> token assembly.  No gradient flows to the input frames.  With patch dropout (geom[9] = keep, int32 [B, K] on the device) all of it
+    -> token assembly.  No gradient flows to the input frames.  With patch dropout (geom.keep, int32 [B, K] on the device) all of it
     runs over the K kept positions of every frame: B*T*K rows in the gather, the GEMM, its saved operand and its weight gradient."""
 
     @staticmethod
     def forward(ctx, video, geom, ec, proj_w, proj_b, cls_token, pos_embed, temporal_embed):
-        B, T, n, P_, D, T_model = geom[:6]
+        geom = PatchCall(*geom)
+        B, T, n, P_, D, T_model, (mean, std), aug, ev, keep = geom
         Pp = ec.fwd_passes_split
         wc = ec.wc
-        mean, std = geom[6] if len(geom) > 6 else (ops.IMAGENET_MEAN, ops.IMAGENET_STD)
-        aug = geom[7] if len(geom) > 7 else None
-        ev = geom[8] if len(geom) > 8 else None
-        keep = geom[9] if len(geom) > 9 else None
         if ev is not None:
             # the val / test transform inside the gather: `video` is the uint8 frame bank, ev = (center_crop, out_res, frame table)
             a = ops.patch_gather_eval(video.contiguous(), ev[2], T, P_, Pp, ev[0], ev[1], mean, std)
@@ -394,7 +391,7 @@ class _PatchTokensFn(torch.autograd.Function):
         pe = torch.empty((a.rows, D), dtype=torch.float32, device=video.device)
         ops.gemm_nt(a, w_pl, passes=Pp, bias=proj_b, out_f32=pe, ec=ec)
         x = ops.assemble_tokens(pe, cls_token, pos_embed, temporal_embed, B, T, n, D, keep=keep)
-        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom[:9], a, Pp, ec
+        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom._replace(keep=None), a, Pp, ec
         ctx.save_for_backward(*(() if keep is None else (keep,)))
         ctx.wshape, ctx.proj_w = proj_w.shape, proj_w
         return x
@@ -531,15 +528,15 @@ class SpaceTimeBlock(nn.Module):
         `ec.cls_tail`) instead of [B, S, D]."""
         # which Linears of THIS block run one fp16 product in the f16x2 mode: the model's precision policy (ops.single_product_policy)
         single = ec.f16_single_mask(getattr(self, "layer_index", None), getattr(self, "depth", None)) if ec.fwd_passes == 2 else 0
-        geom = (B, T, n, self.num_heads, self.norm1.eps, single)
+        geom = BlockCall(B, T, n, self.num_heads, self.norm1.eps, single)
         if self.training and self.drop_path > 0.:
             if drop_seeds is None:
                 raise ValueError("SpaceTimeBlock: a train-mode forward with drop_path > 0 needs its seeds (drop_seeds)")
-            geom = geom + ((self.drop_path,) + tuple(drop_seeds),)
-        fn = _SpaceTimeBlockCFn if block_calls_ok(ec, B * (1 + T * n), x.shape[-1], self.mlp.fc1.weight.shape[0], drop_path=len(geom) > 6) \
+            geom = geom._replace(drop=(self.drop_path,) + tuple(drop_seeds))
+        fn = _SpaceTimeBlockCFn if block_calls_ok(ec, B * (1 + T * n), x.shape[-1], self.mlp.fc1.weight.shape[0], drop_path=geom.drop is not None) \
             else _SpaceTimeBlockFn
         if cls_only and fn is _SpaceTimeBlockCFn and cls_tail_ok(ec, B * (1 + T * n), x.shape[-1]):
-            geom = geom + (None, True)
+            geom = geom._replace(tail=True)
         return fn.apply(
             x, geom, ec,
             self.norm3.weight, self.norm3.bias, self.timeattn.qkv.weight, self.timeattn.qkv.bias,
@@ -730,8 +727,8 @@ class SpaceTimeTransformer(nn.Module):
             raise NotImplementedError("input resolution must match the positional embedding")
         # `input_norm` = (mean, std) of the loader's Normalize (data_loader/transforms.py:34-39); only used when the frames
         # arrive as decoded uint8 (then x / 255 and the normalisation are fused into the patch gather on the device)
-        geom = (b, curr_frames, n, P_, self.embed_dim, self.num_frames,
-                getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev)
+        geom = PatchCall(b, curr_frames, n, P_, self.embed_dim, self.num_frames,
+                         getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev)
         ec = self.exec_ctx
         drops = self.training and any(blk.drop_path > 0. for blk in self.blocks)
         patch_drop = self.training and self.patch_drop_rate > 0.
@@ -746,7 +743,7 @@ class SpaceTimeTransformer(nn.Module):
             kept = self.patch_keep_count(n)
             self.last_patch_keep = ops.patch_keep_draw(b, n, kept, self._seed(self.PATCH_DROP_SITE), self.seed_device,
                                                        device=self.cls_token.device)
-            geom = geom + (self.last_patch_keep,)
+            geom = geom._replace(keep=self.last_patch_keep)
         x = _PatchTokensFn.apply(x, geom, ec, self.patch_embed.proj.weight, self.patch_embed.proj.bias,
                                  self.cls_token, self.pos_embed, self.temporal_embed)
         last = len(self.blocks) - 1

@@ -159,8 +159,12 @@ int egv_layernorm_fwd_f16x2(const float* x, int64_t ldx, const float* gamma, con
  * per-kernel entry points above (LayerNorm -> qkv GEMM -> divided attention -> proj GEMM, twice, then fc1 / GELU / fc2), with every
  * intermediate in ONE caller-provided arena per direction -- what costs the host ~50 tensor allocations and ~30 calls per block
  * otherwise.  Token-major [M = B (1 + T n), D] fp32 residual stream; D = 64 H.
- * fwd_passes / bwd_passes: 3 = split-bf16 three-product, 1 = single-pass bf16 (bwd_passes <= fwd_passes); train != 0 keeps what
- * the backward needs (z_bf16 != 0: fc1 saves gelu'(z) as bf16 -- single-pass backward -- instead of the fp32 pre-activation).
+ * fwd_passes: 3 = split-bf16 three-product, 1 = single-pass bf16, 2 = the f16x2 format (two fp16 products in the qkv / fc1 / fc2
+ * Linears, or one where f16_single says so; attention and, unless the backward is fp16, the proj Linears stay split-bf16).
+ * bwd_passes: 3 (fwd_passes 3 only), 1 (any forward), or 4 = ONE fp16 product on loss-scaled gradients (fwd_passes 2 only: it reads
+ * the forward's own fp16 planes).  train bit 0 keeps what the backward needs (z_bf16 != 0: fc1 saves gelu'(z) in 16 bits -- bf16, fp16
+ * for bwd_passes 4; single-product backwards, required with fwd_passes 2 -- instead of the fp32 pre-activation).  Every decision that
+ * follows from these five words is made once, in csrc/block_plan.h.
  * The forward arena must stay untouched until egv_block_bwd has run on it.
  * CLS tail (train bit 1; the tower's LAST block, whose output is read on the B CLS rows only -- norm(x)[:, 0], :330): `out` of
  * egv_block_fwd is the dense [B, D] fp32 CLS rows and io.g_out of egv_block_bwd their [B, D] gradient (io.g_hi NULL); d_x stays
