@@ -96,11 +96,22 @@ inline int gemm_check(const egv_gemm_desc& p, int x2_seg) {
   if (p.out_fmt < 0 || p.out_fmt > 4 || p.aux_bf16 < 0 || p.aux_bf16 > 3) return EGV_ERR_ARG;
   if (p.grid_cap != 0 && (p.grid_cap < 8 || p.grid_cap > GEMM_BIG_WGS || p.grid_cap % 8 != 0)) return EGV_ERR_ARG;
   if ((ks > 1 && !p.partial) || (p.colsum && !p.trans)) return EGV_ERR_ARG;
+  if ((p.act == EGV_ACT_GELU_BWD || p.act == EGV_ACT_RELU_BWD) && !p.aux_in) return EGV_ERR_ARG;        // (the epilogues read it unasked)
   const int family = gemm_family(p);
   if (family < 0) return EGV_ERR_ARG;
   // what only the big kernel, and only its fp16 products, can do
   if (p.aux_bf16 && (family != GEMM_BIG || p.act == EGV_ACT_RELU_BWD)) return EGV_ERR_ARG;   // 16-bit aux: the GELU epilogues
   if ((p.aux_bf16 == 3 || p.out_fmt != 0) && !fp16) return EGV_ERR_ARG;                        // fp16 gelu', fp16 plane outputs
+  // ... and fp16 gelu' is known to the plane epilogue alone (planes and nothing else): the rolled one takes every 16-bit aux for bf16
+  if (p.aux_bf16 == 3 && (p.act == EGV_ACT_GELU || p.act == EGV_ACT_GELU_BWD) && (!p.out_hi || p.residual || p.out_f32)) return EGV_ERR_ARG;
+  // The big kernel computes the columns its shifted last tile shares with the tile before it twice and stores both results.  Its plane
+  // epilogue gives a lane 8 consecutive columns, so with N % 8 != 0 an element sits in the other half of a lane's piece the second time.
+  // The linear epilogues are the same fp32 additions there; the erf ones are not bit for bit (read from the ISA of
+  // gemm_big_kernel<5, false, EPI_GELU_BWD, 3>: hipcc contracts `1 - half` of gelu_parts to an fma in the second half of the piece and
+  // leaves a multiply and a subtract in the first), and two planes stored by two workgroups can then pair the hi of one result
+  // with the lo of the other: one bf16 ulp of the value (tests/test_gpu_gemm_elements.py, refused-gelu-planes-N260).  A single
+  // plane cannot pair, but which of two results it holds would still depend on the order of two workgroups: refused alike.
+  if (family == GEMM_BIG && p.out_hi && p.N % 8 != 0 && (p.act == EGV_ACT_GELU || p.act == EGV_ACT_GELU_BWD)) return EGV_ERR_ARG;
   // fp16 operands / outputs (csrc/f16x2.h): NT un-split, or (passes 4) the TN weight gradient of the fp16 backward with its k-slices
   if (fp16 && (p.trans ? p.passes == 2 || p.out_fmt != 0 : ks > 1)) return EGV_ERR_ARG;
   if (p.trans && p.alpha != 1.0f && !(p.alpha > 0.f)) return EGV_ERR_ARG;                      // (a NaN is refused)

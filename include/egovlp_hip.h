@@ -50,12 +50,19 @@ enum { EGV_ACT_NONE = 0, EGV_ACT_GELU = 1, EGV_ACT_GELU_BWD = 2, EGV_ACT_RELU_BW
  * 1 / (1 - 2^-6) when X is plane 1 of an f16x2 first-operand encoding -- but not the column sums).  Requirements: K % 32 == 0, N % 4 == 0,
  * lda % 8 == ldb % 8 == 0, 16-byte aligned base pointers.
  *  act = EGV_ACT_GELU      : v = gelu(v); if aux_out != NULL the pre-activation is stored there first
- *  act = EGV_ACT_GELU_BWD  : v *= gelu'(aux_in[m,n])           (fc2 dgrad -> dZ)
- *  act = EGV_ACT_RELU_BWD  : v  = aux_in[m,n] > 0 ? v : 0
+ *  act = EGV_ACT_GELU_BWD  : v *= gelu'(aux_in[m,n])           (fc2 dgrad -> dZ; aux_in NULL is an invalid argument)
+ *  act = EGV_ACT_RELU_BWD  : v  = aux_in[m,n] > 0 ? v : 0      (likewise)
  * Outputs: any subset of out_f32 / (out_hi[, out_lo]).  Split-K (ksplit > 1, used by wgrad where
  * K = #tokens): raw partial sums go to partial[ksplit][M][N] and a second kernel reduces them into
  * out_f32 (ldo must equal N; accumulate == 1 adds to the existing contents; accumulate == 2, trans == 1 only: the slabs are left
- * un-reduced for egv_splitk_reduce_multi); no epilogue then.   */
+ * un-reduced for egv_splitk_reduce_multi); no epilogue then.
+ * What "no epilogue" means, per kernel (csrc/gemm_dispatch.h says which one a shape takes): a split-K launch of the 128x128 kernel applies
+ * the WHOLE epilogue in its reduce (alpha, bias, activation, residual, every output; accumulate must be 0); a split-K launch of the
+ * big-tile kernel writes the plain sum of the products to out_f32 -- NT: alpha, bias, act and residual are NOT applied even when given;
+ * trans == 1: alpha scales the products (not the column sums).  `accumulate` is read by that slab reduce only: an un-split launch
+ * (ksplit <= 1) overwrites its outputs whatever `accumulate` says.
+ * Plane outputs of EGV_ACT_GELU / EGV_ACT_GELU_BWD from the big-tile kernel require N % 8 == 0 (the columns two tiles share are computed
+ * twice, and only then bit-identically: gemm_dispatch.h); every other combination takes any N % 4 == 0.   */
 typedef struct egv_gemm_desc {
   const egv_bf16* a_hi; const egv_bf16* a_lo; int64_t lda;
   const egv_bf16* b_hi; const egv_bf16* b_lo; int64_t ldb;
@@ -74,8 +81,9 @@ typedef struct egv_gemm_desc {
                        fc2's dgrad: half the bytes when backward runs single-pass bf16 anyway).  Big-tile kernel only.
                        2: the bf16 buffer holds gelu'(pre-activation) itself -- EGV_ACT_GELU stores the derivative (it has
                        Phi and phi in registers) and EGV_ACT_GELU_BWD multiplies by the stored value, no second erf.
-                       3: as 2 with the derivative stored as FP16 (passes == 2 / 4 launches only): the fp16 backward, where bf16's
-                       2^-9 on gelu' would cap the accuracy of dZ.
+                       3: as 2 with the derivative stored as FP16 (passes == 2 / 4 launches only; plane outputs and neither
+                       out_f32 nor residual next to them -- anything else is an invalid argument: only the plane epilogue
+                       reads and writes fp16 there): the fp16 backward, where bf16's 2^-9 on gelu' would cap the accuracy of dZ.
                        trans = 0: A[M,K], B[N,K] (contraction index contiguous).  1 ("TN", wgrad): A is stored [K, lda] with
                        its M rows as COLUMNS and B is stored [K, ldb] with N columns, C[m,n] = sum_k A[k,m] B[k,n] --
                        no transposed copy of either operand is ever made (CDNA4 transpose-read from LDS).  Requires

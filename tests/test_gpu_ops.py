@@ -150,8 +150,13 @@ def test_gemm_splitk_wgrad_shape(ops, passes):
 @pytest.mark.parametrize("M,N,K", [(1570, 768, 768), (1024, 256, 64), (2011, 512, 192), (1100, 320, 128), (1300, 2304, 128),
                                    (25120, 768, 64)])
 def test_gemm_big_tiles(ops, passes, M, N, K):
-    """gemm_big.hip (320x256 / 256x256 tiles, k-tile 64): ragged last tile row / column (shifted inwards, computed
-    twice); the last shape is the EgoClip token count, where the 320-row tile (MF = 5) is selected."""
+    """Ragged NT shapes on both GEMM kernels.  A bf16 / bf16x3 product takes gemm_big.hip (320x256 / 256x256 tiles, last tile row /
+    column shifted inwards and computed twice) only from 128 tiles of 256x256 (gemm_family, csrc/gemm_dispatch.h): of these shapes that
+    is the last one alone, (25120, 768, 64), the EgoClip token count, where the 320-row tile (MF = 5) is selected and the last row band is
+    shifted.  (1570, 768, 768), (1024, 256, 64), (2011, 512, 192), (1100, 320, 128) and (1300, 2304, 128) make 4 to 54 such tiles and run
+    on the 128x128 kernel of gemm_nt.hip with its clipped last tiles.  The shifted tile COLUMN of the big kernel and its instances are
+    tests/test_gpu_gemm_elements.py's."""
+    assert ops.uses_big_gemm(M, N, K, passes) == ((M, N, K) == (25120, 768, 64))
     g = torch.Generator().manual_seed(M * 7 + N + K)
     a = torch.randn(M, K, generator=g)
     b = torch.randn(N, K, generator=g) * 0.05
