@@ -6,6 +6,7 @@ would void the parity claims.
 """
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 # ORDER MATTERS: PyTorch-ROCm ships its own libamdhip64 (HIP 7.0) while libegovlp_hip.so was linked against
 # /opt/rocm's (7.2).  Both have SONAME libamdhip64.so.7, so whichever is loaded first serves the whole process.
@@ -192,6 +193,24 @@ PROTOTYPES = {
     "egv_diag_mfma_peak": (i32, [i32, i32, c_p, c_p]),
     "egv_diag_traffic_calib": (i32, [i32, c_p, c_p, i64, c_p]),
 }
+
+# Every enumerator of include/egovlp_hip.h (activation, format and mode codes), by its name there -- the one place in the package
+# that spells these values; tests/test_abi.py compiles the header and requires this table to equal it exactly.
+CODES = {
+    "EGV_ACT_NONE": 0, "EGV_ACT_GELU": 1, "EGV_ACT_GELU_BWD": 2, "EGV_ACT_RELU_BWD": 3,
+    "EGV_OUT_BF16_SPLIT": 0, "EGV_OUT_F16X2": 1, "EGV_OUT_F16": 2, "EGV_OUT_F16_SPLIT": 3, "EGV_OUT_F16_GRAD": 4,
+    "EGV_AUX_F32": 0, "EGV_AUX_Z_BF16": 1, "EGV_AUX_DGELU_BF16": 2, "EGV_AUX_DGELU_F16": 3,
+    "EGV_ATTN_OUT_BF16_SPLIT": 0, "EGV_ATTN_OUT_BF16_F16": 1, "EGV_ATTN_OUT_F16X2": 2, "EGV_ATTN_OUT_F16": 3,
+    "EGV_ATTN_TIME": 1, "EGV_ATTN_OUT_SHIFT": 1, "EGV_ATTN_OUT_MASK": 3,
+    "EGV_ATTN_FWD_QKV_F16": 8, "EGV_ATTN_BWD_GRAD_F16": 8, "EGV_ATTN_BWD_QKV_F16": 16,
+    "EGV_LN_DX_F16": 1, "EGV_LN_DY_F16": 2,
+    "EGV_F16X2_FIRST": 0, "EGV_F16X2_SECOND": 1, "EGV_F16X2_GRAD_CAST": 2,
+    "EGV_TRAIN_KEEP": 1, "EGV_TRAIN_CLS_TAIL": 2,
+    "EGV_SINGLE_FC1": 1, "EGV_SINGLE_FC2": 2, "EGV_SINGLE_QKV": 4, "EGV_SINGLE_PROJ": 8,
+    "EGV_CLS_KV_BF16": 0, "EGV_CLS_KV_F16": 1,
+    "EGV_CLS_DX_STORE": 0, "EGV_CLS_DX_ADD_F32": 1, "EGV_CLS_DX_ADD_F16": 2,
+}
+EGV = SimpleNamespace(**{name[4:]: value for name, value in CODES.items()})      # EGV.OUT_F16X2 is CODES["EGV_OUT_F16X2"]
 
 ABI_VERSION = 6      # EGV_ABI_VERSION of the header this binding was written against (include/egovlp_hip.h)
 _lib = None

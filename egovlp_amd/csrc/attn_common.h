@@ -194,22 +194,25 @@ __device__ __forceinline__ f32x4_t att_mma(bf16x8_t ah, bf16x8_t al, bf16x8_t bh
 //  MODE_TEXT : separate q,k,v [B,L,H*64]; group = (b, h); nq = nk = L; key j masked if mask[b,j] == 0
 enum { MODE_SPACE = 0, MODE_TEXT = 2 };
 
-// one output pair in the plane formats of the attention forward (egv_divided_attn_fwd, mode >> 1):
-//   0  hi = bf16 pair, lo = the bf16 residual pair (split planes: a three-product proj)
-//   1  hi = bf16 pair (what a bf16 backward reads), lo = the fp16 pair of the VALUES (the proj Linear runs ONE fp16 product)
-//   2  the f16x2 operand format, first-operand role (csrc/f16x2.h): hi = a1 = fp16((1 - e) v), lo = a2 = fp16(v - a1) -- a two-product proj
-//      whose backward is fp16 as well (the weight gradient reads a1, the attention backward takes O = a1 / (1 - e))
-//   3  hi = fp16(value), nothing else (the second plane does not exist): one-product proj, fp16 backward
-enum { ATT_OUT_SPLIT = 0, ATT_OUT_BF16_F16 = 1, ATT_OUT_F16X2 = 2, ATT_OUT_F16 = 3, ATT_GRAD_F16 = 4 };
+// one output pair in the plane formats of the attention forward (EGV_ATTN_OUT_*, the format field of egv_divided_attn_fwd's mode):
+//   _BF16_SPLIT  hi = bf16 pair, lo = the bf16 residual pair (split planes: a three-product proj)
+//   _BF16_F16    hi = bf16 pair (what a bf16 backward reads), lo = the fp16 pair of the VALUES (the proj Linear runs ONE fp16 product)
+//   _F16X2       the f16x2 operand format, first-operand role (csrc/f16x2.h): hi = a1 = fp16((1 - e) v), lo = a2 = fp16(v - a1) -- a two-product
+//                proj whose backward is fp16 as well (the weight gradient reads a1, the attention backward takes O = a1 / (1 - e))
+//   _F16         hi = fp16(value), nothing else (the second plane does not exist): one-product proj, fp16 backward
+// and, through the same argument, the gradient planes of the backward: split-bf16 (0 in both numberings) or ATT_GRAD_F16
+enum { ATT_GRAD_F16 = 4 };
+static_assert(ATT_GRAD_F16 == EGV_OUT_F16_GRAD && EGV_OUT_BF16_SPLIT == EGV_ATTN_OUT_BF16_SPLIT && ATT_GRAD_F16 > EGV_ATTN_OUT_MASK,
+              "g_fmt (att_check_divided_bwd) arrives in the GEMM's numbering and shares att_out2's fmt argument with the EGV_ATTN_OUT_* codes");
 __device__ __forceinline__ void att_out2(float a, float b, int fmt, uint32_t& hi, uint32_t& lo) {
-  if (fmt == ATT_OUT_F16X2) {       // f16x2_a on the pair, packed conversions
+  if (fmt == EGV_ATTN_OUT_F16X2) {       // f16x2_a on the pair, packed conversions
     const float x0 = f16x2_clamp(a), x1 = f16x2_clamp(b);
     const f16pk_h2_t h = __builtin_convertvector(((f16pk_f2_t){x0 - x0 * F16X2_E, x1 - x1 * F16X2_E}), f16pk_h2_t);
     hi = __builtin_bit_cast(uint32_t, h);
     lo = f16_pk(x0 - (float)h[0], x1 - (float)h[1]);
     return;
   }
-  if (fmt == ATT_OUT_F16) {
+  if (fmt == EGV_ATTN_OUT_F16) {
     hi = lo = f16_pk(f16x2_clamp(a), f16x2_clamp(b));
     return;
   }
@@ -218,19 +221,19 @@ __device__ __forceinline__ void att_out2(float a, float b, int fmt, uint32_t& hi
     return;
   }
   split_bf16x2(a, b, hi, lo);
-  if (fmt) lo = f16_pk(f16x2_clamp(a), f16x2_clamp(b));
+  if (fmt != EGV_ATTN_OUT_BF16_SPLIT) lo = f16_pk(f16x2_clamp(a), f16x2_clamp(b));      // EGV_ATTN_OUT_BF16_F16
 }
 // the forward output O as the backward reads it back (delta = rowsum(dO o O)): one 32-bit word of the first plane (and of the second,
-// fmt 0 only) -> two fp32 values
+// EGV_ATTN_OUT_BF16_SPLIT only) -> two fp32 values
 __device__ __forceinline__ void att_o_unpack(uint32_t w_hi, uint32_t w_lo, bool has_lo, int fmt, float& x, float& y) {
-  if (fmt == ATT_OUT_F16X2 || fmt == ATT_OUT_F16) {
+  if (fmt == EGV_ATTN_OUT_F16X2 || fmt == EGV_ATTN_OUT_F16) {
     f16x2_unpack(w_hi, x, y);
-    if (fmt == ATT_OUT_F16X2) { x *= (1.0f / (1.0f - F16X2_E)); y *= (1.0f / (1.0f - F16X2_E)); }
+    if (fmt == EGV_ATTN_OUT_F16X2) { x *= (1.0f / (1.0f - F16X2_E)); y *= (1.0f / (1.0f - F16X2_E)); }
     return;
   }
   x = __uint_as_float(w_hi << 16);
   y = __uint_as_float(w_hi & 0xffff0000u);
-  if (has_lo && fmt == ATT_OUT_SPLIT) { x += __uint_as_float(w_lo << 16); y += __uint_as_float(w_lo & 0xffff0000u); }
+  if (has_lo && fmt == EGV_ATTN_OUT_BF16_SPLIT) { x += __uint_as_float(w_lo << 16); y += __uint_as_float(w_lo & 0xffff0000u); }
 }
 
 struct AttGeom {
@@ -245,7 +248,7 @@ struct AttGeom {
   const long long* mask;  // MODE_TEXT only
   EgvDrop drop;           // MODE_TEXT only: attention-probability dropout (thresh == 0: none); element index
                           // ((b * H + h) * S + query) * S + key
-  int out_fmt;            // format of the output planes (ATT_OUT_*, see att_out2)
+  int out_fmt;            // format of the output planes (EGV_ATTN_OUT_*, see att_out2)
   int f16;                // MODE_SPACE: the qkv planes (and, backward, the dO planes) hold fp16 -- (hi, lo) = (fp16(x), fp16(x - hi)) -- and
                           // every product runs on the fp16 MFMA
 };
@@ -292,11 +295,11 @@ struct AttGrad {
   float* delta;        // [B, H, S] workspace (written by dQ kernel, read by dKV kernel; slot 0 = the CLS row's delta,
                        //  precomputed by egv_attn_cls_delta in MODE_SPACE)
   float* dcls;         // MODE_SPACE: [B, H, 3, 64] fp32 accumulators of the CLS token's raw dq / dk / dv (zeroed first)
-  int o_fmt;           // MODE_SPACE: format of the forward's output planes (attn_common.h ATT_OUT_*)
-  int g_fmt;           // MODE_SPACE: format of the gradient planes: 0 = split-bf16 (hi[, lo]), ATT_GRAD_F16 = ONE plane of un-clamped fp16
+  int o_fmt;           // MODE_SPACE: format of the forward's output planes (EGV_ATTN_OUT_*)
+  int g_fmt;           // MODE_SPACE: format of the gradient planes: EGV_OUT_BF16_SPLIT (hi[, lo]), ATT_GRAD_F16 = ONE plane of un-clamped fp16
 };
 
-__device__ __forceinline__ void store_planes4(bf16_t* hi, bf16_t* lo, long off, f32x4_t v, int fmt = 0) {
+__device__ __forceinline__ void store_planes4(bf16_t* hi, bf16_t* lo, long off, f32x4_t v, int fmt = EGV_ATTN_OUT_BF16_SPLIT) {
   uint32_t h0, h1, l0, l1;
   att_out2(v[0], v[1], fmt, h0, l0);
   att_out2(v[2], v[3], fmt, h1, l1);
@@ -304,7 +307,7 @@ __device__ __forceinline__ void store_planes4(bf16_t* hi, bf16_t* lo, long off, 
   if (lo) egv_store<EGV_NT_SPACE_ATTN>(lo + off, (u32x2_t){l0, l1});
 }
 
-// a = dO (split-bf16), b = O in the format the forward wrote it (b_fmt: ATT_OUT_*)
+// a = dO (split-bf16), b = O in the format the forward wrote it (b_fmt: EGV_ATTN_OUT_*)
 template <bool F16 = false>
 __device__ __forceinline__ float frag_dot8(bf16x8_t ah, bf16x8_t al, bool a_lo, bf16x8_t bh, bf16x8_t bl, bool b_lo, int b_fmt) {
   const u32x4_t a0 = __builtin_bit_cast(u32x4_t, ah), a1 = __builtin_bit_cast(u32x4_t, al);

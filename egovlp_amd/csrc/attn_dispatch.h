@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/egovlp_hip.h"      // by its place in the tree: the CPU tests compile this file with csrc alone on the include path
+
 #ifndef EGV_OK
 #define EGV_OK 0
 #define EGV_ERR_ARG 1
@@ -30,39 +32,41 @@ inline int att_check_divided_sizes(int B, int T, int n, int H, int time, int pas
 }
 
 struct AttDividedFwd {
-  int time;               // mode bit 0: time attention, else space
-  int out_fmt;            // mode bits 1-2: format of the output planes (attn_common.h ATT_OUT_*), three-product forward only
-  int f16;                // mode bit 3: the qkv planes are an fp16 split: fp16 MFMA products, three-product forward only
+  int time;               // EGV_ATTN_TIME: time attention, else space
+  int out_fmt;            // EGV_ATTN_OUT_*: format of the output planes, three-product forward only
+  int f16;                // EGV_ATTN_FWD_QKV_F16: the qkv planes are an fp16 split: fp16 MFMA products, three-product forward only
   bool qkv_lo, out_lo;
 };
 inline int att_check_divided_fwd(int B, int T, int n, int H, int mode, int passes, bool required, bool qkv_lo, bool out_lo,
                                  AttDividedFwd* d) {
-  if (!required || mode < 0 || mode > 15) return EGV_ERR_ARG;
-  *d = {mode & 1, (mode >> 1) & 3, (mode >> 3) & 1, qkv_lo, out_lo};
+  if (!required || mode < 0 || mode > (EGV_ATTN_TIME | EGV_ATTN_OUT_MASK << EGV_ATTN_OUT_SHIFT | EGV_ATTN_FWD_QKV_F16)) return EGV_ERR_ARG;
+  *d = {mode & EGV_ATTN_TIME, (mode >> EGV_ATTN_OUT_SHIFT) & EGV_ATTN_OUT_MASK, (mode & EGV_ATTN_FWD_QKV_F16) != 0, qkv_lo, out_lo};
   if (att_check_divided_sizes(B, T, n, H, d->time, passes)) return EGV_ERR_ARG;
-  if ((d->f16 || d->out_fmt) && passes != 3) return EGV_ERR_ARG;
-  if (d->out_fmt == 3) d->out_lo = false;                     // ONE plane of fp16(value)
-  if (passes == 3 && (!qkv_lo || (!d->out_lo && d->out_fmt != 3))) return EGV_ERR_ARG;
+  if ((d->f16 || d->out_fmt != EGV_ATTN_OUT_BF16_SPLIT) && passes != 3) return EGV_ERR_ARG;
+  if (d->out_fmt == EGV_ATTN_OUT_F16) d->out_lo = false;                     // ONE plane of fp16(value)
+  if (passes == 3 && (!qkv_lo || (!d->out_lo && d->out_fmt != EGV_ATTN_OUT_F16))) return EGV_ERR_ARG;
   if (passes == 1) d->qkv_lo = d->out_lo = false;
   return EGV_OK;
 }
 
 struct AttDividedBwd {
-  int time;               // mode bit 0
-  int o_fmt;              // mode bits 1-2: the format the forward wrote its output planes in
-  int g_fmt;              // mode bit 3: dqkv as ONE plane of un-clamped fp16 (ATT_GRAD_F16 = 4) instead of split-bf16 (0); passes == 1 only
-  int f16;                // mode bit 4: q / k / v / dO are fp16 planes; with bit 3 and passes == 1 only
+  int time;               // EGV_ATTN_TIME
+  int o_fmt;              // EGV_ATTN_OUT_*: the format the forward wrote its output planes in
+  int g_fmt;              // EGV_ATTN_BWD_GRAD_F16: dqkv in the format the GEMMs that read it call EGV_OUT_F16_GRAD (ONE plane of un-clamped
+                          // fp16) instead of EGV_OUT_BF16_SPLIT; passes == 1 only
+  int f16;                // EGV_ATTN_BWD_QKV_F16: q / k / v / dO are fp16 planes; with EGV_ATTN_BWD_GRAD_F16 and passes == 1 only
   bool qkv_lo, out_lo, dout_lo, dqkv_lo;
 };
 inline int att_check_divided_bwd(int B, int T, int n, int H, int mode, int passes, bool required, bool qkv_lo, bool out_lo,
                                  bool dout_lo, bool dqkv_lo, AttDividedBwd* d) {
-  if (!required || mode < 0 || mode > 31) return EGV_ERR_ARG;
-  *d = {mode & 1, (mode >> 1) & 3, (mode & 8) ? 4 : 0, (mode >> 4) & 1, qkv_lo, out_lo, dout_lo, dqkv_lo};
+  if (!required || mode < 0 || mode > (EGV_ATTN_TIME | EGV_ATTN_OUT_MASK << EGV_ATTN_OUT_SHIFT | EGV_ATTN_BWD_GRAD_F16 | EGV_ATTN_BWD_QKV_F16)) return EGV_ERR_ARG;
+  *d = {mode & EGV_ATTN_TIME, (mode >> EGV_ATTN_OUT_SHIFT) & EGV_ATTN_OUT_MASK, (mode & EGV_ATTN_BWD_GRAD_F16) ? EGV_OUT_F16_GRAD : EGV_OUT_BF16_SPLIT,
+        (mode & EGV_ATTN_BWD_QKV_F16) != 0, qkv_lo, out_lo, dout_lo, dqkv_lo};
   if (att_check_divided_sizes(B, T, n, H, d->time, passes)) return EGV_ERR_ARG;
   if (d->f16 && !d->g_fmt) return EGV_ERR_ARG;
-  if ((d->o_fmt >= 2 || d->g_fmt) && passes != 1) return EGV_ERR_ARG;
-  if (d->o_fmt) d->out_lo = false;                            // only the split-bf16 format has a residual plane
-  if (passes == 3 && (!qkv_lo || (!out_lo && d->o_fmt == 0) || !dout_lo || !dqkv_lo)) return EGV_ERR_ARG;
+  if ((d->o_fmt >= EGV_ATTN_OUT_F16X2 || d->g_fmt) && passes != 1) return EGV_ERR_ARG;      // fp16 outputs: an fp16 backward
+  if (d->o_fmt != EGV_ATTN_OUT_BF16_SPLIT) d->out_lo = false;                            // only the split-bf16 format has a residual plane
+  if (passes == 3 && (!qkv_lo || (!out_lo && d->o_fmt == EGV_ATTN_OUT_BF16_SPLIT) || !dout_lo || !dqkv_lo)) return EGV_ERR_ARG;
   // single-pass: first planes only -- except the forward's output, whose residual plane (if the caller has one: a three-pass forward)
   // makes delta = rowsum(dO o O) exact in O at no cost
   if (passes == 1) d->qkv_lo = d->dout_lo = d->dqkv_lo = false;

@@ -8,7 +8,7 @@
 //   forward : workgroup = (group, block of 128 queries): 8 waves, one 16-query tile each.  The workgroup walks the group's keys in
 //             tiles of 64 (K and V planes in the swizzled image of attn_common.h); a wave keeps the online-softmax state of its
 //             tile -- running maximum (exp2 domain), running sum, O accumulator rescaled ONCE per 64-key tile -- and writes what
-//             the LDS-resident forward writes: output planes in every ATT_OUT_* format, lse, and (space mode) the CLS query's
+//             the LDS-resident forward writes: output planes in every EGV_ATTN_OUT_* format, lse, and (space mode) the CLS query's
 //             un-normalised partial for egv_attn_cls_combine.  The CLS query rides as query row n, as there.
 //   dQ      : the same ownership and the same K / V ring; probabilities are rebuilt from the saved lse, so nothing is rescaled.
 //             Space mode takes delta = rowsum(dO o O) from the forward's output planes (the CLS row's from egv_attn_cls_delta);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(LONG_WAVES * 64, long_min_waves(MODE, PASSES)) void
   } else if (qi < g.nq) {
     const float inv = 1.0f / l;
     bf16_t* oh = out_hi + qtok * out_stride + hoff;
-    bf16_t* ol = out_lo ? out_lo + qtok * out_stride + hoff : nullptr;          // ATT_OUT_F16 / single product: no second plane
+    bf16_t* ol = out_lo ? out_lo + qtok * out_stride + hoff : nullptr;          // EGV_ATTN_OUT_F16 / single product: no second plane
 #pragma unroll
     for (int df = 0; df < 4; ++df) {
       uint32_t h0, h1, l0, l1;

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream3_kernel(const AttGeom g,
     } else if (qi < g.nq) {
       const float inv = 1.0f / l;
       bf16_t* oh = out_hi + qtok * out_stride + hoff;
-      bf16_t* ol = out_lo ? out_lo + qtok * out_stride + hoff : nullptr;      // ATT_OUT_F16: no second plane
+      bf16_t* ol = out_lo ? out_lo + qtok * out_stride + hoff : nullptr;      // EGV_ATTN_OUT_F16: no second plane
 #pragma unroll
       for (int df = 0; df < 4; ++df) {
         uint32_t h0, h1, l0, l1;

@@ -58,14 +58,14 @@ __global__ __launch_bounds__(256) void attn_cls_combine_kernel(const float* __re
     oo /= ll;
     bf16_t hh, lo2;
     split_bf16(oo, hh, lo2);
-    if (out_fmt == 1) lo2 = __builtin_bit_cast(unsigned short, (_Float16)f16x2_clamp(oo));      // second plane = fp16(value)
-    if (out_fmt == 2) {          // f16x2, first-operand role
+    if (out_fmt == EGV_ATTN_OUT_BF16_F16) lo2 = __builtin_bit_cast(unsigned short, (_Float16)f16x2_clamp(oo));      // second plane = fp16(value)
+    if (out_fmt == EGV_ATTN_OUT_F16X2) {          // f16x2, first-operand role
       _Float16 a1, a2;
       f16x2_a(oo, a1, a2);
       hh = __builtin_bit_cast(unsigned short, a1);
       lo2 = __builtin_bit_cast(unsigned short, a2);
     }
-    if (out_fmt == 3) hh = __builtin_bit_cast(unsigned short, (_Float16)f16x2_clamp(oo));         // the only plane = fp16(value)
+    if (out_fmt == EGV_ATTN_OUT_F16) hh = __builtin_bit_cast(unsigned short, (_Float16)f16x2_clamp(oo));         // the only plane = fp16(value)
     const long off = (long)b * S * H * D + (long)h * D + t;
     out_hi[off] = hh;
     if (out_lo) out_lo[off] = lo2;
@@ -86,12 +86,12 @@ __global__ __launch_bounds__(64) void attn_cls_delta_kernel(const bf16_t* __rest
   }
   const long off = (long)b * S * H * D + (long)h * D + lane;
   float o, g = f16 ? (float)__builtin_bit_cast(_Float16, doh[off]) : bf16_to_f32(doh[off]);      // dO: an fp16 plane in the fp16 attention backward
-  if (o_fmt == 2 || o_fmt == 3) {       // the forward wrote fp16 planes (attn_common.h ATT_OUT_F16X2 / ATT_OUT_F16): O from the first one
+  if (o_fmt == EGV_ATTN_OUT_F16X2 || o_fmt == EGV_ATTN_OUT_F16) {       // the forward wrote fp16 planes: O from the first one
     o = (float)__builtin_bit_cast(_Float16, oh[off]);
-    if (o_fmt == 2) o *= 1.0f / (1.0f - F16X2_E);
+    if (o_fmt == EGV_ATTN_OUT_F16X2) o *= 1.0f / (1.0f - F16X2_E);
   } else {
     o = bf16_to_f32(oh[off]);
-    if (ol && o_fmt == 0) o += bf16_to_f32(ol[off]);
+    if (ol && o_fmt == EGV_ATTN_OUT_BF16_SPLIT) o += bf16_to_f32(ol[off]);
   }
   if (dol) g += bf16_to_f32(dol[off]);
   const float d = wave_sum(o * g);
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64) void attn_cls_finish_kernel(const float* __rest
   for (int part = 0; part < 3; ++part) {
     bf16_t hh, ll;
     split_bf16(v[part], hh, ll);
-    if (gfmt == 4) hh = __builtin_bit_cast(unsigned short, (_Float16)v[part]);      // un-clamped fp16 (the fp16 backward)
+    if (gfmt == EGV_OUT_F16_GRAD) hh = __builtin_bit_cast(unsigned short, (_Float16)v[part]);      // un-clamped fp16 (the fp16 backward)
     gh[off + part * HD] = hh;
     if (gl) gl[off + part * HD] = ll;
   }

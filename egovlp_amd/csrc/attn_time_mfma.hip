@@ -83,7 +83,7 @@ __device__ __forceinline__ bf16x8_t frag_rows20(const char* img, int col0, int l
   return __builtin_bit_cast(bf16x8_t, z);
 }
 
-__device__ __forceinline__ void store4(bf16_t* __restrict__ ph, bf16_t* __restrict__ pl, long off, const f32x4_t& v, float scale, int fmt = 0) {
+__device__ __forceinline__ void store4(bf16_t* __restrict__ ph, bf16_t* __restrict__ pl, long off, const f32x4_t& v, float scale, int fmt = EGV_ATTN_OUT_BF16_SPLIT) {
   uint32_t h0, h1, l0, l1;
   att_out2(v[0] * scale, v[1] * scale, fmt, h0, l0);
   att_out2(v[2] * scale, v[3] * scale, fmt, h1, l1);

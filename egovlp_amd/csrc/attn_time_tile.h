@@ -57,7 +57,7 @@ __device__ __forceinline__ f32x4_t mma2(const bf16x8_t (&ah)[2], const bf16x8_t 
 // 16 x 64 tile of a plane is staged in the wave's own LDS instead (the image layout: 128-B rows, 16-B chunk XOR (row & 7); LDS
 // operations of a wave execute in order, so no barrier) and leaves as whole rows: lane -> (row 8 it + (l >> 3), chunk l & 7), one
 // 16-byte store per lane, 8 lanes per 128-byte row.  -DEGV_TMF_OLD_STORES: the direct 8-byte stores (A/B builds).
-__device__ __forceinline__ void stage4(char* sh, char* sl, int p, int col, const f32x4_t& v, float scale, int fmt = 0) {
+__device__ __forceinline__ void stage4(char* sh, char* sl, int p, int col, const f32x4_t& v, float scale, int fmt = EGV_ATTN_OUT_BF16_SPLIT) {
   uint32_t h0, h1, l0, l1;
   att_out2(v[0] * scale, v[1] * scale, fmt, h0, l0);
   att_out2(v[2] * scale, v[3] * scale, fmt, h1, l1);

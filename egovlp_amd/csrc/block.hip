@@ -5,7 +5,7 @@
 // (egovlp_amd/model/video_transformer.py::_SpaceTimeBlockFn, kept as the reference) gives them, in the same order -- results are
 // bit-identical (tests/test_gpu_block.py).  Which geometries are accepted, every operand format and the layout of the two arenas are
 // csrc/block_plan.h's; a call here is check, plan, layout, enqueue.
-// CLS-tail mode (egv_block_geom.train bit 1, the tower's last block): only the B CLS rows of the output are wanted, so what follows the
+// CLS-tail mode (egv_block_geom.train EGV_TRAIN_CLS_TAIL, the tower's last block): only the B CLS rows of the output are wanted, so what follows the
 // k / v projection of the space branch runs on B rows through the egv_cls_* entry points (csrc/cls_tail.hip; tests/test_gpu_cls_tail.py).
 #include <hip/hip_runtime.h>
 
@@ -59,7 +59,7 @@ struct Call {
     EGV_TRY(layernorm(A, in, gw, gb, r.n_hi, r.n_lo, r.n_bf, r.mean, r.rstd));
     EGV_TRY(qkv_linear(A, r, wi));
     egv_bf16 *a_hi = at<egv_bf16>(A, r.a_hi), *a_lo = at<egv_bf16>(A, r.a_lo);
-    EGV_TRY(egv_divided_attn_fwd(at<egv_bf16>(A, r.qkv_hi), at<egv_bf16>(A, r.qkv_lo), g.B, g.T, g.n, g.H, time | pl.attn_mode_fwd, pl.attn_passes,
+    EGV_TRY(egv_divided_attn_fwd(at<egv_bf16>(A, r.qkv_hi), at<egv_bf16>(A, r.qkv_lo), g.B, g.T, g.n, g.H, block_attn_mode(pl.attn_mode_fwd, time), pl.attn_passes,
                                  a_hi, a_lo, at<float>(A, r.lse), at<float>(A, r.work), stream));
     egv_gemm_desc d = linear(wi + 1, a_hi, a_lo);
     d.residual = x; d.ldr = D; d.out_f32 = res; d.ldo = D;
@@ -181,14 +181,14 @@ struct Bwd : Call {
   // ... into the input of a LayerNorm backward (d_n2, d_n1, d_n3): fp32; in the fp16 backward ONE plane of un-clamped fp16 in the same
   // buffer (half the bytes written here and read there: 77 -> 38.6 MB per launch at M = 25 120)
   int to_ln(egv_gemm_desc d, float* buf) const {
-    if (pl.grad_fmt) return to_planes(d, (egv_bf16*)buf, nullptr);
+    if (pl.grad_fmt == EGV_OUT_F16_GRAD) return to_planes(d, (egv_bf16*)buf, nullptr);
     d.out_f32 = buf; d.ldo = D;
     return egv_gemm_nt(&d, stream);
   }
   // dx = add1 + add2 + LN'(d_n) of the LayerNorm whose forward read `x`: fp32 and planes; the affine gradients' partial sums into ln_work[w]
   int ln_bwd(const float* d_n, const float* x, int64_t ldx, const float* gw, int64_t mean, int64_t rstd, int32_t rows, const float* add1,
              const float* add2, float* dx, egv_bf16* dx_hi, egv_bf16* dx_lo, int fmt, int gi, int w) const {
-    const bool plane = fmt != 0;
+    const bool plane = (fmt & EGV_LN_DY_F16) != 0;
     return egv_layernorm_bwd_partial(plane ? nullptr : d_n, plane ? (const egv_bf16*)d_n : nullptr, nullptr, D, x, ldx, gw, at<float>(FA, mean),
                                      at<float>(FA, rstd), rows, D, add1, add2, dx, D, dx_hi, dx_lo, fmt, grads + goff[gi], grads + goff[gi + 1],
                                      at<float>(A, L.ln_work[w]), stream);
@@ -210,7 +210,7 @@ struct Bwd : Call {
     // the attention backward takes the forward output's second plane whenever it is a bf16 lo plane, also in a single-pass backward
     // (delta = rowsum(dO o O) exact in O: egv_divided_attn_bwd)
     EGV_TRY(egv_divided_attn_bwd(q_hi, q_lo, a_hi, pl.attn_bwd_o_lo ? at<egv_bf16>(FA, f.a_lo) : nullptr, do_hi, do_lo, at<float>(FA, f.lse), g.B, g.T,
-                                 g.n, g.H, time | pl.attn_mode_bwd, pl.attn_bwd_passes, dq_hi, dq_lo, at<float>(A, L.attn_work), stream));
+                                 g.n, g.H, block_attn_mode(pl.attn_mode_bwd, time), pl.attn_bwd_passes, dq_hi, dq_lo, at<float>(A, L.attn_work), stream));
     EGV_TRY(wgrad(wi, dq_hi, dq_lo, n_hi, n_lo));
     return to_ln(dgrad(wi, dq_hi, dq_lo), at<float>(A, r.d_n));
   }
@@ -236,13 +236,13 @@ struct Bwd : Call {
                   *hc = at<float>(FA, F.hc);
       float *dzc = at<float>(A, L.dzc), *dn2c = at<float>(A, L.dn2c), *dsrc = at<float>(A, L.dsrc), *doc = at<float>(A, L.doc),
             *dqc = at<float>(A, L.dqc), *lw = at<float>(A, L.lin_work);
-      EGV_TRY(egv_cls_linear_dgrad(G, D, w_fc2, Hd, B, D, Hd, at<float>(FA, F.z), dzc, Hd, 0, lw, stream));
+      EGV_TRY(egv_cls_linear_dgrad(G, D, w_fc2, Hd, B, D, Hd, at<float>(FA, F.z), dzc, Hd, EGV_CLS_DX_STORE, lw, stream));
       EGV_TRY(egv_cls_linear_wgrad(G, D, hc, Hd, B, D, Hd, grads + goff[5], Hd, grads + goff[11], stream));
-      EGV_TRY(egv_cls_linear_dgrad(dzc, Hd, w_fc1, D, B, Hd, D, nullptr, dn2c, D, 0, lw, stream));
+      EGV_TRY(egv_cls_linear_dgrad(dzc, Hd, w_fc1, D, B, Hd, D, nullptr, dn2c, D, EGV_CLS_DX_STORE, lw, stream));
       EGV_TRY(egv_cls_linear_wgrad(dzc, Hd, n2c, D, B, Hd, D, grads + goff[4], D, grads + goff[10], stream));
       EGV_TRY(ln_bwd(dn2c, sr, D, p.n2w, F.mean2, F.rstd2, B, G, nullptr, dsrc, nullptr, nullptr, 0, 16, 0));
       EGV_TRY(egv_cls_linear_wgrad(dsrc, D, oc, D, B, D, D, grads + goff[3], D, grads + goff[9], stream));
-      EGV_TRY(egv_cls_linear_dgrad(dsrc, D, w_proj, D, B, D, D, nullptr, doc, D, 0, lw, stream));
+      EGV_TRY(egv_cls_linear_dgrad(dsrc, D, w_proj, D, B, D, D, nullptr, doc, D, EGV_CLS_DX_STORE, lw, stream));
       uint16_t *dkv_hi = at<uint16_t>(A, L.s.dqkv_hi), *dkv_lo = at<uint16_t>(A, L.s.dqkv_lo);
       const uint16_t *kv_hi = at<uint16_t>(FA, F.s.qkv_hi), *kv_lo = at<uint16_t>(FA, F.s.qkv_lo);
       EGV_TRY(egv_cls_attn_bwd(qc, D, kv_hi, kv_lo, kv_hi + D, kv_lo ? kv_lo + D : nullptr, 2 * D, pl.kv_fmt, oc, doc, at<float>(FA, F.s.lse), B,
@@ -259,7 +259,7 @@ struct Bwd : Call {
       const egv_bf16 *g_hi = io.g_hi, *g_lo = pl.bwd_lo ? io.g_lo : nullptr;
       if (!g_hi) {
         egv_bf16 *gh = at<egv_bf16>(A, L.g_hi), *gl = at<egv_bf16>(A, L.g_lo);
-        if (pl.grad_fmt) EGV_TRY(egv_f16x2_encode(io.g_out, D, M, D, gh, nullptr, nullptr, D, 2, stream));
+        if (pl.grad_fmt == EGV_OUT_F16_GRAD) EGV_TRY(egv_f16x2_encode(io.g_out, D, M, D, gh, nullptr, nullptr, D, EGV_F16X2_GRAD_CAST, stream));
         else EGV_TRY(egv_split_f32(io.g_out, D, M, D, gh, gl, D, nullptr, nullptr, 0, nullptr, stream));
         g_hi = gh; g_lo = gl;
       }
@@ -347,7 +347,7 @@ extern "C" int egv_block_fwd(const egv_block_geom* g, const egv_block_params* p,
 }
 
 extern "C" int egv_block_bwd(const egv_block_geom* g, const egv_block_params* p, const egv_block_bwd_io* io, void* stream) {
-  if (!ok(g) || !p || !io || !(g->train & 1)) return EGV_ERR_ARG;
+  if (!ok(g) || !p || !io || !(g->train & EGV_TRAIN_KEEP)) return EGV_ERR_ARG;
   if (!io->g_out || !io->x || !io->fwd_arena || !io->bwd_arena || !io->d_x || !io->dx_hi || !io->grads) return EGV_ERR_ARG;
   return Bwd(*g, *p, *io, stream).backward();
 }

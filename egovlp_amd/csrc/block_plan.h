@@ -19,31 +19,31 @@ enum { WFMT_BF16, WFMT_F16X2 };          // weight planes: split-bf16 (hi[, lo])
 
 constexpr float BLOCK_A1_INV = 1.0f / (1.0f - 0.015625f);      // csrc/f16x2.h: a1 = fp16((1 - 2^-6) x)
 
-// train, tail: egv_block_geom.train bit 0 (keep what the backward needs), bit 1 (CLS tail)
+// train, tail: egv_block_geom.train EGV_TRAIN_KEEP (keep what the backward needs), EGV_TRAIN_CLS_TAIL
 // ---- per Linear
 // passes      forward products, as egv_gemm_desc.passes: 1 bf16, 3 split-bf16, 2 f16x2, 4 ONE fp16 product
 // operand     OPND_*: which saved planes are its first operand (the proj Linears read the attention's SECOND plane alone when that
-//             plane holds fp16(value) next to a bf16 plane, attn_fmt 1)
+//             plane holds fp16(value) next to a bf16 plane, EGV_ATTN_OUT_BF16_F16)
 // w_fmt       WFMT_*: the format of w_hi / w_lo it multiplies;  w_lo: the forward reads w_lo (every format but one bf16 product)
 // walpha      weight-gradient rescale: 1 / (1 - 2^-6) where the fp16 backward reads a1 of an f16x2 encoding as X
 // ---- per hand-over: planes and formats
 // ln_f16      LayerNorm outputs through egv_layernorm_fwd_f16x2 (fp16 planes) instead of split-bf16
 // lnq_lo, ln2_lo, qkv_lo, attn_lo, h_lo   second plane of norm3 / norm1 (-> qkv), of norm2 (-> fc1), of qkv, the attention outputs, h
 // bf          bf16 copies of the LayerNorm outputs and of h: the single-pass bf16 backward of an f16x2 forward reads them
-// qkv_fmt     out_fmt of the qkv GEMMs: 0 split-bf16, 3 an fp16 split (the fp16 attention's operands)
+// qkv_fmt     out_fmt of the qkv GEMMs: EGV_OUT_BF16_SPLIT, or EGV_OUT_F16_SPLIT (the fp16 attention's operands)
 // attn_passes attention forward: split-bf16 three-product operands in the f16x2 mode
-// attn_fmt    what the attention writes: 0 split-bf16, 1 bf16 + fp16(value), 2 f16x2 planes, 3 ONE plane of fp16(value)
-// attn_mode_fwd, attn_mode_bwd   the mode words of egv_divided_attn_fwd / _bwd without the branch bit
-// kv_fmt      egv_cls_attn_*: 0 bf16 planes, 1 fp16 planes (k / v operands and, in the backward, dk / dv)
-// h_fmt       out_fmt of fc1: 0 split-bf16, 1 f16x2, 2 ONE plain fp16 plane
-// z_code      aux_bf16 of fc1 / the fc2 dgrad: 0 the fp32 pre-activation, 2 gelu' as bf16, 3 gelu' as fp16;  z_bytes per element, 0: not kept
+// attn_fmt    what the attention writes, EGV_ATTN_OUT_*: split-bf16, bf16 + fp16(value), f16x2 planes, ONE plane of fp16(value)
+// attn_mode_fwd, attn_mode_bwd   the mode words of egv_divided_attn_fwd / _bwd without EGV_ATTN_TIME (block_attn_mode adds it)
+// kv_fmt      egv_cls_attn_*: EGV_CLS_KV_BF16 or EGV_CLS_KV_F16 planes (k / v operands and, in the backward, dk / dv)
+// h_fmt       out_fmt of fc1: EGV_OUT_BF16_SPLIT, EGV_OUT_F16X2, or EGV_OUT_F16 (ONE plain fp16 plane)
+// z_code      aux_bf16 of fc1 / the fc2 dgrad: EGV_AUX_F32 (the pre-activation), EGV_AUX_DGELU_BF16, EGV_AUX_DGELU_F16;  z_bytes per element, 0: not kept
 // ---- backward
 // bwd_passes  passes of every GEMM of the backward (4: one fp16 product on un-clamped fp16 gradients)
 // bwd_lo      three-product backward: lo planes of gradients, saved operands and W^T;  saved_bf: its activation operands are the bf16 copies
-// grad_fmt    out_fmt of dZ, dO and the three LayerNorm-backward inputs: 0 split-bf16 (LayerNorm inputs: fp32), 4 ONE fp16 plane
-// ln_fmt      dx_fmt of egv_layernorm_bwd_partial;  attn_bwd_passes: of egv_divided_attn_bwd
+// grad_fmt    out_fmt of dZ, dO and the three LayerNorm-backward inputs: EGV_OUT_BF16_SPLIT (LayerNorm inputs: fp32) or EGV_OUT_F16_GRAD
+// ln_fmt      dx_fmt of egv_layernorm_bwd_partial (EGV_LN_* bits);  attn_bwd_passes: of egv_divided_attn_bwd
 // attn_bwd_o_lo  the attention backward is handed O's second plane (delta exact in O) -- not when that plane is fp16
-// cls_dx_mode egv_cls_linear_dgrad onto the d_n1 the big dgrad wrote: 1 fp32, 2 a plane of un-clamped fp16
+// cls_dx_mode egv_cls_linear_dgrad onto the d_n1 the big dgrad wrote: EGV_CLS_DX_ADD_F32, or _ADD_F16 (a plane of un-clamped fp16)
 struct BlockPlan {
   bool train, tail;
   int passes[6], operand[6], w_fmt[6];
@@ -60,9 +60,9 @@ inline int block_check(const egv_block_geom& g) {
   // (forward, backward): bf16 (1, 1); split-bf16 three-product (3, 3) or (3, 1); f16x2 (2, 1), or (2, 4): one FP16 product on scaled
   // gradients, which reads the forward's own fp16 planes
   if (!((Pb == 1 && P >= 1 && P <= 3) || (Pb == 3 && P == 3) || (Pb == 4 && P == 2))) return EGV_ERR_ARG;
-  if (g.train < 0 || g.train > 3) return EGV_ERR_ARG;
-  if (P == 2 && (g.train & 1) && !g.z_bf16) return EGV_ERR_ARG;      // the fc1 epilogue of the f16x2 format saves gelu' in 16 bits
-  if (g.f16_single < 0 || g.f16_single > 15 || (g.f16_single && P != 2)) return EGV_ERR_ARG;
+  if (g.train < 0 || g.train > (EGV_TRAIN_KEEP | EGV_TRAIN_CLS_TAIL)) return EGV_ERR_ARG;
+  if (P == 2 && (g.train & EGV_TRAIN_KEEP) && !g.z_bf16) return EGV_ERR_ARG;      // the fc1 epilogue of the f16x2 format saves gelu' in 16 bits
+  if (g.f16_single < 0 || g.f16_single > (EGV_SINGLE_FC1 | EGV_SINGLE_FC2 | EGV_SINGLE_QKV | EGV_SINGLE_PROJ) || (g.f16_single && P != 2)) return EGV_ERR_ARG;
   return EGV_OK;
 }
 
@@ -71,17 +71,18 @@ inline BlockPlan block_plan(const egv_block_geom& g) {
   const int P = g.fwd_passes;
   const bool x2 = P == 2, h16 = g.bwd_passes == 4, lo = P != 1;      // h16, the fp16 backward: no bf16 copies, fp16 planes only
   const int s = g.f16_single;
-  const bool one[6] = {(s & 4) != 0, (s & 8) != 0, (s & 4) != 0, (s & 8) != 0, (s & 1) != 0, (s & 2) != 0};      // ONE fp16 product
-  pl.train = (g.train & 1) != 0;
-  pl.tail = (g.train & 2) != 0;
+  const bool one[6] = {(s & EGV_SINGLE_QKV) != 0, (s & EGV_SINGLE_PROJ) != 0, (s & EGV_SINGLE_QKV) != 0, (s & EGV_SINGLE_PROJ) != 0,
+                       (s & EGV_SINGLE_FC1) != 0, (s & EGV_SINGLE_FC2) != 0};      // ONE fp16 product
+  pl.train = (g.train & EGV_TRAIN_KEEP) != 0;
+  pl.tail = (g.train & EGV_TRAIN_CLS_TAIL) != 0;
   pl.attn_passes = x2 ? 3 : P;
-  pl.attn_fmt = (h16 ? 2 : 0) | (one[LIN_TPROJ] ? 1 : 0);
+  pl.attn_fmt = h16 ? (one[LIN_TPROJ] ? EGV_ATTN_OUT_F16 : EGV_ATTN_OUT_F16X2) : (one[LIN_TPROJ] ? EGV_ATTN_OUT_BF16_F16 : EGV_ATTN_OUT_BF16_SPLIT);
   for (int i = 0; i < 6; ++i) {
     if (i == LIN_TPROJ || i == LIN_SPROJ) {      // by attention format: bf16 planes; fp16(value) beside them; f16x2 planes; fp16(value) alone
       const int passes[4] = {pl.attn_passes, 4, 2, 4}, operand[4] = {OPND_BOTH, OPND_SECOND, OPND_BOTH, OPND_FIRST};
       pl.passes[i] = passes[pl.attn_fmt];
       pl.operand[i] = operand[pl.attn_fmt];
-      pl.w_fmt[i] = pl.attn_fmt ? WFMT_F16X2 : WFMT_BF16;
+      pl.w_fmt[i] = pl.attn_fmt != EGV_ATTN_OUT_BF16_SPLIT ? WFMT_F16X2 : WFMT_BF16;
     } else {
       pl.passes[i] = one[i] ? 4 : P;
       pl.operand[i] = one[i] ? OPND_FIRST : OPND_BOTH;
@@ -94,26 +95,30 @@ inline BlockPlan block_plan(const egv_block_geom& g) {
   pl.lnq_lo = lo && !one[LIN_TQKV];
   pl.ln2_lo = lo && !one[LIN_FC1];
   pl.qkv_lo = lo;
-  pl.attn_lo = lo && pl.attn_fmt != 3;
+  pl.attn_lo = lo && pl.attn_fmt != EGV_ATTN_OUT_F16;
   pl.h_lo = lo && !one[LIN_FC2];
   pl.bf = x2 && pl.train && !h16;
-  pl.qkv_fmt = h16 ? 3 : 0;
-  pl.attn_mode_fwd = (pl.attn_fmt << 1) | (h16 ? 8 : 0);           // 8: the attention multiplies fp16 (qkv planes = an fp16 split)
-  pl.attn_mode_bwd = (pl.attn_fmt << 1) | (h16 ? 8 | 16 : 0);      // 16: dqkv as fp16; q / k / v / dO read as fp16
-  pl.kv_fmt = h16 ? 1 : 0;
-  pl.h_fmt = x2 ? (one[LIN_FC2] ? 2 : 1) : 0;
-  pl.z_code = g.z_bf16 ? (h16 ? 3 : 2) : 0;
+  pl.qkv_fmt = h16 ? EGV_OUT_F16_SPLIT : EGV_OUT_BF16_SPLIT;
+  // the fp16 attention multiplies fp16 (qkv planes = an fp16 split); its backward writes dqkv as fp16 and reads q / k / v / dO as fp16
+  pl.attn_mode_fwd = (pl.attn_fmt << EGV_ATTN_OUT_SHIFT) | (h16 ? EGV_ATTN_FWD_QKV_F16 : 0);
+  pl.attn_mode_bwd = (pl.attn_fmt << EGV_ATTN_OUT_SHIFT) | (h16 ? EGV_ATTN_BWD_GRAD_F16 | EGV_ATTN_BWD_QKV_F16 : 0);
+  pl.kv_fmt = h16 ? EGV_CLS_KV_F16 : EGV_CLS_KV_BF16;
+  pl.h_fmt = x2 ? (one[LIN_FC2] ? EGV_OUT_F16 : EGV_OUT_F16X2) : EGV_OUT_BF16_SPLIT;
+  pl.z_code = g.z_bf16 ? (h16 ? EGV_AUX_DGELU_F16 : EGV_AUX_DGELU_BF16) : EGV_AUX_F32;
   pl.z_bytes = pl.train ? (g.z_bf16 ? 2 : 4) : 0;
   pl.bwd_passes = g.bwd_passes;
   pl.bwd_lo = g.bwd_passes == 3;
   pl.saved_bf = x2 && !h16;
-  pl.grad_fmt = h16 ? 4 : 0;
-  pl.ln_fmt = h16 ? 3 : 0;
+  pl.grad_fmt = h16 ? EGV_OUT_F16_GRAD : EGV_OUT_BF16_SPLIT;
+  pl.ln_fmt = h16 ? EGV_LN_DX_F16 | EGV_LN_DY_F16 : 0;
   pl.attn_bwd_passes = h16 ? 1 : g.bwd_passes;
-  pl.attn_bwd_o_lo = pl.attn_fmt == 0;
-  pl.cls_dx_mode = h16 ? 2 : 1;
+  pl.attn_bwd_o_lo = pl.attn_fmt == EGV_ATTN_OUT_BF16_SPLIT;
+  pl.cls_dx_mode = h16 ? EGV_CLS_DX_ADD_F16 : EGV_CLS_DX_ADD_F32;
   return pl;
 }
+
+// the mode word of one attention branch: the plan's word and the branch bit
+inline int block_attn_mode(int word, int time) { return word | (time ? EGV_ATTN_TIME : 0); }
 
 // ------------------------------------------------------------------------------------------------------------------- geometry
 // tokens, tokens per clip, widths, and (N, K) of W[N,K] in the order of egv_block_params: tqkv, tproj, sqkv, sproj, fc1, fc2

@@ -100,12 +100,12 @@ __global__ __launch_bounds__(256) void cls_linear_dgrad_finish_kernel(const floa
   float v = 0.f;
   for (int s = 0; s < slabs; ++s) v += partial[(long)s * R * K + i];
   if (z) v *= gelu_grad_f(z[i]);
-  if (mode == 2) {
+  if (mode == EGV_CLS_DX_ADD_F16) {
     _Float16* p = (_Float16*)dx + (long)r * lddx + k;
     *p = (_Float16)((float)*p + v);          // un-clamped: a scaled gradient beyond fp16's range becomes inf (a skipped step)
   } else {
     float* p = (float*)dx + (long)r * lddx + k;
-    *p = mode == 1 ? *p + v : v;
+    *p = mode == EGV_CLS_DX_ADD_F32 ? *p + v : v;
   }
 }
 
@@ -322,7 +322,7 @@ extern "C" int64_t egv_cls_linear_work_floats(int32_t R, int32_t N, int32_t K) {
 extern "C" int egv_cls_linear_dgrad(const float* dy, int64_t lddy, const float* W, int64_t ldw, int32_t R, int32_t N, int32_t K, const float* z,
                                     void* dx, int64_t lddx, int32_t dx_mode, float* work, void* stream) {
   if (!dy || !W || !dx || !work || R <= 0 || N <= 0 || K <= 0 || K % 4 || ldw % 4 || ldw < K || lddy < N || lddx < K) return EGV_ERR_ARG;
-  if (dx_mode < 0 || dx_mode > 2 || !aligned16(W) || !aligned16(work)) return EGV_ERR_ARG;
+  if (dx_mode < EGV_CLS_DX_STORE || dx_mode > EGV_CLS_DX_ADD_F16 || !aligned16(W) || !aligned16(work)) return EGV_ERR_ARG;
   const int slabs = (N + DG_NS - 1) / DG_NS;
   const int kz = (K / 4 + 255) / 256;
   EGV_LAUNCH(cls_linear_dgrad_kernel, dim3(slabs, (R + DG_RT - 1) / DG_RT, kz), dim3(256), 0, (hipStream_t)stream, dy, lddy, W, ldw, R, N, K, work);
@@ -356,14 +356,14 @@ extern "C" int egv_cls_rows_add(float* dst, int64_t lddst, const float* src, int
 extern "C" int egv_cls_attn_fwd(const float* q, int64_t ldq, const uint16_t* k_hi, const uint16_t* k_lo, const uint16_t* v_hi,
                                 const uint16_t* v_lo, int64_t ldkv, int32_t kv_fmt, int32_t B, int32_t S, int32_t H, float* out, int64_t ldo,
                                 float* lse, void* stream) {
-  if (!q || !k_hi || !v_hi || !out || !lse || B <= 0 || S <= 0 || H <= 0 || (kv_fmt != 0 && kv_fmt != 1)) return EGV_ERR_ARG;
+  if (!q || !k_hi || !v_hi || !out || !lse || B <= 0 || S <= 0 || H <= 0 || (kv_fmt != EGV_CLS_KV_BF16 && kv_fmt != EGV_CLS_KV_F16)) return EGV_ERR_ARG;
   if (ldkv % 8 || ldkv < (int64_t)H * 64 || ldq < (int64_t)H * 64 || ldo < (int64_t)H * 64 || (k_lo == nullptr) != (v_lo == nullptr))
     return EGV_ERR_ARG;
   if (!aligned16(k_hi) || !aligned16(v_hi) || !aligned16(k_lo) || !aligned16(v_lo)) return EGV_ERR_ARG;
-  if (kv_fmt == 1)
-    EGV_LAUNCH(cls_attn_fwd_kernel<1>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, q, ldq, k_hi, k_lo, v_hi, v_lo, ldkv, S, H, out, ldo, lse);
+  if (kv_fmt == EGV_CLS_KV_F16)
+    EGV_LAUNCH(cls_attn_fwd_kernel<EGV_CLS_KV_F16>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, q, ldq, k_hi, k_lo, v_hi, v_lo, ldkv, S, H, out, ldo, lse);
   else
-    EGV_LAUNCH(cls_attn_fwd_kernel<0>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, q, ldq, k_hi, k_lo, v_hi, v_lo, ldkv, S, H, out, ldo, lse);
+    EGV_LAUNCH(cls_attn_fwd_kernel<EGV_CLS_KV_BF16>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, q, ldq, k_hi, k_lo, v_hi, v_lo, ldkv, S, H, out, ldo, lse);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }
@@ -373,7 +373,8 @@ extern "C" int egv_cls_attn_bwd(const float* q, int64_t ldq, const uint16_t* k_h
                                 int32_t B, int32_t S, int32_t H, float* dq, uint16_t* dk_hi, uint16_t* dk_lo, uint16_t* dv_hi, uint16_t* dv_lo,
                                 int64_t lddkv, int32_t d_fmt, void* stream) {
   if (!q || !k_hi || !v_hi || !out || !d_out || !lse || !dq || !dk_hi || !dv_hi || B <= 0 || S <= 0 || H <= 0) return EGV_ERR_ARG;
-  if ((kv_fmt != 0 && kv_fmt != 1) || (d_fmt != 0 && d_fmt != 1) || (d_fmt == 1 && (dk_lo || dv_lo))) return EGV_ERR_ARG;
+  if ((kv_fmt != EGV_CLS_KV_BF16 && kv_fmt != EGV_CLS_KV_F16) || (d_fmt != EGV_CLS_KV_BF16 && d_fmt != EGV_CLS_KV_F16) || (d_fmt == EGV_CLS_KV_F16 && (dk_lo || dv_lo)))
+    return EGV_ERR_ARG;
   if (ldkv % 8 || lddkv % 8 || ldkv < (int64_t)H * 64 || lddkv < (int64_t)H * 64 || ldq < (int64_t)H * 64) return EGV_ERR_ARG;
   if ((k_lo == nullptr) != (v_lo == nullptr) || (dk_lo == nullptr) != (dv_lo == nullptr)) return EGV_ERR_ARG;
   if (!aligned16(k_hi) || !aligned16(v_hi) || !aligned16(k_lo) || !aligned16(v_lo) || !aligned16(dk_hi) || !aligned16(dv_hi) || !aligned16(dk_lo) ||
@@ -383,10 +384,10 @@ extern "C" int egv_cls_attn_bwd(const float* q, int64_t ldq, const uint16_t* k_h
 #define EGV_CLS_BWD(F, DF)                                                                                                              \
   EGV_LAUNCH((cls_attn_bwd_kernel<F, DF>), dim3(B * H), dim3(256), 0, s, q, ldq, k_hi, k_lo, v_hi, v_lo, ldkv, out, d_out, lse, S, H, dq, dk_hi, \
              dk_lo, dv_hi, dv_lo, lddkv)
-  if (kv_fmt == 1 && d_fmt == 1) EGV_CLS_BWD(1, 1);
-  else if (kv_fmt == 1) EGV_CLS_BWD(1, 0);
-  else if (d_fmt == 1) EGV_CLS_BWD(0, 1);
-  else EGV_CLS_BWD(0, 0);
+  if (kv_fmt == EGV_CLS_KV_F16 && d_fmt == EGV_CLS_KV_F16) EGV_CLS_BWD(EGV_CLS_KV_F16, EGV_CLS_KV_F16);
+  else if (kv_fmt == EGV_CLS_KV_F16) EGV_CLS_BWD(EGV_CLS_KV_F16, EGV_CLS_KV_BF16);
+  else if (d_fmt == EGV_CLS_KV_F16) EGV_CLS_BWD(EGV_CLS_KV_BF16, EGV_CLS_KV_F16);
+  else EGV_CLS_BWD(EGV_CLS_KV_BF16, EGV_CLS_KV_BF16);
 #undef EGV_CLS_BWD
   EGV_CHECK_LAUNCH();
   return EGV_OK;

@@ -22,7 +22,7 @@ __device__ __forceinline__ void encode_piece(const float* __restrict__ x, long l
   if (bf) *(u32x4_t*)(bf + (long)r * ldo + c) = bf16_piece8(v);
 }
 
-// fp32 [rows, cols] -> ONE plane of plain fp16, NOT saturating (role 2: a scaled gradient handed to the fp16 backward as fp32 --
+// fp32 [rows, cols] -> ONE plane of plain fp16, NOT saturating (EGV_F16X2_GRAD_CAST: a scaled gradient handed to the fp16 backward as fp32 --
 // the loss gradient arriving at the last block, or a block input gradient whose plane hand-over was dropped)
 __global__ __launch_bounds__(256) void f16_cast_kernel(const float* __restrict__ x, long ldx, int rows, int cols,
                                                        unsigned short* __restrict__ p1, long ldo) {
@@ -135,16 +135,17 @@ __global__ __launch_bounds__(256) void layernorm_fwd_f16x2_kernel(
 
 extern "C" int egv_f16x2_encode(const float* x, int64_t ldx, int32_t rows, int32_t cols, uint16_t* p1, uint16_t* p2, egv_bf16* bf,
                                 int64_t ldo, int32_t role, void* stream) {
-  if (!x || !p1 || (!p2 && role != 2) || rows <= 0 || cols <= 0 || cols % 8 != 0 || ldo % 8 != 0 || ldx % 4 != 0 || role < 0 || role > 2)
+  if (!x || !p1 || (!p2 && role != EGV_F16X2_GRAD_CAST) || rows <= 0 || cols <= 0 || cols % 8 != 0 || ldo % 8 != 0 || ldx % 4 != 0 ||
+      role < EGV_F16X2_FIRST || role > EGV_F16X2_GRAD_CAST)
     return EGV_ERR_ARG;
   const long pieces = (long)rows * (cols >> 3);
   const dim3 grid((unsigned)((pieces + 255) / 256));
-  if (role == 2)
+  if (role == EGV_F16X2_GRAD_CAST)
     EGV_LAUNCH(f16_cast_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, cols, p1, (long)ldo);
-  else if (role == 0)
-    EGV_LAUNCH(f16x2_encode_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, cols, p1, p2, bf, (long)ldo);
+  else if (role == EGV_F16X2_FIRST)
+    EGV_LAUNCH(f16x2_encode_kernel<EGV_F16X2_FIRST>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, cols, p1, p2, bf, (long)ldo);
   else
-    EGV_LAUNCH(f16x2_encode_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, cols, p1, p2, bf, (long)ldo);
+    EGV_LAUNCH(f16x2_encode_kernel<EGV_F16X2_SECOND>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, cols, p1, p2, bf, (long)ldo);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }
@@ -152,7 +153,7 @@ extern "C" int egv_f16x2_encode(const float* x, int64_t ldx, int32_t rows, int32
 extern "C" int egv_f16x2_encode_multi(int32_t count, const float* const* x, const int64_t* ldx, const int32_t* rows,
                                       const int32_t* cols, uint16_t* const* p1, uint16_t* const* p2, const int64_t* ldo, int32_t role,
                                       void* stream) {
-  if (count < 0 || !x || !ldx || !rows || !cols || !p1 || !p2 || !ldo || (role != 0 && role != 1)) return EGV_ERR_ARG;
+  if (count < 0 || !x || !ldx || !rows || !cols || !p1 || !p2 || !ldo || (role != EGV_F16X2_FIRST && role != EGV_F16X2_SECOND)) return EGV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   return mt_for_each_launch<EncodeTable>(
       count,
@@ -167,8 +168,8 @@ extern "C" int egv_f16x2_encode_multi(int32_t count, const float* const* x, cons
         t.ldx[k] = (int)ldx[i]; t.ldo[k] = (int)ldo[i]; t.rows[k] = rows[i]; t.cols[k] = cols[i];
       },
       [&](const EncodeTable& t, int nb) -> int {
-        if (role == 0) EGV_LAUNCH(f16x2_encode_multi_kernel<0>, dim3(nb), dim3(256), 0, s, t);
-        else EGV_LAUNCH(f16x2_encode_multi_kernel<1>, dim3(nb), dim3(256), 0, s, t);
+        if (role == EGV_F16X2_FIRST) EGV_LAUNCH(f16x2_encode_multi_kernel<EGV_F16X2_FIRST>, dim3(nb), dim3(256), 0, s, t);
+        else EGV_LAUNCH(f16x2_encode_multi_kernel<EGV_F16X2_SECOND>, dim3(nb), dim3(256), 0, s, t);
         EGV_CHECK_LAUNCH();
         return EGV_OK;
       });

@@ -148,23 +148,23 @@ __device__ __forceinline__ void epilogue4(const egv_gemm_desc& p, f32x4_t v, int
   if (EPI == EPI_GENERIC && p.alpha != 1.0f) v *= p.alpha;
   if (EPI != EPI_GELU_BWD && p.bias) v += *(const f32x4_t*)(p.bias + n);
   if (EPI == EPI_GELU || (EPI == EPI_GENERIC && p.act == EGV_ACT_GELU)) {
-    f32x4_t s = v;                    // what is saved for backward: the pre-activation, or (aux_bf16 == 2) gelu'(it)
+    f32x4_t s = v;                    // what is saved for backward: the pre-activation, or (EGV_AUX_DGELU_BF16) gelu'(it)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float cdf, pdf;
       gelu_parts(v[e], cdf, pdf);
-      if (p.aux_bf16 == 2) s[e] = cdf + v[e] * pdf;
+      if (p.aux_bf16 == EGV_AUX_DGELU_BF16) s[e] = cdf + v[e] * pdf;
       v[e] *= cdf;
     }
     if (p.aux_out) {
-      if (p.aux_bf16)
+      if (p.aux_bf16 != EGV_AUX_F32)
         *(u32x2_t*)((bf16_t*)p.aux_out + (long)m * p.ldaux + n) = (u32x2_t){f32x2_to_bf16x2(s[0], s[1]), f32x2_to_bf16x2(s[2], s[3])};
       else
         *(f32x4_t*)(p.aux_out + (long)m * p.ldaux + n) = s;
     }
   } else if (EPI == EPI_GELU_BWD || (EPI == EPI_GENERIC && p.act == EGV_ACT_GELU_BWD)) {
     f32x4_t zv;
-    if (p.aux_bf16) {
+    if (p.aux_bf16 != EGV_AUX_F32) {
       const u32x2_t zb = *(const u32x2_t*)((const bf16_t*)p.aux_in + (long)m * p.ldaux + n);
       zv = (f32x4_t){__uint_as_float(zb[0] << 16), __uint_as_float(zb[0] & 0xffff0000u), __uint_as_float(zb[1] << 16),
                      __uint_as_float(zb[1] & 0xffff0000u)};
@@ -172,7 +172,7 @@ __device__ __forceinline__ void epilogue4(const egv_gemm_desc& p, f32x4_t v, int
       zv = *(const f32x4_t*)(p.aux_in + (long)m * p.ldaux + n);
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] *= (p.aux_bf16 == 2) ? zv[e] : gelu_grad_f(zv[e]);
+    for (int e = 0; e < 4; ++e) v[e] *= (p.aux_bf16 == EGV_AUX_DGELU_BF16) ? zv[e] : gelu_grad_f(zv[e]);
   } else if (EPI == EPI_GENERIC && p.act == EGV_ACT_RELU_BWD) {
     const f32x4_t zv = *(const f32x4_t*)(p.aux_in + (long)m * p.ldaux + n);
 #pragma unroll
@@ -952,7 +952,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const egv_gemm_desc p,
     // fc2 dgrad) are loaded a whole 16-row group at a time, at the top of the group: within the group no load is issued
     // behind a store, so the only store round trip a wave waits for is the previous group's (MF per tile, not 8 MF).
     const bool pf_res = (EPI == EPI_LINEAR) && !lay16 && p.residual != nullptr;
-    const bool pf_aux = (EPI == EPI_GELU_BWD) && lay16 && p.aux_bf16 != 0 && p.aux_in != nullptr;
+    const bool pf_aux = (EPI == EPI_GELU_BWD) && lay16 && p.aux_bf16 != EGV_AUX_F32 && p.aux_in != nullptr;
     constexpr int NPF = (EPI == EPI_LINEAR) ? 8 : ((EPI == EPI_GELU_BWD) ? 4 : 1);
     f32x4_t pre[NPF];
     const float* pf_ptr = nullptr;       // this lane's address in the first row of the group to be fetched next
@@ -1047,7 +1047,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const egv_gemm_desc p,
       // ---------------- plane layout: lane -> 8 columns (16 B of every bf16 plane), four 256-B rows per instruction ----------------
       const int n = nw + 8 * L16;
       const bool fast = (EPI == EPI_LINEAR && !p.residual && !p.out_f32) ||
-                        (IS_GELU && !p.residual && !p.out_f32 && (!p.aux_out || p.aux_bf16)) ||
+                        (IS_GELU && !p.residual && !p.out_f32 && (!p.aux_out || p.aux_bf16 != EGV_AUX_F32)) ||
                         (EPI == EPI_GELU_BWD && pf_aux && !p.residual && !p.out_f32);
       if ((EPI == EPI_LINEAR || IS_GELU || EPI == EPI_GELU_BWD) && fast) {
         f32x4_t b0 = (f32x4_t){0.f, 0.f, 0.f, 0.f}, b1 = b0;
@@ -1075,18 +1075,18 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const egv_gemm_desc p,
           if (sink_stores) asm volatile("" ::"v"(v));
           else egv_store16<decltype(site)::value>(ptr, v);
         };
-        const bool saved_grad = p.aux_bf16 >= 2;
-        const bool aux_f16 = (H1 || X2) && p.aux_bf16 == 3;       // the saved gelu' as fp16 (the fp16 backward: bf16's 2^-9 would cap dZ's accuracy)
-        // fp16 plane outputs of the plain epilogues (out_fmt 4: ONE plane of un-clamped fp16 -- a scaled gradient: dZ, the dO of the
-        // attention backward; out_fmt 3: an fp16 split (hi, lo) -- the qkv planes of the fp16 attention)
-        const bool grad_f16 = H1 && (EPI == EPI_GELU_BWD || EPI == EPI_LINEAR) && p.out_fmt == 4;
-        const bool split_f16 = (H1 || X2) && EPI == EPI_LINEAR && p.out_fmt == 3;
+        const bool saved_grad = p.aux_bf16 >= EGV_AUX_DGELU_BF16;      // either width of the derivative
+        const bool aux_f16 = (H1 || X2) && p.aux_bf16 == EGV_AUX_DGELU_F16;       // the saved gelu' as fp16 (the fp16 backward: bf16's 2^-9 would cap dZ's accuracy)
+        // fp16 plane outputs of the plain epilogues (EGV_OUT_F16_GRAD: ONE plane of un-clamped fp16 -- a scaled gradient: dZ, the dO of the
+        // attention backward; EGV_OUT_F16_SPLIT: an fp16 split (hi, lo) -- the qkv planes of the fp16 attention)
+        const bool grad_f16 = H1 && (EPI == EPI_GELU_BWD || EPI == EPI_LINEAR) && p.out_fmt == EGV_OUT_F16_GRAD;
+        const bool split_f16 = (H1 || X2) && EPI == EPI_LINEAR && p.out_fmt == EGV_OUT_F16_SPLIT;
         auto row16 = [&](const int it, const f32x4_t zin) {
           const unsigned a0 = (r16 + it * 2048) ^ ((it & 1) << 6);
           f32x4_t v0 = *(const f32x4_t*)(smem + a0) + b0, v1 = *(const f32x4_t*)(smem + (a0 ^ 16u)) + b1;
           if constexpr (IS_GELU) {
             // one evaluation of (Phi, phi) gives both the activation and -- saved in place of the pre-activation when the
-            // caller asks for it (aux_bf16 == 2) -- its derivative, so that the fc2-dgrad epilogue is a plain multiply
+            // caller asks for it (EGV_AUX_DGELU_*) -- its derivative, so that the fc2-dgrad epilogue is a plain multiply
             f32x4_t s0 = v0, s1 = v1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1141,7 +1141,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const egv_gemm_desc p,
           if constexpr (EPI == EPI_GELU_X2) {
             // the activation in the f16x2 operand format (first-operand role): two fp16 planes [+ the bf16 copy]
             const float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            if (p.out_fmt == 2) {       // ONE plane of plain fp16: the consumer runs a single fp16 product
+            if (p.out_fmt == EGV_OUT_F16) {       // ONE plane of plain fp16: the consumer runs a single fp16 product
               st16(std::integral_constant<int, PSITE>{}, dh, f16_piece8(vv));
             } else {
               u32x4_t o1, o2;

@@ -27,8 +27,8 @@ enum { EPI_RAW = 0,      // store the accumulators (split-K partial slab, or pla
        EPI_GELU = 2,     // + bias, pre-activation -> aux_out, gelu -> fp32 and/or planes
        EPI_GELU_BWD = 3, // * gelu'(aux_in) -> fp32 and/or planes
        EPI_GENERIC = 4,  // everything at run time (alpha, ReLU', ...)
-       EPI_GELU_X2 = 5 };// EPI_GELU with the activation written as fp16 operand planes -- out_fmt 1: the f16x2 format (csrc/f16x2.h,
-                         // first-operand role, two planes); out_fmt 2: ONE plane of plain fp16 (the consumer runs a single fp16 product)
+       EPI_GELU_X2 = 5 };// EPI_GELU with the activation written as fp16 operand planes -- EGV_OUT_F16X2: the f16x2 format (csrc/f16x2.h,
+                         // first-operand role, two planes); EGV_OUT_F16: ONE plane of plain fp16 (the consumer runs a single fp16 product)
                          // -- [+ bf16 plane for the backward], the saved gelu' as bf16: fc1 forward of the f16x2 mode
 
 // What follows a split-K launch.  GEMM_RED_NONE      un-split
@@ -93,17 +93,17 @@ inline int gemm_check(const egv_gemm_desc& p, int x2_seg) {
   if ((p.passes == 2 || p.passes == 3) && (!p.a_lo || !p.b_lo)) return EGV_ERR_ARG;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 4 != 0 || p.lda % 8 != 0 || p.ldb % 8 != 0 || (!p.trans && p.K % 32 != 0))
     return EGV_ERR_ARG;                                                    // (TN: any K, rows past it come from a zero page)
-  if (p.out_fmt < 0 || p.out_fmt > 4 || p.aux_bf16 < 0 || p.aux_bf16 > 3) return EGV_ERR_ARG;
+  if (p.out_fmt < EGV_OUT_BF16_SPLIT || p.out_fmt > EGV_OUT_F16_GRAD || p.aux_bf16 < EGV_AUX_F32 || p.aux_bf16 > EGV_AUX_DGELU_F16) return EGV_ERR_ARG;
   if (p.grid_cap != 0 && (p.grid_cap < 8 || p.grid_cap > GEMM_BIG_WGS || p.grid_cap % 8 != 0)) return EGV_ERR_ARG;
   if ((ks > 1 && !p.partial) || (p.colsum && !p.trans)) return EGV_ERR_ARG;
   if ((p.act == EGV_ACT_GELU_BWD || p.act == EGV_ACT_RELU_BWD) && !p.aux_in) return EGV_ERR_ARG;        // (the epilogues read it unasked)
   const int family = gemm_family(p);
   if (family < 0) return EGV_ERR_ARG;
   // what only the big kernel, and only its fp16 products, can do
-  if (p.aux_bf16 && (family != GEMM_BIG || p.act == EGV_ACT_RELU_BWD)) return EGV_ERR_ARG;   // 16-bit aux: the GELU epilogues
-  if ((p.aux_bf16 == 3 || p.out_fmt != 0) && !fp16) return EGV_ERR_ARG;                        // fp16 gelu', fp16 plane outputs
+  if (p.aux_bf16 != EGV_AUX_F32 && (family != GEMM_BIG || p.act == EGV_ACT_RELU_BWD)) return EGV_ERR_ARG;   // 16-bit aux: the GELU epilogues
+  if ((p.aux_bf16 == EGV_AUX_DGELU_F16 || p.out_fmt != EGV_OUT_BF16_SPLIT) && !fp16) return EGV_ERR_ARG;                        // fp16 gelu', fp16 plane outputs
   // ... and fp16 gelu' is known to the plane epilogue alone (planes and nothing else): the rolled one takes every 16-bit aux for bf16
-  if (p.aux_bf16 == 3 && (p.act == EGV_ACT_GELU || p.act == EGV_ACT_GELU_BWD) && (!p.out_hi || p.residual || p.out_f32)) return EGV_ERR_ARG;
+  if (p.aux_bf16 == EGV_AUX_DGELU_F16 && (p.act == EGV_ACT_GELU || p.act == EGV_ACT_GELU_BWD) && (!p.out_hi || p.residual || p.out_f32)) return EGV_ERR_ARG;
   // The big kernel computes the columns its shifted last tile shares with the tile before it twice and stores both results.  Its plane
   // epilogue gives a lane 8 consecutive columns, so with N % 8 != 0 an element sits in the other half of a lane's piece the second time.
   // The linear epilogues are the same fp32 additions there; the erf ones are not bit for bit (read from the ISA of
@@ -113,7 +113,7 @@ inline int gemm_check(const egv_gemm_desc& p, int x2_seg) {
   // plane cannot pair, but which of two results it holds would still depend on the order of two workgroups: refused alike.
   if (family == GEMM_BIG && p.out_hi && p.N % 8 != 0 && (p.act == EGV_ACT_GELU || p.act == EGV_ACT_GELU_BWD)) return EGV_ERR_ARG;
   // fp16 operands / outputs (csrc/f16x2.h): NT un-split, or (passes 4) the TN weight gradient of the fp16 backward with its k-slices
-  if (fp16 && (p.trans ? p.passes == 2 || p.out_fmt != 0 : ks > 1)) return EGV_ERR_ARG;
+  if (fp16 && (p.trans ? p.passes == 2 || p.out_fmt != EGV_OUT_BF16_SPLIT : ks > 1)) return EGV_ERR_ARG;
   if (p.trans && p.alpha != 1.0f && !(p.alpha > 0.f)) return EGV_ERR_ARG;                      // (a NaN is refused)
   if (fp16 && !p.trans) {
     // the epilogues the fp16 instances have.  One product (also the two k-segments of f16x2) -- forward: fc2 / proj (bias + residual
@@ -121,19 +121,19 @@ inline int gemm_check(const egv_gemm_desc& p, int x2_seg) {
     // GELU' epilogue).  Fused f16x2: forward products only.
     const int prod = gemm_prod(p, x2_seg, 1);
     if (p.alpha != 1.0f) return EGV_ERR_ARG;
-    if (prod == 1 ? !(p.act == EGV_ACT_NONE || (p.act == EGV_ACT_GELU && p.out_fmt != 0) || (p.act == EGV_ACT_GELU_BWD && !p.bias))
+    if (prod == 1 ? !(p.act == EGV_ACT_NONE || (p.act == EGV_ACT_GELU && p.out_fmt != EGV_OUT_BF16_SPLIT) || (p.act == EGV_ACT_GELU_BWD && !p.bias))
                   : !(p.act == EGV_ACT_NONE || p.act == EGV_ACT_GELU))
       return EGV_ERR_ARG;
-    if (p.out_fmt != 0) {
-      // fp16 plane outputs, planes only: the GELU epilogue (h for fc2: 1 = f16x2, two planes; 2 = one plain plane); the plain
-      // epilogue as an fp16 split (3: the qkv planes of the fp16 attention); and -- one fp16 product only -- un-clamped gradient
-      // planes (4): dZ from the GELU' epilogue, dO from a plain dgrad
-      const bool gelu_fwd = p.act == EGV_ACT_GELU && (p.out_fmt == 1 || p.out_fmt == 2);
-      const bool gelu_bwd16 = prod == 1 && p.act == EGV_ACT_GELU_BWD && p.out_fmt == 4 && p.aux_in && p.aux_bf16 >= 2;
-      const bool lin_split = p.act == EGV_ACT_NONE && p.out_fmt == 3 && p.out_lo;
-      const bool lin_grad = prod == 1 && p.act == EGV_ACT_NONE && p.out_fmt == 4 && !p.bias;
-      if (!(gelu_fwd || gelu_bwd16 || lin_split || lin_grad) || !p.out_hi || (p.out_fmt == 1 && !p.out_lo) || p.residual || p.out_f32 ||
-          (p.aux_out && !p.aux_bf16) || p.ldoh % 8 != 0)
+    if (p.out_fmt != EGV_OUT_BF16_SPLIT) {
+      // fp16 plane outputs, planes only: the GELU epilogue (h for fc2: the f16x2 format, two planes, or one plain plane); the plain
+      // epilogue as an fp16 split (the qkv planes of the fp16 attention); and -- one fp16 product only -- un-clamped gradient
+      // planes: dZ from the GELU' epilogue on a saved derivative, dO from a plain dgrad
+      const bool gelu_fwd = p.act == EGV_ACT_GELU && (p.out_fmt == EGV_OUT_F16X2 || p.out_fmt == EGV_OUT_F16);
+      const bool gelu_bwd16 = prod == 1 && p.act == EGV_ACT_GELU_BWD && p.out_fmt == EGV_OUT_F16_GRAD && p.aux_in && p.aux_bf16 >= EGV_AUX_DGELU_BF16;
+      const bool lin_split = p.act == EGV_ACT_NONE && p.out_fmt == EGV_OUT_F16_SPLIT && p.out_lo;
+      const bool lin_grad = prod == 1 && p.act == EGV_ACT_NONE && p.out_fmt == EGV_OUT_F16_GRAD && !p.bias;
+      if (!(gelu_fwd || gelu_bwd16 || lin_split || lin_grad) || !p.out_hi || (p.out_fmt == EGV_OUT_F16X2 && !p.out_lo) || p.residual ||
+          p.out_f32 || (p.aux_out && p.aux_bf16 == EGV_AUX_F32) || p.ldoh % 8 != 0)
         return EGV_ERR_ARG;
     }
   }
@@ -201,7 +201,7 @@ inline GemmPick gemm_pick(const egv_gemm_desc& p, int x2_seg, int f3) {
     g.mf = gemm_pick_mf(p); g.tn = p.trans != 0; g.prod = gemm_prod(p, x2_seg, f3);
     if (p.trans || ks > 1) g.epi = EPI_RAW;                        // wgrad / split-K slab: plain fp32, no epilogue
     else if (p.alpha == 1.0f && p.act == EGV_ACT_NONE) g.epi = nothing_fused && p.out_f32 ? EPI_RAW : EPI_LINEAR;
-    else if (p.alpha == 1.0f && p.act == EGV_ACT_GELU) g.epi = p.out_fmt != 0 ? EPI_GELU_X2 : EPI_GELU;
+    else if (p.alpha == 1.0f && p.act == EGV_ACT_GELU) g.epi = p.out_fmt != EGV_OUT_BF16_SPLIT ? EPI_GELU_X2 : EPI_GELU;
     else if (p.alpha == 1.0f && p.act == EGV_ACT_GELU_BWD && !p.bias) g.epi = EPI_GELU_BWD;
     else g.epi = EPI_GENERIC;
     // the two multi-round forward shapes of the step (qkv: plane outputs; fc1: GELU + planes + saved gelu') with mixed row bands

@@ -12,6 +12,7 @@ from collections import namedtuple
 import torch
 
 from .. import _lib, ops
+from .._lib import EGV as E
 from ..ops import ExecContext, Planes
 
 
@@ -129,22 +130,26 @@ A1_INV = 1.0 / (1.0 - 2.0 ** -6)          # csrc/f16x2.h: a1 = fp16((1 - 2^-6) x
 def block_plan(P, Pb, single, train, z_bf16=False):
     """csrc/block_plan.h::block_plan for an accepted (fwd_passes, bwd_passes, f16_single, egv_block_geom.train, z_bf16)."""
     x2, h16, lo = P == 2, Pb == 4, P != 1
-    one = tuple(bool(single & b) for b in (4, 8, 4, 8, 1, 2))
-    keep, tail = bool(train & 1), bool(train & 2)
+    one = tuple(bool(single & b) for b in (E.SINGLE_QKV, E.SINGLE_PROJ, E.SINGLE_QKV, E.SINGLE_PROJ, E.SINGLE_FC1, E.SINGLE_FC2))
+    keep, tail = bool(train & E.TRAIN_KEEP), bool(train & E.TRAIN_CLS_TAIL)
     attn_passes = 3 if x2 else P
-    attn_fmt = (2 if h16 else 0) | (1 if one[1] else 0)
+    attn_fmt = (E.ATTN_OUT_F16 if one[1] else E.ATTN_OUT_F16X2) if h16 else (E.ATTN_OUT_BF16_F16 if one[1] else E.ATTN_OUT_BF16_SPLIT)
     # (passes, operand, w_fmt) per Linear; the proj Linears by attention format
-    proj = ((attn_passes, 0), (4, 2), (2, 0), (4, 1))[attn_fmt] + (int(attn_fmt != 0),)
+    proj = {E.ATTN_OUT_BF16_SPLIT: (attn_passes, 0, 0), E.ATTN_OUT_BF16_F16: (4, 2, 1), E.ATTN_OUT_F16X2: (2, 0, 1), E.ATTN_OUT_F16: (4, 1, 1)}[attn_fmt]
     passes, operand, w_fmt = zip(*(proj if i in (1, 3) else (4 if one[i] else P, int(one[i]), int(x2)) for i in range(6)))
+    attn_mode = attn_fmt << E.ATTN_OUT_SHIFT
     return BlockPlan(
         train=keep, tail=tail, passes=passes, operand=operand, w_fmt=w_fmt,
         walpha=tuple(A1_INV if h16 and not one[i] else 1.0 for i in range(6)),
-        w_lo=lo, ln_f16=x2, lnq_lo=lo and not one[0], ln2_lo=lo and not one[4], qkv_lo=lo, attn_lo=lo and attn_fmt != 3,
-        h_lo=lo and not one[5], bf=x2 and keep and not h16, qkv_fmt=3 if h16 else 0, attn_passes=attn_passes, attn_fmt=attn_fmt,
-        attn_mode_fwd=(attn_fmt << 1) | (8 if h16 else 0), attn_mode_bwd=(attn_fmt << 1) | (24 if h16 else 0), kv_fmt=int(h16),
-        h_fmt=(2 if one[5] else 1) if x2 else 0, z_code=(3 if h16 else 2) if z_bf16 else 0, z_bytes=(2 if z_bf16 else 4) if keep else 0,
-        bwd_passes=Pb, bwd_lo=Pb == 3, saved_bf=x2 and not h16, grad_fmt=4 if h16 else 0, ln_fmt=3 if h16 else 0,
-        attn_bwd_passes=1 if h16 else Pb, attn_bwd_o_lo=attn_fmt == 0, cls_dx_mode=2 if h16 else 1)
+        w_lo=lo, ln_f16=x2, lnq_lo=lo and not one[0], ln2_lo=lo and not one[4], qkv_lo=lo, attn_lo=lo and attn_fmt != E.ATTN_OUT_F16,
+        h_lo=lo and not one[5], bf=x2 and keep and not h16, qkv_fmt=E.OUT_F16_SPLIT if h16 else E.OUT_BF16_SPLIT, attn_passes=attn_passes,
+        attn_fmt=attn_fmt, attn_mode_fwd=attn_mode | (E.ATTN_FWD_QKV_F16 if h16 else 0),
+        attn_mode_bwd=attn_mode | (E.ATTN_BWD_GRAD_F16 | E.ATTN_BWD_QKV_F16 if h16 else 0), kv_fmt=E.CLS_KV_F16 if h16 else E.CLS_KV_BF16,
+        h_fmt=(E.OUT_F16 if one[5] else E.OUT_F16X2) if x2 else E.OUT_BF16_SPLIT,
+        z_code=(E.AUX_DGELU_F16 if h16 else E.AUX_DGELU_BF16) if z_bf16 else E.AUX_F32, z_bytes=(2 if z_bf16 else 4) if keep else 0,
+        bwd_passes=Pb, bwd_lo=Pb == 3, saved_bf=x2 and not h16, grad_fmt=E.OUT_F16_GRAD if h16 else E.OUT_BF16_SPLIT,
+        ln_fmt=E.LN_DX_F16 | E.LN_DY_F16 if h16 else 0, attn_bwd_passes=1 if h16 else Pb, attn_bwd_o_lo=attn_fmt == E.ATTN_OUT_BF16_SPLIT,
+        cls_dx_mode=E.CLS_DX_ADD_F16 if h16 else E.CLS_DX_ADD_F32)
 
 
 # ---------------------------------------------------------------------------------------------- one C call per layer

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from .. import _lib, ops
-from .._lib import BlockBwdIO, BlockGeom, BlockParams
+from .._lib import EGV, BlockBwdIO, BlockGeom, BlockParams
 from ..ops import ACT_GELU, ACT_GELU_BWD, ExecContext
 from .layer_common import (PLANE_HANDOFF, _attach_grad_planes, _lin_bwd, _take_grad_planes, bwd_arena_bytes,  # noqa: F401  (PLANE_HANDOFF: tests)
                            block_plan, gelu_grad_16bit, grad_views, layer_sizes, need_fwd_arena, param_struct)
@@ -116,9 +116,9 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         # anyway, gelu'(z) itself as bf16 -- the epilogue has Phi(z) and phi(z) in registers, the buffer is half the bytes,
         # and the fc2-dgrad epilogue becomes one multiply instead of a second erf evaluation over 77 M elements
         # (the fp16 backward keeps gelu' as fp16: bf16's 2^-9 on the derivative would cap dZ's accuracy)
-        z_dtype = {0: torch.float32, 2: torch.bfloat16, 3: torch.float16}[pl.z_code]
+        z_dtype = {EGV.AUX_F32: torch.float32, EGV.AUX_DGELU_BF16: torch.bfloat16, EGV.AUX_DGELU_F16: torch.float16}[pl.z_code]
         z = torch.empty((M, Hd), dtype=z_dtype, device=dev) if train else None
-        lin(4, n2, fc1_w, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h, aux_is_grad=z is not None and pl.z_code != 0)
+        lin(4, n2, fc1_w, bias=fc1_b, act=ACT_GELU, aux_out=z, out_planes=h, aux_is_grad=z is not None and pl.z_code != EGV.AUX_F32)
         out = torch.empty((M, D), dtype=torch.float32, device=dev)
         lin(5, h, fc2_w, bias=fc2_b, residual=None if dp else sr, out_f32=out)
         if dp:      # out = sr + s2[b] * mlp(..)
@@ -168,7 +168,7 @@ class _SpaceTimeBlockFn(torch.autograd.Function):
         ops.gemm_nt(G_pl, Wt(fc2_w), passes=Pb, act=ACT_GELU_BWD, aux_in=z, out_planes=dZ, K=D,
                     aux_is_grad=z.dtype != torch.float32, ec=ec)
         _, d_fc2_w, d_fc2_b = _lin_bwd(G_pl, h, None, Pb, need_dx=False, params=(fc2_w,), ec=ec)
-        ln16 = pl.grad_fmt != 0          # fp16 backward: the dgrads in front of a LayerNorm backward hand it ONE plane of un-clamped fp16 (no fp32 copy)
+        ln16 = pl.grad_fmt == EGV.OUT_F16_GRAD          # fp16 backward: the dgrads in front of a LayerNorm backward hand it ONE plane of un-clamped fp16 (no fp32 copy)
         d_n2, d_fc1_w, d_fc1_b = _lin_bwd(dZ, n2, Wt(fc1_w), Pb, dx_planes=ln16, params=(fc1_w,), ec=ec)
         # d_sr = G + LN2'(d_n2)
         if dp:      # the space branch's gradient is s1[b] * d_sr, formatted from the fp32 d_sr
@@ -215,8 +215,8 @@ def block_calls_ok(ec: ExecContext, M, D, Hd, drop_path=False):
 
 
 def _block_geom(B, T, n, H, D, Hd, P, Pb, train, z_bf16, single, eps, grid, tail=False):
-    # egv_block_geom.train: bit 0 = keep what the backward needs, bit 1 = CLS tail (only the B CLS rows of the output are wanted)
-    return BlockGeom(B, T, n, H, D, Hd, P, Pb, int(train) | (2 if tail else 0), int(z_bf16), float(eps), int(grid), int(single))
+    # egv_block_geom.train: keep what the backward needs; CLS tail (only the B CLS rows of the output are wanted)
+    return BlockGeom(B, T, n, H, D, Hd, P, Pb, (EGV.TRAIN_KEEP if train else 0) | (EGV.TRAIN_CLS_TAIL if tail else 0), int(z_bf16), float(eps), int(grid), int(single))
 
 
 def cls_tail_ok(ec: ExecContext, M, D):
@@ -333,7 +333,7 @@ class _SpaceTimeBlockCFn(torch.autograd.Function):
         _, goff, gtot = ctx.sizes
         grads = torch.empty(gtot, dtype=torch.float32, device=dev)
         d_x = torch.empty((M, D), dtype=torch.float32, device=dev)
-        dx_pl = ops.empty_planes_f16x2(M, D, dev, single=True) if pl.grad_fmt else ops.empty_planes(M, D, Pb, dev)
+        dx_pl = ops.empty_planes_f16x2(M, D, dev, single=True) if pl.grad_fmt == EGV.OUT_F16_GRAD else ops.empty_planes(M, D, Pb, dev)
         used = {s_ for s_ in streams if s_ is not None}          # the side streams read / write these allocations of the main stream
         if used:
             # held until the side streams are joined (end of backward) instead of record_stream-ed: the multi-GB arenas (see

@@ -21,9 +21,9 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import GemmDesc, check
+from ._lib import EGV, GemmDesc, check
 
-ACT_NONE, ACT_GELU, ACT_GELU_BWD, ACT_RELU_BWD = 0, 1, 2, 3
+ACT_NONE, ACT_GELU, ACT_GELU_BWD, ACT_RELU_BWD = EGV.ACT_NONE, EGV.ACT_GELU, EGV.ACT_GELU_BWD, EGV.ACT_RELU_BWD
 
 
 # ---------------------------------------------------------------------------------------------- execution context
@@ -55,7 +55,7 @@ _ENV_F16_SINGLE = os.environ.get("EGV_F16_SINGLE", "auto")     # read once: late
 # fp32 with the bf16 backward (profiles/r05_backward_fp16_table.txt priced this).  Everything outside the video blocks (text tower, patch
 # embedding, heads: 2 % of the FLOPs) then runs its backward on three bf16 products (`bwd_passes_split`).
 _PASSES = {"bf16x3": 3, "bf16": 1, "f16x2": 2, "f16": 4}
-F16_SINGLE_BITS = {"fc1": 1, "fc2": 2, "qkv": 4, "proj": 8}
+F16_SINGLE_BITS = {"fc1": EGV.SINGLE_FC1, "fc2": EGV.SINGLE_FC2, "qkv": EGV.SINGLE_QKV, "proj": EGV.SINGLE_PROJ}
 _PASSES_INV = {3: "bf16x3", 1: "bf16", 2: "f16x2", 4: "f16"}
 A1_INV = 1.0 / (1.0 - 2.0 ** -6)      # csrc/f16x2.h: plane 1 of a first-operand f16x2 encoding is fp16((1 - 2^-6) x)
 _HARD_DEFAULTS = {
@@ -612,16 +612,18 @@ def empty_planes_f16x2(rows, cols, device, want_bf=False, single=False, split=Fa
 
 
 def f16_cast(x2d: torch.Tensor) -> Planes:
-    """fp32 [rows, cols] -> ONE plane of un-clamped fp16 (fmt 'f16'; egv_f16x2_encode role 2): a scaled gradient entering the fp16 backward."""
+    """fp32 [rows, cols] -> ONE plane of un-clamped fp16 (fmt 'f16'; egv_f16x2_encode role EGV_F16X2_GRAD_CAST): a scaled gradient entering the fp16 backward."""
     _need_cuda(x2d)
     rows, cols = x2d.shape
     pl = empty_planes_f16x2(rows, cols, x2d.device, single=True)
-    check(_lib.lib().egv_f16x2_encode(_p(x2d), x2d.stride(0), rows, cols, _p(pl.hi), None, None, pl.ld, 2, _stream(x2d)), "egv_f16x2_encode")
+    check(_lib.lib().egv_f16x2_encode(_p(x2d), x2d.stride(0), rows, cols, _p(pl.hi), None, None, pl.ld, EGV.F16X2_GRAD_CAST, _stream(x2d)),
+          "egv_f16x2_encode")
     return pl
 
 
 def f16x2_encode(x2d: torch.Tensor, role: int, want_bf=False) -> Planes:
-    """fp32 [rows, cols] -> f16x2 operand planes (egv_f16x2_encode); role 0 = first operand (activations), 1 = second (weights)."""
+    """fp32 [rows, cols] -> f16x2 operand planes (egv_f16x2_encode); role EGV.F16X2_FIRST = first operand (activations), EGV.F16X2_SECOND = second
+    (weights)."""
     _need_cuda(x2d)
     rows, cols = x2d.shape
     pl = empty_planes_f16x2(rows, cols, x2d.device, want_bf)
@@ -641,7 +643,7 @@ def f16x2_encode_multi(jobs, prepare=False):
         _need_cuda(j[0])
     args = (n, vp(*[j[0].data_ptr() for j in jobs]), i64(*[j[0].stride(0) for j in jobs]),
             i32(*[j[0].shape[0] for j in jobs]), i32(*[j[0].shape[1] for j in jobs]),
-            vp(*[j[1] for j in jobs]), vp(*[j[2] for j in jobs]), i64(*[j[3] for j in jobs]), 1)
+            vp(*[j[1] for j in jobs]), vp(*[j[2] for j in jobs]), i64(*[j[3] for j in jobs]), EGV.F16X2_SECOND)
     fn = _lib.lib().egv_f16x2_encode_multi
 
     def run(stream):
@@ -711,22 +713,23 @@ def gemm_nt(a: Planes, b: Planes, *, passes, bias=None, residual=None, act=ACT_N
             b.fmt not in (("f16x2", "f16") if passes == 4 else (("f16x2",) if passes == 2 else ("bf16",))):
         raise ValueError(f"gemm_nt: operand formats {a.fmt} / {b.fmt} do not go with passes = {passes}")
     a_hi = a.f16_plane() if passes == 4 else a.hi
-    out_fmt = 0
+    out_fmt = EGV.OUT_BF16_SPLIT
     if out_planes is not None and out_planes.fmt != "bf16":
-        # 'f16x2' -> 1; 'f16' -> 2 (an activation: saturating) or 4 (a scaled gradient: un-clamped -- the GELU' epilogue, or grad_out);
-        # 'f16s' -> 3 (an fp16 split: the qkv planes of the fp16 attention)
-        out_fmt = {"f16x2": 1, "f16": 4 if (act == ACT_GELU_BWD or grad_out) else 2, "f16s": 3}[out_planes.fmt]
+        # 'f16': an activation (saturating), or a scaled gradient (un-clamped -- the GELU' epilogue, or grad_out);
+        # 'f16s': an fp16 split (the qkv planes of the fp16 attention)
+        out_fmt = {"f16x2": EGV.OUT_F16X2, "f16": EGV.OUT_F16_GRAD if (act == ACT_GELU_BWD or grad_out) else EGV.OUT_F16,
+                   "f16s": EGV.OUT_F16_SPLIT}[out_planes.fmt]
     if ksplit is None:
         ksplit = 1 if passes in (2, 4) else auto_ksplit_nt(M, N, K)
     aux = aux_in if aux_in is not None else aux_out
-    aux_bf16 = int(aux is not None and aux.dtype in (torch.bfloat16, torch.float16))
+    aux_bf16 = EGV.AUX_Z_BF16 if aux is not None and aux.dtype in (torch.bfloat16, torch.float16) else EGV.AUX_F32
     if aux_is_grad:
-        if not aux_bf16:
+        if aux_bf16 == EGV.AUX_F32:
             raise ValueError("aux_is_grad needs a 16-bit aux buffer")
-        aux_bf16 = 3 if aux.dtype == torch.float16 else 2       # 3: gelu' saved as fp16 (the fp16 backward)
+        aux_bf16 = EGV.AUX_DGELU_F16 if aux.dtype == torch.float16 else EGV.AUX_DGELU_BF16       # fp16: the fp16 backward
     elif aux is not None and aux.dtype == torch.float16:
         raise ValueError("an fp16 aux buffer holds gelu' (aux_is_grad)")
-    if aux_bf16 and not uses_big_gemm(M, N, K, passes):
+    if aux_bf16 != EGV.AUX_F32 and not uses_big_gemm(M, N, K, passes):
         raise ValueError("bf16 aux buffers are only supported by the big-tile GEMM kernel (see uses_big_gemm)")
     partial = torch.empty((ksplit, M, N), dtype=torch.float32, device=a.hi.device) if ksplit > 1 else None
     # one positional construction (the field order of egv_gemm_desc): 30 attribute stores cost ~6 us of host time per GEMM,
@@ -738,7 +741,7 @@ def gemm_nt(a: Planes, b: Planes, *, passes, bias=None, residual=None, act=ACT_N
                  _p(out_planes.hi) if out_planes is not None else None, _p(out_planes.lo) if out_planes is not None else None,
                  out_planes.ld if out_planes is not None else 0,
                  ksplit, 0, _p(partial), 0, aux_bf16, None, ec.gemm_grid, out_fmt,
-                 _p(out_planes.bf) if out_fmt else None)
+                 _p(out_planes.bf) if out_fmt != EGV.OUT_BF16_SPLIT else None)
     timer = ec.kernel_timer
     if timer is not None:
         timer.time("egv_gemm_nt", 2.0 * M * N * K,
@@ -966,7 +969,8 @@ def layernorm_bwd(dy2d, x2d, gamma, mean, rstd, *, add1=None, add2=None, rows=No
         dy_args = (_p(dy2d), None, None, dy2d.stride(0))
     check(_lib.lib().egv_layernorm_bwd_fmt(*dy_args, _p(x2d), ldx, _p(gamma), _p(mean), _p(rstd), rows,
                                            cols, _p(add1), _p(add2), _p(dx), lddx, _p(pl.hi) if pl else None,
-                                           _p(pl.lo) if pl else None, (1 if planes_passes == 4 else 0) | (2 if dy_f16 else 0), _p(dg), _p(db),
+                                           _p(pl.lo) if pl else None, (EGV.LN_DX_F16 if planes_passes == 4 else 0) | (EGV.LN_DY_F16 if dy_f16 else 0),
+                                           _p(dg), _p(db),
                                            _p(work), _stream(x2d)), "egv_layernorm_bwd_fmt")
     if planes_passes:
         return dx, dg, db, pl
@@ -1123,12 +1127,12 @@ def assemble_tokens_bwd(dx, B, T, n, D, T_model, keep=None):
 
 
 # ---------------------------------------------------------------------------------------------- attention
-ATT_OUT_FMTS = {"bf16": 0, "bf16+f16": 1, "f16x2": 2, "f16": 3}      # csrc/attn_common.h ATT_OUT_*
-TIME_ATTN_MAX_FRAMES = 64    # frames of a time-attention group (mode & 1): csrc/attn_time_mfma.hip up to 16, attn_time_long.hip up to 64
+ATT_OUT_FMTS = {"bf16": EGV.ATTN_OUT_BF16_SPLIT, "bf16+f16": EGV.ATTN_OUT_BF16_F16, "f16x2": EGV.ATTN_OUT_F16X2, "f16": EGV.ATTN_OUT_F16}
+TIME_ATTN_MAX_FRAMES = 64    # frames of a time-attention group (EGV_ATTN_TIME): csrc/attn_time_mfma.hip up to 16, attn_time_long.hip up to 64
 
 
 def _check_time_frames(who, T, mode):
-    if mode & 1 and T > TIME_ATTN_MAX_FRAMES:
+    if mode & EGV.ATTN_TIME and T > TIME_ATTN_MAX_FRAMES:
         raise ValueError("%s: time attention takes at most TIME_ATTN_MAX_FRAMES = %d frames, got T = %d" % (who, TIME_ATTN_MAX_FRAMES, T))
 
 
@@ -1142,7 +1146,7 @@ def divided_attn_fwd(qkv: Planes, B, T, n, H, mode, passes, out_f16=False, out_f
     S = 1 + T * n
     dev = qkv.hi.device
     if qkv.fmt == "f16s":
-        mode = mode | 8                      # the qkv planes are an fp16 split: fp16 MFMA products
+        mode = mode | EGV.ATTN_FWD_QKV_F16   # the qkv planes are an fp16 split: fp16 MFMA products
     out_fmt = ("bf16+f16" if out_f16 else "bf16") if out_fmt is None else out_fmt
     if out_fmt != "bf16":
         if passes != 3:
@@ -1152,11 +1156,11 @@ def divided_attn_fwd(qkv: Planes, B, T, n, H, mode, passes, out_f16=False, out_f
         else:
             out = empty_planes(B * S, H * 64, passes, dev)
             out = Planes(out.hi, out.lo.view(torch.float16), out.rows, out.cols, "bf16+f16")
-        mode = mode | (ATT_OUT_FMTS[out_fmt] << 1)
+        mode = mode | (ATT_OUT_FMTS[out_fmt] << EGV.ATTN_OUT_SHIFT)
     else:
         out = empty_planes(B * S, H * 64, passes, dev)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)
-    work = torch.empty(_cached_size("attn_fwd", B, T, n, H, mode & 1), dtype=torch.float32, device=dev)
+    work = torch.empty(_cached_size("attn_fwd", B, T, n, H, mode & EGV.ATTN_TIME), dtype=torch.float32, device=dev)
     check(_lib.lib().egv_divided_attn_fwd(_p(qkv.hi), _p(qkv.lo), B, T, n, H, mode, passes, _p(out.hi), _p(out.lo),
                                           _p(lse), _p(work), _stream(qkv.hi)), "egv_divided_attn_fwd")
     return out, lse
@@ -1170,14 +1174,14 @@ def divided_attn_bwd(qkv: Planes, out: Planes, d_out: Planes, lse, B, T, n, H, m
     dev = qkv.hi.device
     if grad_f16:
         dqkv = empty_planes_f16x2(B * S, 3 * H * 64, dev, single=True)
-        mode = mode | 8
+        mode = mode | EGV.ATTN_BWD_GRAD_F16
     else:
         dqkv = empty_planes(B * S, 3 * H * 64, passes, dev)
-    mode = mode | (ATT_OUT_FMTS[out.fmt] << 1)          # how the forward wrote `out` (delta = rowsum(dO o O) decodes it)
+    mode = mode | (ATT_OUT_FMTS[out.fmt] << EGV.ATTN_OUT_SHIFT)      # how the forward wrote `out` (delta = rowsum(dO o O) decodes it)
     if qkv.fmt == "f16s":
         if not grad_f16 or d_out.fmt != "f16":
             raise ValueError("divided_attn_bwd: fp16 qkv planes go with an fp16 dO plane and an fp16 dqkv plane (the fp16 backward)")
-        mode = mode | 16                                # q / k / v / dO are fp16: fp16 products throughout
+        mode = mode | EGV.ATTN_BWD_QKV_F16              # q / k / v / dO are fp16: fp16 products throughout
     work = torch.empty(_cached_size("attn_bwd", B, T, n, H), dtype=torch.float32, device=dev)
     out_lo = out.lo if out.fmt == "bf16" else None      # an fp16(value) plane is not a residual: delta comes from the first plane alone
     check(_lib.lib().egv_divided_attn_bwd(_p(qkv.hi), _p(qkv.lo), _p(out.hi), _p(out_lo), _p(d_out.hi), _p(d_out.lo),
@@ -1412,7 +1416,7 @@ def cls_linear_dgrad(dy, W, *, z=None, out=None, ldo=None, add=False):
     if out is None:
         out = torch.empty((R, K), dtype=torch.float32, device=dy.device)
         add = False
-    mode = (2 if out.dtype == torch.float16 else 1) if add else 0
+    mode = (EGV.CLS_DX_ADD_F16 if out.dtype == torch.float16 else EGV.CLS_DX_ADD_F32) if add else EGV.CLS_DX_STORE
     if out.dtype == torch.float16 and not add:
         raise ValueError("cls_linear_dgrad: an fp16 destination is accumulated into (add=True)")
     lib = _lib.lib()
@@ -1439,7 +1443,8 @@ def _kv_planes(kv: Planes, D):
         raise ValueError(f"cls_attn: k | v planes are split-bf16 or an fp16 split, got {kv.fmt!r}")
     es = kv.hi.element_size()
     lo = kv.lo
-    return (_p(kv.hi), _p(lo), _p(kv.hi) + D * es, None if lo is None else _p(lo) + D * es, kv.ld, 0 if kv.fmt == "bf16" else 1)
+    return (_p(kv.hi), _p(lo), _p(kv.hi) + D * es, None if lo is None else _p(lo) + D * es, kv.ld,
+            EGV.CLS_KV_BF16 if kv.fmt == "bf16" else EGV.CLS_KV_F16)
 
 
 def cls_attn_fwd(q, kv: Planes, B, S, H):

@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._lib import EGV
 
 EPOCH = 0
 
@@ -184,7 +185,7 @@ class WeightCache:
             ent.t16 = ops.Planes(t, None, k, n, "f16")
             ops.split_f32_multi([(w2c, None, None, 0, None, None, ld, ld, t.data_ptr())])
         if fmt == "f16x2" or ent.p2 is not None:
-            ent.p2 = ops.f16x2_encode(w2.contiguous(), role=1)
+            ent.p2 = ops.f16x2_encode(w2.contiguous(), role=EGV.F16X2_SECOND)
         ent.ver = ent.version()
         return out()
 

@@ -35,6 +35,30 @@ typedef uint16_t egv_bf16;
 
 enum { EGV_ACT_NONE = 0, EGV_ACT_GELU = 1, EGV_ACT_GELU_BWD = 2, EGV_ACT_RELU_BWD = 3 };
 
+/* Every format and mode code of this ABI, named once; what each means stands at the field or argument that takes it.  The Python
+ * mirror is the CODES table of egovlp_amd/_lib.py; tests/test_abi.py holds the two together, name by name.                       */
+/* egv_gemm_desc.out_fmt: the format of (out_hi, out_lo) */
+enum { EGV_OUT_BF16_SPLIT = 0, EGV_OUT_F16X2 = 1, EGV_OUT_F16 = 2, EGV_OUT_F16_SPLIT = 3, EGV_OUT_F16_GRAD = 4 };
+/* egv_gemm_desc.aux_bf16: what aux_in / aux_out hold */
+enum { EGV_AUX_F32 = 0, EGV_AUX_Z_BF16 = 1, EGV_AUX_DGELU_BF16 = 2, EGV_AUX_DGELU_F16 = 3 };
+/* the format of the attention output planes: a field of the mode word of egv_divided_attn_fwd / _bwd */
+enum { EGV_ATTN_OUT_BF16_SPLIT = 0, EGV_ATTN_OUT_BF16_F16 = 1, EGV_ATTN_OUT_F16X2 = 2, EGV_ATTN_OUT_F16 = 3 };
+/* the mode word of egv_divided_attn_fwd / _bwd: EGV_ATTN_TIME | fmt << EGV_ATTN_OUT_SHIFT | the FWD_ or BWD_ bits of the call */
+enum { EGV_ATTN_TIME = 1, EGV_ATTN_OUT_SHIFT = 1, EGV_ATTN_OUT_MASK = 3,
+       EGV_ATTN_FWD_QKV_F16 = 8, EGV_ATTN_BWD_GRAD_F16 = 8, EGV_ATTN_BWD_QKV_F16 = 16 };
+/* dx_fmt of egv_layernorm_bwd_fmt / _partial: bits */
+enum { EGV_LN_DX_F16 = 1, EGV_LN_DY_F16 = 2 };
+/* role of egv_f16x2_encode[_multi] */
+enum { EGV_F16X2_FIRST = 0, EGV_F16X2_SECOND = 1, EGV_F16X2_GRAD_CAST = 2 };
+/* egv_block_geom.train: bits */
+enum { EGV_TRAIN_KEEP = 1, EGV_TRAIN_CLS_TAIL = 2 };
+/* egv_block_geom.f16_single: bits, one per pair of Linears */
+enum { EGV_SINGLE_FC1 = 1, EGV_SINGLE_FC2 = 2, EGV_SINGLE_QKV = 4, EGV_SINGLE_PROJ = 8 };
+/* kv_fmt / d_fmt of egv_cls_attn_fwd / _bwd */
+enum { EGV_CLS_KV_BF16 = 0, EGV_CLS_KV_F16 = 1 };
+/* dx_mode of egv_cls_linear_dgrad */
+enum { EGV_CLS_DX_STORE = 0, EGV_CLS_DX_ADD_F32 = 1, EGV_CLS_DX_ADD_F16 = 2 };
+
 /* ---- GEMM --------------------------------------------------------------------------------------
  * C[M,N] = alpha * A[M,K] . B[N,K]^T, then (in this order) + bias[n], activation, + residual[m,n].
  * Replaces nn.Linear / Conv2d-as-GEMM forward, dgrad and wgrad: model/video_transformer.py:41-50
@@ -44,7 +68,7 @@ enum { EGV_ACT_NONE = 0, EGV_ACT_GELU = 1, EGV_ACT_GELU_BWD = 2, EGV_ACT_RELU_BW
  * egv_f16x2_encode: a_hi / a_lo = the two fp16 planes of a first-operand encoding, b_hi / b_lo of a second-operand encoding;
  * big-tile NT kernel only, un-split) -- the same fp32-grade product from TWO fp16 MFMA products; passes = 4: ONE fp16 MFMA product of
  * plain fp16 planes (a_hi = fp16(A), b_hi = fp16(B) = plane 1 of a second-operand f16x2 encoding; a_lo / b_lo ignored; big-tile NT
- * kernel only, un-split; epilogues: bias + residual -> fp32 / split planes, or EGV_ACT_GELU -> out_fmt 1 / 2) -- 2^-11 per operand:
+ * kernel only, un-split; epilogues: bias + residual -> fp32 / split planes, or EGV_ACT_GELU -> EGV_OUT_F16X2 / EGV_OUT_F16) -- 2^-11 per operand:
  * for the Linears whose share of the 1e-3 parity budget allows it -- and, with trans == 1, the weight gradient of the
  * FP16 BACKWARD (dW = dY^T X on fp16(S dY) and the forward's fp16 activation plane, split-K allowed; alpha rescales the product --
  * 1 / (1 - 2^-6) when X is plane 1 of an f16x2 first-operand encoding -- but not the column sums).  Requirements: K % 32 == 0, N % 4 == 0,
@@ -77,12 +101,14 @@ typedef struct egv_gemm_desc {
   int32_t ksplit, accumulate;
   float* partial;
   int32_t trans;    /* (see below) */
-  int32_t aux_bf16; /* != 0: aux_in / aux_out are bf16 [M, ldaux] instead of fp32 (the GELU pre-activation saved by fc1 for
-                       fc2's dgrad: half the bytes when backward runs single-pass bf16 anyway).  Big-tile kernel only.
-                       2: the bf16 buffer holds gelu'(pre-activation) itself -- EGV_ACT_GELU stores the derivative (it has
+  int32_t aux_bf16; /* a CODE, not a flag (the name is older than its values): what aux_in / aux_out [M, ldaux] hold.
+                       EGV_AUX_F32: the fp32 pre-activation.  Every other code is 16 bits per element, big-tile kernel and the GELU
+                       epilogues only.  EGV_AUX_Z_BF16: the pre-activation as bf16 (saved by fc1 for fc2's dgrad: half the bytes
+                       when backward runs single-pass bf16 anyway).
+                       EGV_AUX_DGELU_BF16: bf16 of gelu'(pre-activation) itself -- EGV_ACT_GELU stores the derivative (it has
                        Phi and phi in registers) and EGV_ACT_GELU_BWD multiplies by the stored value, no second erf.
-                       3: as 2 with the derivative stored as FP16 (passes == 2 / 4 launches only; plane outputs and neither
-                       out_f32 nor residual next to them -- anything else is an invalid argument: only the plane epilogue
+                       EGV_AUX_DGELU_F16: the same derivative stored as FP16 (passes == 2 / 4 launches only; plane outputs and
+                       neither out_f32 nor residual next to them -- anything else is an invalid argument: only the plane epilogue
                        reads and writes fp16 there): the fp16 backward, where bf16's 2^-9 on gelu' would cap the accuracy of dZ.
                        trans = 0: A[M,K], B[N,K] (contraction index contiguous).  1 ("TN", wgrad): A is stored [K, lda] with
                        its M rows as COLUMNS and B is stored [K, ldb] with N columns, C[m,n] = sum_k A[k,m] B[k,n] --
@@ -94,12 +120,20 @@ typedef struct egv_gemm_desc {
                        callers pass e.g. 248 so that the RCCL kernels of the overlapped gradient all-reduce find free CUs.
                        Multiples of 8 in [8, 256]; anything else is an invalid argument.  (Per call, not per process: the
                        library keeps no state between calls.)                                                         */
-  int32_t out_fmt;  /* format of (out_hi, out_lo): 0 = split-bf16 planes; 1 = the f16x2 operand format below, first-operand role
-                       (two fp16 planes); 2 = ONE plane of plain fp16 in out_hi (out_lo unused): the operand of a passes == 4
-                       consumer.  1 / 2: EGV_ACT_GELU of a passes == 2 or 4 product only (fc1 -> fc2 of the forward); 2 also with
-                       EGV_ACT_GELU_BWD of a passes == 4 product: dZ of the fp16 backward as ONE plane of UN-CLAMPED fp16 (a scaled
-                       gradient beyond fp16's range becomes inf, which the loss-scale logic answers with a skipped step).            */
-  egv_bf16* out_bf; /* out_fmt != 0, optional: bf16(value) as a further plane [M, ldoh] -- the single-pass operand the backward GEMMs
+  int32_t out_fmt;  /* format of (out_hi, out_lo).  EGV_OUT_BF16_SPLIT: split-bf16 planes.  Every other format is fp16: an un-split NT
+                       launch with passes == 2 or 4 that writes planes only (out_hi given, ldoh % 8 == 0; no out_f32, no residual, a
+                       16-bit aux_out if any) -- anything else is an invalid argument.
+                       EGV_OUT_F16X2: the f16x2 operand format below, first-operand role (two fp16 planes; out_lo required).
+                       EGV_OUT_F16: ONE plane of plain, saturating fp16 in out_hi (out_lo unused): the operand of a passes == 4
+                       consumer.  Both: EGV_ACT_GELU only (fc1 -> fc2 of the forward).
+                       EGV_OUT_F16_SPLIT: out_hi = fp16(v), out_lo = fp16(v - out_hi) (out_lo required), EGV_ACT_NONE only: the qkv
+                       planes that the fp16 attention multiplies.
+                       EGV_OUT_F16_GRAD: ONE plane of UN-CLAMPED fp16 in out_hi (a scaled gradient beyond fp16's range becomes inf,
+                       which the loss-scale logic answers with a skipped step): the gradients of the fp16 backward, from a launch
+                       that runs ONE fp16 product per k-tile (passes == 4; passes == 2 where csrc/gemm_dispatch.h runs it as two
+                       k-segments) -- EGV_ACT_NONE without bias (dO of a plain dgrad), or EGV_ACT_GELU_BWD on a saved derivative
+                       (aux_bf16 EGV_AUX_DGELU_BF16 / _F16): dZ.                                                                   */
+  egv_bf16* out_bf; /* out_fmt != EGV_OUT_BF16_SPLIT, optional: bf16(value) as a further plane [M, ldoh] -- the single-pass operand the backward GEMMs
                        (wgrad) read, since an fp16 plane cannot share an MFMA with bf16 gradients.                               */
 } egv_gemm_desc;
 int egv_gemm_nt(const egv_gemm_desc* d, void* stream);
@@ -143,10 +177,11 @@ int egv_transpose_planes(const egv_bf16* hi, const egv_bf16* lo, int64_t ldx, in
  * and cancels a1's rounding error rho; the roundings that are not compensated are attenuated by e or 2^-12 / e (~2^-17 per product:
  * 5.3e-6 on random operands where split-bf16 x3 gives 4.4e-6; embeddings 3.2e-5 from the fp32 oracle where it gives 2.7e-5).
  * An operand [rows, cols] (cols % 8 == 0) is two fp16 planes [rows, ld] (ld % 8 == 0) -- the geometry of split-bf16 planes.
- * bf (optional): bf16(x) [rows, ld], the operand of single-pass backward GEMMs.  role: 0 = first operand, 1 = second operand;
- * 2 = ONE plane of plain, UN-CLAMPED fp16 in p1 (p2 / bf unused): a scaled gradient entering the fp16 backward as fp32.
+ * bf (optional): bf16(x) [rows, ld], the operand of single-pass backward GEMMs.  role: EGV_F16X2_FIRST = first operand, EGV_F16X2_SECOND =
+ * second operand; EGV_F16X2_GRAD_CAST (egv_f16x2_encode only) = ONE plane of plain, UN-CLAMPED fp16 in p1 (p2 / bf unused): a scaled
+ * gradient entering the fp16 backward as fp32.
  * Replaces nothing in the reference (fp32 there); producers: this converter (weights, tests), egv_layernorm_fwd_f16x2, the
- * EGV_ACT_GELU epilogue with out_fmt = 1.  Range: fp16 (saturating at 65504; below ~4e-3 a2 loses relative, not absolute, accuracy):
+ * EGV_ACT_GELU epilogue with out_fmt = EGV_OUT_F16X2.  Range: fp16 (saturating at 65504; below ~4e-3 a2 loses relative, not absolute, accuracy):
  * forward operands only.                                                                                                          */
 int egv_f16x2_encode(const float* x, int64_t ldx, int32_t rows, int32_t cols, uint16_t* p1, uint16_t* p2, egv_bf16* bf,
                      int64_t ldo, int32_t role, void* stream);
@@ -170,11 +205,11 @@ int egv_layernorm_fwd_f16x2(const float* x, int64_t ldx, const float* gamma, con
  * fwd_passes: 3 = split-bf16 three-product, 1 = single-pass bf16, 2 = the f16x2 format (two fp16 products in the qkv / fc1 / fc2
  * Linears, or one where f16_single says so; attention and, unless the backward is fp16, the proj Linears stay split-bf16).
  * bwd_passes: 3 (fwd_passes 3 only), 1 (any forward), or 4 = ONE fp16 product on loss-scaled gradients (fwd_passes 2 only: it reads
- * the forward's own fp16 planes).  train bit 0 keeps what the backward needs (z_bf16 != 0: fc1 saves gelu'(z) in 16 bits -- bf16, fp16
+ * the forward's own fp16 planes).  train & EGV_TRAIN_KEEP keeps what the backward needs (z_bf16 != 0: fc1 saves gelu'(z) in 16 bits -- bf16, fp16
  * for bwd_passes 4; single-product backwards, required with fwd_passes 2 -- instead of the fp32 pre-activation).  Every decision that
  * follows from these five words is made once, in csrc/block_plan.h.
  * The forward arena must stay untouched until egv_block_bwd has run on it.
- * CLS tail (train bit 1; the tower's LAST block, whose output is read on the B CLS rows only -- norm(x)[:, 0], :330): `out` of
+ * CLS tail (train & EGV_TRAIN_CLS_TAIL; the tower's LAST block, whose output is read on the B CLS rows only -- norm(x)[:, 0], :330): `out` of
  * egv_block_fwd is the dense [B, D] fp32 CLS rows and io.g_out of egv_block_bwd their [B, D] gradient (io.g_hi NULL); d_x stays
  * [M, D].  The time branch, norm1 and the k / v rows of the space qkv Linear run over all rows as before; the space attention's CLS
  * query, the space proj, norm2, fc1 / GELU and fc2 run on B rows in fp32 from the fp32 MASTER weights (the egv_cls_* entry points
@@ -185,13 +220,13 @@ int egv_layernorm_fwd_f16x2(const float* x, int64_t ldx, const float* gamma, con
  * does not.                                                                                                                     */
 typedef struct egv_block_geom {
   int32_t B, T, n, H, D, Hd;
-  int32_t fwd_passes, bwd_passes, train /* bit 0: keep what the backward needs; bit 1: CLS tail */, z_bf16;
+  int32_t fwd_passes, bwd_passes, train /* EGV_TRAIN_KEEP: keep what the backward needs | EGV_TRAIN_CLS_TAIL */, z_bf16;
   float eps;
   int32_t grid_cap;     /* as egv_gemm_desc.grid_cap */
   int32_t f16_single;   /* fwd_passes == 2 only: which Linears of THIS block run ONE fp16 product (egv_gemm_nt passes == 4) instead of
-                           the two of the f16x2 format -- bit 0: fc1 (norm2 then writes one plain fp16 plane), bit 1: fc2 (the GELU
-                           epilogue of fc1 then writes h as one plain fp16 plane), bit 2: both qkv Linears (norm3 / norm1 write one
-                           plain fp16 plane), bit 3: both proj Linears (the attention kernels write fp16(value) as their second
+                           the two of the f16x2 format -- EGV_SINGLE_FC1 (norm2 then writes one plain fp16 plane), EGV_SINGLE_FC2 (the GELU
+                           epilogue of fc1 then writes h as one plain fp16 plane), EGV_SINGLE_QKV: both qkv Linears (norm3 / norm1 write
+                           one plain fp16 plane), EGV_SINGLE_PROJ: both proj Linears (the attention kernels write fp16(value) as their second
                            output plane; w_hi[1] / w_hi[3] are then the weights' f16x2 encodings like those of the other single-
                            product Linears).  0 elsewhere.  Which blocks may is the caller's precision policy.        */
 } egv_block_geom;
@@ -274,10 +309,10 @@ int egv_layernorm_bwd(const float* dy, const egv_bf16* dy_hi, const egv_bf16* dy
                       const float* mean, const float* rstd, int32_t rows, int32_t cols,
                       const float* add1, const float* add2, float* dx, int64_t lddx,
                       egv_bf16* dx_hi, egv_bf16* dx_lo, float* dgamma, float* dbeta, float* work, void* stream);
-/* The same with the plane formats as an argument.  dx_fmt bit 0: 0 = dx planes are split-bf16 (dx_hi[, dx_lo]); 1 = ONE plane of
- * UN-CLAMPED fp16 in dx_hi (dx_lo must be NULL): the operand of the next dgrad / wgrad GEMMs of the fp16 backward.  dx_fmt bit 1 (+ 2):
- * dy is ONE plane of un-clamped fp16 in dy_hi (dy and dy_lo NULL) -- what the dgrad GEMM in front writes in the fp16 backward
- * (egv_gemm_desc.out_fmt 4): half the bytes of an fp32 dy on both sides, one more fp16 rounding of a scaled gradient.                */
+/* The same with the plane formats as an argument, dx_fmt = 0 or an OR of: EGV_LN_DX_F16 -- the dx planes are ONE plane of UN-CLAMPED
+ * fp16 in dx_hi (dx_lo must be NULL) instead of split-bf16 (dx_hi[, dx_lo]): the operand of the next dgrad / wgrad GEMMs of the fp16
+ * backward; EGV_LN_DY_F16 -- dy is ONE plane of un-clamped fp16 in dy_hi (dy and dy_lo NULL), what the dgrad GEMM in front writes in
+ * the fp16 backward (egv_gemm_desc.out_fmt EGV_OUT_F16_GRAD): half the bytes of an fp32 dy on both sides, one more fp16 rounding of a scaled gradient.                */
 int egv_layernorm_bwd_fmt(const float* dy, const egv_bf16* dy_hi, const egv_bf16* dy_lo, int64_t lddy,
                           const float* x, int64_t ldx, const float* gamma,
                           const float* mean, const float* rstd, int32_t rows, int32_t cols,
@@ -384,7 +419,7 @@ int egv_assemble_tokens_bwd_sel(const float* dx, const int32_t* keep, int32_t B,
  * VarAttention core (model/video_transformer.py:104-133) on the fused qkv buffer [B, S, 3, H, 64] given as split-bf16
  * planes (exactly what the qkv GEMM epilogue writes; qkv_lo is ignored / may be NULL when passes == 1).
  * S = 1 + T*n, token order 1 + f*n + i.  q is scaled by 64^-0.5 inside.  mode 0 = space (group = (b,f,h): n queries x
- * (CLS + n) keys, bf16 MFMA, scores never leave LDS / registers), mode 1 = time (group = (b,i,h): T queries x (CLS + T)
+ * (CLS + n) keys, bf16 MFMA, scores never leave LDS / registers), mode EGV_ATTN_TIME = time (group = (b,i,h): T queries x (CLS + T)
  * keys, bf16 MFMA as well).  The CLS query row (attends to all S keys, :112) rides in every group as an extra query; its
  * partials are merged by a small combine kernel.  Output: split planes [B, S, H*64]; lse [B, H, S] (log-sum-exp of each
  * query row, saved for backward).  `work`: egv_divided_attn_fwd_work_floats(...) floats.
@@ -393,12 +428,17 @@ int egv_assemble_tokens_bwd_sel(const float* dx, const int32_t* keep, int32_t B,
  * workspaces, precision combinations and output formats.  No structural upper bound on n (S = 1 + T*n must fit int32); largest
  * size tested: n = 784 (785 keys).  Time groups: T <= 16 frames are ONE 16-row tile per location (csrc/attn_time_mfma.hip),
  * 16 < T <= 64 are 2 - 4 tiles held by one workgroup (csrc/attn_time_long.hip) with the same arguments, workspaces, precision
- * combinations and output formats; mode 1 with T > 64 returns EGV_ERR_ARG (space mode has no bound on T).  head dim 64 only.
- * mode bits 1-2 (mode = 2 fmt + (0 space | 1 time); fmt != 0 with passes == 3 only) = the format of the output planes:
- *   0  split-bf16 (out_hi = bf16(v), out_lo = bf16(v - out_hi)): a three-product proj;
- *   1  out_hi = bf16(v) (what a bf16 backward reads), out_lo = fp16(v): the operand of a proj Linear that runs ONE fp16 product;
- *   2  the f16x2 operand format, first-operand role (out_hi = a1, out_lo = a2): a TWO-product proj whose backward is fp16;
- *   3  out_hi = fp16(v), out_lo unused (may be NULL): a one-product proj whose backward is fp16 as well.                 */
+ * combinations and output formats; EGV_ATTN_TIME with T > 64 returns EGV_ERR_ARG (space mode has no bound on T).  head dim 64 only.
+ * The mode word: mode = (0 space | EGV_ATTN_TIME) | fmt << EGV_ATTN_OUT_SHIFT | (0 | EGV_ATTN_FWD_QKV_F16).  fmt (EGV_ATTN_OUT_MASK wide;
+ * any but EGV_ATTN_OUT_BF16_SPLIT with passes == 3 only) = the format of the output planes:
+ *   EGV_ATTN_OUT_BF16_SPLIT  split-bf16 (out_hi = bf16(v), out_lo = bf16(v - out_hi)): a three-product proj;
+ *   EGV_ATTN_OUT_BF16_F16    out_hi = bf16(v) (what a bf16 backward reads), out_lo = fp16(v): the operand of a proj Linear that runs ONE
+ *                            fp16 product;
+ *   EGV_ATTN_OUT_F16X2       the f16x2 operand format, first-operand role (out_hi = a1, out_lo = a2): a TWO-product proj whose backward
+ *                            is fp16;
+ *   EGV_ATTN_OUT_F16         out_hi = fp16(v), out_lo unused (may be NULL): a one-product proj whose backward is fp16 as well.
+ * EGV_ATTN_FWD_QKV_F16 (passes == 3 only): the qkv planes are an fp16 split (egv_gemm_desc.out_fmt EGV_OUT_F16_SPLIT) and the kernels
+ * multiply fp16.  Any other bit is an invalid argument.                                                                            */
 int egv_divided_attn_fwd(const egv_bf16* qkv_hi, const egv_bf16* qkv_lo, int32_t B, int32_t T, int32_t n, int32_t H,
                          int32_t mode, int32_t passes, egv_bf16* out_hi, egv_bf16* out_lo, float* lse, float* work,
                          void* stream);
@@ -408,9 +448,10 @@ int64_t egv_divided_attn_fwd_work_floats(int32_t B, int32_t T, int32_t n, int32_
  * contribution -- i.e. directly in the operand format of the qkv dgrad / wgrad GEMMs.  Only the CLS token's own
  * gradients are accumulated in fp32 (atomics) and converted by a finish kernel.
  * `work`: egv_divided_attn_bwd_work_floats(...) floats.
- * mode: bit 0 = time; bits 1-2 = the format the forward wrote out_* in (as above: delta = rowsum(dO o O) decodes it; formats 1-3
- * take out_lo = NULL); bit 3 (passes == 1 only) = dqkv_hi receives ONE plane of UN-CLAMPED fp16 instead of bf16 (the fp16 backward;
- * q / k / v / dO are still read as bf16 planes); bit 4 (with bit 3 and passes == 1 only) = q / k / v (qkv_hi: the first plane of an
+ * mode: EGV_ATTN_TIME; fmt << EGV_ATTN_OUT_SHIFT = the format the forward wrote out_* in (as above: delta = rowsum(dO o O) decodes it;
+ * every format but EGV_ATTN_OUT_BF16_SPLIT takes out_lo = NULL, the fp16 ones passes == 1 only); EGV_ATTN_BWD_GRAD_F16 (passes == 1
+ * only) = dqkv_hi receives ONE plane of UN-CLAMPED fp16 instead of bf16 (the fp16 backward; q / k / v / dO are still read as bf16
+ * planes); EGV_ATTN_BWD_QKV_F16 (with EGV_ATTN_BWD_GRAD_F16 and passes == 1 only) = q / k / v (qkv_hi: the first plane of an
  * fp16-split qkv) and dO (dout_hi) are fp16 planes: fp16 MFMA products throughout.  A refused call (EGV_ERR_ARG) enqueues nothing. */
 int egv_divided_attn_bwd(const egv_bf16* qkv_hi, const egv_bf16* qkv_lo, const egv_bf16* out_hi, const egv_bf16* out_lo,
                          const egv_bf16* dout_hi, const egv_bf16* dout_lo, const float* lse, int32_t B, int32_t T,
@@ -420,7 +461,7 @@ int64_t egv_divided_attn_bwd_work_floats(int32_t B, int32_t T, int32_t n, int32_
 
 /* ---- the CLS tail of the last video block (csrc/cls_tail.hip) ------------------------------------------------------------
  * forward_features ends with norm(x)[:, 0] (model/video_transformer.py:330): of the last SpaceTimeBlock's output only the B CLS rows
- * are read, so its space-attention output, space proj, norm2, fc1 / GELU, fc2 run on R = B rows (egv_block_fwd / _bwd with bit 1 of
+ * are read, so its space-attention output, space proj, norm2, fc1 / GELU, fc2 run on R = B rows (egv_block_fwd / _bwd with EGV_TRAIN_CLS_TAIL in
  * egv_block_geom.train).  These are the R-row pieces: Linears in plain fp32 straight from the fp32 master weights W[N,K] (latency-
  * sized: W is streamed once; no operand planes), and the attention of ONE query row per (clip, head).  Every sum runs in a fixed
  * order (no float atomics).  R >= 1; N % 4 == 0, K % 4 == 0, every leading dimension % 4 == 0, 16-byte aligned base pointers.
@@ -431,7 +472,8 @@ int egv_cls_linear_fwd(const float* x, int64_t ldx, const float* W, int64_t ldw,
                        int32_t K, int32_t act, float* z_out, const float* residual /* or NULL */, int64_t ldr, float* y, int64_t ldy,
                        void* stream);
 /* dX[R,K] = dY[R,N] . W[N,K]  (x gelu'(z[r,k]) when z != NULL: z = the [R, K] pre-activation egv_cls_linear_fwd saved).  dx_mode:
- * 0 = dX fp32 [R, lddx] is overwritten; 1 = added to the fp32 there; 2 = added to a plane of UN-CLAMPED fp16 (dx is uint16 [R, lddx]):
+ * EGV_CLS_DX_STORE = dX fp32 [R, lddx] is overwritten; EGV_CLS_DX_ADD_F32 = added to the fp32 there; EGV_CLS_DX_ADD_F16 = added to a
+ * plane of UN-CLAMPED fp16 (dx is uint16 [R, lddx]):
  * the B CLS rows of a gradient the big dgrad GEMM wrote for all rows.  `work`: egv_cls_linear_work_floats(R, N, K) floats.           */
 int64_t egv_cls_linear_work_floats(int32_t R, int32_t N, int32_t K);
 int egv_cls_linear_dgrad(const float* dy, int64_t lddy, const float* W, int64_t ldw, int32_t R, int32_t N, int32_t K, const float* z,
@@ -443,12 +485,13 @@ int egv_cls_linear_wgrad(const float* dy, int64_t lddy, const float* x, int64_t 
 int egv_cls_rows_add(float* dst, int64_t lddst, const float* src, int64_t ldsrc, int32_t R, int32_t cols, void* stream);
 /* Attention of the CLS query (model/video_transformer.py:112: cls_out = attn(cls_q, k, v) over all S = 1 + T n keys of its clip, the
  * CLS key / value row an ordinary key): q fp32 [B, H 64] (scaled by 64^-0.5 inside), k / v = operand planes with rows b S + j and the
- * head's 64 columns at h 64 (row stride ldkv elements; value = hi + lo, lo may be NULL); kv_fmt 0 = bf16 planes, 1 = fp16 planes.
+ * head's 64 columns at h 64 (row stride ldkv elements; value = hi + lo, lo may be NULL); kv_fmt EGV_CLS_KV_BF16 = bf16 planes,
+ * EGV_CLS_KV_F16 = fp16 planes.
  * The keys are streamed (online softmax): no bound on S.  out fp32 [B, H 64]; lse [B, H] = log sum_j exp(q . k_j / 8).               */
 int egv_cls_attn_fwd(const float* q, int64_t ldq, const uint16_t* k_hi, const uint16_t* k_lo, const uint16_t* v_hi, const uint16_t* v_lo,
                      int64_t ldkv, int32_t kv_fmt, int32_t B, int32_t S, int32_t H, float* out, int64_t ldo, float* lse, void* stream);
 /* Backward: dq fp32 [B, H 64] (contiguous) and dK / dV of EVERY key row, written once as gradient planes of row stride lddkv --
- * d_fmt 0: split-bf16 (dk_lo / dv_lo may be NULL), 1: ONE plane of un-clamped fp16 in dk_hi / dv_hi -- the operand format of the qkv
+ * d_fmt EGV_CLS_KV_BF16: split-bf16 (dk_lo / dv_lo may be NULL), EGV_CLS_KV_F16: ONE plane of un-clamped fp16 in dk_hi / dv_hi -- the operand format of the qkv
  * dgrad / wgrad GEMMs.  out / d_out fp32 [B, H 64] contiguous.                                                                      */
 int egv_cls_attn_bwd(const float* q, int64_t ldq, const uint16_t* k_hi, const uint16_t* k_lo, const uint16_t* v_hi, const uint16_t* v_lo,
                      int64_t ldkv, int32_t kv_fmt, const float* out, const float* d_out, const float* lse, int32_t B, int32_t S,

@@ -94,6 +94,28 @@ def test_every_abi_struct_layout_matches_header(tmp_path):
         i += 1 + len(fields)
 
 
+def test_every_enumerator_matches_the_python_mirror(tmp_path):
+    """The activation, format and mode codes of the C ABI: every enumerator the header declares, with the value the host C compiler
+    gives it, is an entry of _lib.CODES and the other way round -- a name missing on either side fails, as does a value that moved."""
+    import shutil
+    import subprocess
+    from egovlp_amd import _lib
+    if shutil.which("gcc") is None:
+        pytest.skip("no host C compiler")
+    hdr_nc = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "egovlp_hip.h")).read(), flags=re.S)
+    names = [item.split("=")[0].strip() for body in re.findall(r"\benum\s*\{(.*?)\}", hdr_nc, flags=re.S) for item in body.split(",")
+             if item.strip()]
+    assert names and len(names) == len(set(names)) and all(re.fullmatch(r"EGV_[A-Z0-9_]+", n) for n in names), names
+    src = tmp_path / "codes.c"
+    src.write_text('#include <stdio.h>\n#include "egovlp_hip.h"\nint main(void){\n' +
+                   "".join('printf("%s %%d\\n", (int)%s);\n' % (n, n) for n in names) + "return 0;}\n")
+    exe = tmp_path / "codes"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    declared = {k: int(v) for k, v in (ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())}
+    assert declared == _lib.CODES
+    assert vars(_lib.EGV) == {k[4:]: v for k, v in _lib.CODES.items()}
+
+
 def test_product_raises_without_gpu_tensors():
     """No CPU fallback: ops refuse host tensors instead of silently computing on the CPU."""
     import torch
