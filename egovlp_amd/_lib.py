@@ -131,7 +131,12 @@ PROTOTYPES = {
     "egv_egonce_from_sim": (i32, [c_p, c_p, c_p, i32, f32, i32, i32, c_p, c_p, c_p, c_p]),
     "egv_egonce_fwd_bwd_ls": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p, f32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "egv_egonce_long_fwd_bwd_ls": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p, f32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "egv_egonce_from_sim_ls": (i32, [c_p, c_p, c_p, i32, c_p, i32, i32, c_p, c_p, c_p, c_p, c_p]),
+    "egv_egonce_queue_work_floats": (i64, [i32, i32, i32, i32, i32]),
+    "egv_egonce_queue_layout": (i32, [i32, i32, i32, c_p, c_p]),
+    "egv_egonce_queue_fwd_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p, c_p, i32, c_p, f32, c_p, f32, i32, i32, c_p,
+                                       c_p, c_p, c_p, c_p, c_p]),
+    "egv_egonce_queue_push": (i32, [c_p, c_p, i32, i32, i32, i32, c_p, c_p, c_p, i32, c_p, c_p]),
+    "egv_egonce_from_sim_ls":(i32, [c_p, c_p, c_p, i32, c_p, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_sigmoid_head_fwd_bwd": (i32, [c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p, f32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p,
                                        c_p]),
     "egv_sigmoid_head_work_floats": (i64, [i32, i32, i32, i32]),

@@ -2,6 +2,8 @@
 (and their *_ls variants), egv_sigmoid_head_fwd_bwd and egv_maxmargin_head_fwd_bwd; the API-compatible pieces egv_sim_matrix_*,
 egv_egonce_from_sim(_ls), egv_sigmoid_from_sim, egv_maxmargin_fwd_bwd, egv_dual_softmax, egv_cross_entropy_fwd_bwd; and the
 classification head of the OSCC / PNR fine-tunes (egv_cls_head_fwd, egv_cls_head_loss_bwd, egv_cls_eval_update)."""
+import ctypes
+
 import torch
 
 from . import _lib, ops
@@ -82,6 +84,75 @@ def egonce_long_fwd_bwd(text, video, noun, verb, temperature, eps=1e-8, use_noun
     check(getattr(_lib.lib(), entry)(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, tau, float(eps), int(use_noun),
                                      int(use_verb), _p(loss), _p(dt), _p(dvv), *map(_p, dls), _p(work), ops._stream(text)), entry)
     return (loss, dt, dvv, *dls)
+
+
+EGONCE_QUEUE_MIN, EGONCE_QUEUE_MAX = 64, 65536     # capacity of an EgonceQueue: a multiple of 64 in this range
+
+
+def egonce_queue_size_ok(Q):
+    return isinstance(Q, int) and EGONCE_QUEUE_MIN <= Q <= EGONCE_QUEUE_MAX and Q % 64 == 0
+
+
+class EgonceQueue:
+    """The device buffers of egv_egonce_queue_fwd_bwd / _push, in the kernels' own layout (egv_egonce_queue_layout: Dp floats per
+    embedding row, W words per noun / verb row): text, video [Q, Dp] fp32, words [Q, W] int32, state int32 {head, filled}.  All
+    zeros: an empty queue.  `dn`, `dv`: the noun / verb widths (0, 0 for NormSoftmaxLoss)."""
+
+    def __init__(self, Q, D, dn, dv, device):
+        if not egonce_queue_size_ok(Q):
+            raise ValueError("queue size must be a multiple of 64 in [%d, %d], got %r" % (EGONCE_QUEUE_MIN, EGONCE_QUEUE_MAX, Q))
+        Dp, W = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(_lib.lib().egv_egonce_queue_layout(D, dn, dv, ctypes.byref(Dp), ctypes.byref(W)), "egv_egonce_queue_layout")
+        self.Q, self.D, self.dn, self.dv, self.Dp, self.W = Q, D, dn, dv, Dp.value, W.value
+        self.text = torch.zeros((Q, self.Dp), dtype=torch.float32, device=device)
+        self.video = torch.zeros((Q, self.Dp), dtype=torch.float32, device=device)
+        self.words = torch.zeros((Q, self.W), dtype=torch.int32, device=device)
+        self.state = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def check_batch(self, text, dn, dv):
+        if text.shape[1] != self.D or (dn, dv) != (self.dn, self.dv) or text.device != self.text.device:
+            raise ValueError("the queue was allocated for D = %d, noun / verb widths %d / %d on %s; got D = %d, %d / %d on %s"
+                             % (self.D, self.dn, self.dv, self.text.device, text.shape[1], dn, dv, text.device))
+        if text.shape[0] > self.Q:
+            raise ValueError("a batch of %d rows does not fit a queue of %d" % (text.shape[0], self.Q))
+
+    def reset(self):
+        self.state.zero_()
+
+    def filled(self):
+        "valid slots, read back from the device (synchronises)"
+        return int(self.state[1].item())
+
+    def head(self):
+        return int(self.state[0].item())
+
+
+def egonce_queue_fwd_bwd(text, video, noun, verb, temperature, queue, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,
+                         logit_scale=None):
+    """egv_egonce_queue_fwd_bwd: EgoNCE / NormSoftmaxLoss (noun = verb = None) of the batch with the valid slots of `queue` (an
+    EgonceQueue) as extra constant columns -> (loss[1], d_text, d_video, work); with `logit_scale` (as in egonce_fwd_bwd)
+    -> (loss[1], d_text, d_video, d_logit_scale [1], work).  Any n in [1, min(65536, queue.Q)].  The queue is only read; `work`
+    holds what egonce_queue_push enqueues."""
+    ops._need_cuda(text, video, noun, verb)
+    n, D = text.shape
+    dn, dv = _nv_widths(noun, verb)
+    queue.check_batch(text, dn, dv)
+    learn = logit_scale is not None
+    ls = _p(_one_fp32_arg(logit_scale, text, "logit_scale")) if learn else None
+    loss, work, dt, dvv, dls = _head_buffers(text, video, _lib.lib().egv_egonce_queue_work_floats(n, D, dn, dv, queue.Q),
+                                             want_grads, int(learn))
+    check(_lib.lib().egv_egonce_queue_fwd_bwd(_p(text), _p(video), _p(noun), _p(verb), n, D, dn, dv, _p(queue.text), _p(queue.video),
+                                              _p(queue.words), queue.Q, _p(queue.state), 0.0 if learn else float(temperature), ls,
+                                              float(eps), int(use_noun), int(use_verb), _p(loss), _p(dt), _p(dvv),
+                                              _p(dls[0]) if learn else None, _p(work), ops._stream(text)), "egv_egonce_queue_fwd_bwd")
+    return (loss, dt, dvv, *dls, work)
+
+
+def egonce_queue_push(work, loss, n, queue):
+    """egv_egonce_queue_push: the n rows the head just normalised and packed (`work`, `loss`: what egonce_queue_fwd_bwd returned)
+    go into the ring; a loss that is not finite enqueues nothing.  No host read."""
+    check(_lib.lib().egv_egonce_queue_push(_p(work), _p(loss), n, queue.D, queue.dn, queue.dv, _p(queue.text), _p(queue.video),
+                                           _p(queue.words), queue.Q, _p(queue.state), ops._stream(work)), "egv_egonce_queue_push")
 
 
 def sigmoid_head_fwd_bwd(text, video, noun, verb, logit_scale, logit_bias, eps=1e-8, use_noun=True, use_verb=True, want_grads=True,

@@ -7,7 +7,10 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip, through the wr
     matrices, the mask, the loss and the gradients w.r.t. both embeddings (egv_egonce_fwd_bwd; past 1 024 rows the tiled
     egv_egonce_long_fwd_bwd of csrc/egonce_long.hip, which forms no n x n matrix).
 Both losses take `learnable_temperature=True` (not in the reference): the temperature becomes CLIP's learnable logit scale, read on the
-device by the *_ls variants of the same entry points, which also return its gradient (_TemperatureMixin below).
+device by the *_ls variants of the same entry points, which also return its gradient (_TemperatureMixin below), and `queue_size=Q`
+(not in the reference): the normalised embeddings of the last steps are kept in a ring of Q rows on the device and serve as extra
+constant columns of the softmax in `fused` (egv_egonce_queue_fwd_bwd, csrc/egonce_queue.hip); the ring is no part of state_dict(),
+so a resumed run refills its queue in Q / n steps.
 SigmoidLoss / EgoSigmoidLoss (not in the reference) are the pairwise sigmoid (SigLIP) counterparts of the two softmax losses, with a
 learnable logit scale AND bias (_SigmoidMixin): `forward` over egv_sigmoid_from_sim, `fused` over egv_sigmoid_head_fwd_bwd
 (csrc/sigmoid_head.hip: one tile walk per direction for any n up to 65 536).
@@ -90,10 +93,13 @@ class _LogitScaleMixin:
 class _TemperatureMixin(_LogitScaleMixin):
     """temperature = 0.05 of the reference (model/loss.py:8-11,28-32), fixed -- or, `learnable_temperature=True`, CLIP's learnable
     logit scale: `self.logit_scale` = s = log(1 / tau), one fp32 parameter initialised to log(1 / temperature); the head kernels
-    read it on the device and return dL/ds.  Off (the default) the module has no parameter and makes the calls it always made."""
+    read it on the device and return dL/ds.  Off (the default) the module has no parameter and makes the calls it always made.
+    `queue_size=Q` (0: none): a ring of the last Q normalised embeddings as extra columns of `fused` in train() mode -- see _init_queue.
+    Its buffers are non-persistent: checkpoints (loss_state_dict) do not carry them and a resumed run refills its queue in Q / n steps."""
 
-    def _init_temperature(self, temperature, learnable_temperature, max_logit_scale):
+    def _init_temperature(self, temperature, learnable_temperature, max_logit_scale, queue_size=0):
         self.temperature = temperature
+        self._init_queue(queue_size)
         self._init_clamp(learnable_temperature, max_logit_scale)
         if self.learnable_temperature:
             if not temperature > 0:
@@ -111,8 +117,73 @@ class _TemperatureMixin(_LogitScaleMixin):
             return (loss, dx, *map(_over_world, dls))
         return _KernelLossFn.apply(call, x, *self._scale())
 
+    # ---- the queue of past embeddings (`queue_size=Q`, a multiple of 64 in [64, 65 536]; 0: none, the module is what it always was)
+    # In train() mode `fused` runs the rectangular head of csrc/egonce_queue.hip for EVERY n <= Q: the batch against itself and
+    # against the valid slots of the ring -- extra negatives and, for EgoNCE, extra positives (a queued clip that shares a noun and
+    # a verb with an anchor), constants that get no gradient -- and then enqueues the batch, unless the loss is not finite.  Every
+    # rank runs the head on the same gathered batch, so every rank enqueues the same rows and nothing is exchanged.  In eval() mode
+    # `fused` is the plain head and nothing is enqueued.  The ring is allocated by the first such call (it needs D, the noun / verb
+    # widths and the device) as NON-PERSISTENT buffers: state_dict() and the checkpoint's loss_state_dict do not change, and a
+    # resumed run refills its queue in Q / n steps.
+    def _init_queue(self, queue_size):
+        if isinstance(queue_size, bool) or not isinstance(queue_size, int) or \
+                (queue_size != 0 and not loss_ops.egonce_queue_size_ok(queue_size)):
+            raise ValueError("queue_size must be 0 or a multiple of 64 in [%d, %d], got %r"
+                             % (loss_ops.EGONCE_QUEUE_MIN, loss_ops.EGONCE_QUEUE_MAX, queue_size))
+        self.queue_size = queue_size
+        self._queue = None
+
+    _QUEUE_BUFFERS = ("text", "video", "words", "state")
+
+    def _ring(self):
+        "the ring, if one is allocated, on the module's current buffers (a module.to(...) replaces them)"
+        if self._queue is not None:
+            for name in self._QUEUE_BUFFERS:
+                setattr(self._queue, name, getattr(self, "queue_" + name))
+        return self._queue
+
+    def _queue_for(self, text, noun, verb):
+        "the ring, allocated on first use; its tensors are the module's buffers queue_text / _video / _words / _state"
+        if self._queue is None:
+            dn, dv = loss_ops._nv_widths(noun, verb)
+            self._queue = loss_ops.EgonceQueue(self.queue_size, text.shape[1], dn, dv, text.device)
+            for name in self._QUEUE_BUFFERS:
+                self.register_buffer("queue_" + name, getattr(self._queue, name), persistent=False)
+        return self._ring()
+
+    def reset_queue(self):
+        "empty the ring (head = filled = 0); the next train-mode `fused` sees the batch alone"
+        if self._ring() is not None:
+            self._queue.reset()
+        return self
+
+    def queue_filled(self):
+        "valid rows of the ring, read back from the device (synchronises: logs and tests); 0 before the first train-mode `fused`"
+        return 0 if self._ring() is None else self._queue.filled()
+
+    def _refuse_matrix_path(self):
+        if self.queue_size and self.training:
+            raise ValueError("a loss with queue_size > 0 in train() mode takes the embeddings, not a similarity matrix: call "
+                             "`fused` (egoclip_head_loss: fused_head=True, D <= 256, D % 4 == 0)")
+
+    def _fused_queue(self, text, video, noun, verb, use_noun, use_verb):
+        "an autograd node over egv_egonce_queue_fwd_bwd, followed by egv_egonce_queue_push on the same stream"
+        noun, verb = _f32(noun), _f32(verb)
+        queue = self._queue_for(text, noun, verb)
+
+        def call(text, video, logit_scale=None):
+            loss, dt, dv, *dls, work = loss_ops.egonce_queue_fwd_bwd(text.contiguous(), video.contiguous(), noun, verb,
+                                                                     self.temperature, queue, use_noun=use_noun,
+                                                                     use_verb=use_verb, logit_scale=logit_scale)
+            loss_ops.egonce_queue_push(work, loss, text.shape[0], queue)
+            return (loss, dt, dv, *map(_over_world, dls))
+        return _KernelLossFn.apply(call, text, video, *self._scale())
+
     def _fused(self, text, video, noun, verb, use_noun, use_verb):
         "an autograd node over egv_egonce_fwd_bwd / egv_egonce_long_fwd_bwd (learnable: their _ls variants)"
+        if self.queue_size and self.training:
+            return self._fused_queue(text, video, noun, verb, use_noun, use_verb)
+
         def call(text, video, logit_scale=None):
             loss, _, dt, dv, *dls = loss_ops.egonce_fwd_bwd(text.contiguous(), video.contiguous(), _f32(noun), _f32(verb),
                                                             self.temperature, use_noun=use_noun, use_verb=use_verb,
@@ -122,12 +193,13 @@ class _TemperatureMixin(_LogitScaleMixin):
 
 
 class NormSoftmaxLoss(_TemperatureMixin, nn.Module):
-    def __init__(self, temperature=0.05, learnable_temperature=False, max_logit_scale=math.log(100)):
+    def __init__(self, temperature=0.05, learnable_temperature=False, max_logit_scale=math.log(100), queue_size=0):
         super().__init__()
-        self._init_temperature(temperature, learnable_temperature, max_logit_scale)
+        self._init_temperature(temperature, learnable_temperature, max_logit_scale, queue_size)
 
     def forward(self, x):
         "x: similarity matrix N x N in [-1, 1] (model/loss.py:13-25)"
+        self._refuse_matrix_path()
         return self._from_sim(x, None, None, True, True)
 
     def fused(self, text_embeds, video_embeds):
@@ -135,13 +207,15 @@ class NormSoftmaxLoss(_TemperatureMixin, nn.Module):
 
 
 class EgoNCE(_TemperatureMixin, nn.Module):
-    def __init__(self, temperature=0.05, noun=True, verb=True, learnable_temperature=False, max_logit_scale=math.log(100)):
+    def __init__(self, temperature=0.05, noun=True, verb=True, learnable_temperature=False, max_logit_scale=math.log(100),
+                 queue_size=0):
         super().__init__()
         self.noun = noun
         self.verb = verb
-        self._init_temperature(temperature, learnable_temperature, max_logit_scale)
+        self._init_temperature(temperature, learnable_temperature, max_logit_scale, queue_size)
 
     def forward(self, x, mask_v, mask_n):
+        self._refuse_matrix_path()
         # noun=False, verb=False falls into the reference's else-branch (mask_v), model/loss.py:40-41
         return self._from_sim(x, mask_v, mask_n, self.noun, self.verb or not self.noun)
 

@@ -76,6 +76,8 @@ def egoclip_head_loss(loss_fn, text_embeds, video_embeds, n_embeds, v_embeds, fu
     if fused_head and hasattr(loss_fn, 'fused') and n <= 65536 and D <= 256 and D % 4 == 0:
         return loss_fn.fused(text_embeds, video_embeds, n_embeds, v_embeds) if is_ego \
             else loss_fn.fused(text_embeds, video_embeds)
+    if getattr(loss_fn, 'queue_size', 0):
+        loss_fn._refuse_matrix_path()           # a queue in train() mode lives in `fused` only: a ValueError that says so
     output = sim_matrix(text_embeds, video_embeds)                          # :130
     if is_ego:
         sim_v = sim_matrix(v_embeds, v_embeds)                              # :133
@@ -227,6 +229,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 self.writer.add_scalar(f'Loss_training/loss_{dl_idx}', float(loss), (epoch - 1) * total + current)   # :143-148
                 if getattr(getattr(self, 'loss', None), 'learnable_temperature', False):   # float(loss) has just synchronised: the read-back is free
                     self.writer.add_scalar(f'Loss_training/temperature_{dl_idx}', self.loss.current_temperature(), (epoch - 1) * total + current)
+                if getattr(getattr(self, 'loss', None), 'queue_size', 0):                   # a loss with a queue of past embeddings: its valid rows
+                    self.writer.add_scalar(f'Loss_training/queue_filled_{dl_idx}', self.loss.queue_filled(), (epoch - 1) * total + current)
                 if hasattr(getattr(self, 'loss', None), 'current_bias'):                    # the sigmoid losses: their second parameter
                     self.writer.add_scalar(f'Loss_training/bias_{dl_idx}', self.loss.current_bias(), (epoch - 1) * total + current)
                 # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has

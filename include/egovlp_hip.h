@@ -601,6 +601,32 @@ int egv_egonce_long_fwd_bwd_ls(const float* text, const float* video, const floa
 int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const float* sim_n, int32_t n, const float* logit_scale,
                            int32_t use_noun, int32_t use_verb, float* loss, float* dx, float* d_logit_scale,
                            float* work /* n*n + 7n floats */, void* stream);
+/* EgoNCE / NormSoftmaxLoss with a QUEUE of past embeddings (csrc/egonce_queue.hip): the normalised rows of earlier steps are extra
+ * constant columns of both softmaxes -- more negatives and, for EgoNCE, more positives (a queued clip that shares a noun and a verb
+ * with an anchor) at no encoder cost.  With K = filled valid slots the head walks the rectangle of n batch rows against n + K columns
+ * per direction, 2 n (n + K) pairs, and forms no queue x queue term; K = 0 is egv_egonce_long_fwd_bwd's loss.  Formulas: the top of
+ * csrc/egonce_queue.hip.  The queue lives in caller-owned DEVICE buffers in the kernels' own layout, which egv_egonce_queue_layout
+ * returns (Dp floats per embedding row, W 32-bit words per noun / verb row; 1 on a bad D / dn / dv):
+ *   q_text, q_video [Q, Dp] fp32;  q_words [Q, W] uint32 (may be NULL when W == 0: no noun / verb vectors);
+ *   q_state int32 {head, filled}, both 0 for an empty queue.  Slots >= filled are never used, whatever they hold.
+ * Limits: 1 <= n <= 65536, Q % 64 == 0, 64 <= Q <= 65536, n <= Q, D <= 256, D % 4 == 0; anything else returns 1 before any launch.
+ * egv_egonce_queue_fwd_bwd reads the queue and `filled` on the device (no host read; the launch is sized by Q) and writes loss[1]
+ * and, when given, d_text AND d_video [n, D] (both or neither; NULL: the loss alone).  The temperature is `temperature` by value, or,
+ * with `logit_scale` non-NULL, 1 / tau = expf(*logit_scale) read on the device; then d_logit_scale[1] = dL/ds (the _ls convention,
+ * queue columns included) is written with the gradients and must be non-NULL with them.  Queue rows get no gradient.  Data contract
+ * of noun / verb as egv_egonce_long_fwd_bwd (a negative or NaN entry: NaN loss).  Deterministic: no float atomics.
+ * egv_egonce_queue_push, after the head on the same stream and with the same n, D, dn, dv, `work` and `loss`: copies the n normalised
+ * rows and packed words the head left in `work` into slots (head + i) mod Q, then head <- (head + n) mod Q and
+ * filled <- min(Q, filled + n) in a launch of its own.  If *loss is not finite nothing is copied and the state stays as it is. */
+int64_t egv_egonce_queue_work_floats(int32_t n, int32_t D, int32_t dn, int32_t dv, int32_t Q);
+int egv_egonce_queue_layout(int32_t D, int32_t dn, int32_t dv, int32_t* Dp, int32_t* W);
+int egv_egonce_queue_fwd_bwd(const float* text, const float* video, const float* noun, const float* verb,
+                             int32_t n, int32_t D, int32_t dn, int32_t dv,
+                             const float* q_text, const float* q_video, const uint32_t* q_words, int32_t Q, const int32_t* q_state,
+                             float temperature, const float* logit_scale, float eps, int32_t use_noun, int32_t use_verb,
+                             float* loss, float* d_text, float* d_video, float* d_logit_scale, float* work, void* stream);
+int egv_egonce_queue_push(const float* work, const float* loss, int32_t n, int32_t D, int32_t dn, int32_t dv,
+                          float* q_text, float* q_video, uint32_t* q_words, int32_t Q, int32_t* q_state, void* stream);
 /* Pairwise sigmoid head (SigLIP) with EgoNCE's positives, for ANY n in [1, 65536] (D <= 256, D % 4 == 0; noun and verb both given or
  * both NULL: mask = I, plain SigLIP), csrc/sigmoid_head.hip.  With tn / vn the normalised rows (sim_matrix's rule, `eps`),
  *   x_ij = tn_i . vn_j,  u_ij = exp(s) x_ij + b,  z_ij = +1 where m_ij else -1,  loss = (1 / n) sum_ij softplus(-z_ij u_ij),
