@@ -99,6 +99,28 @@ class Multi_BaseTrainer_dist:
         if getattr(config, 'resume', None) is not None:
             self._resume_checkpoint(config.resume)
 
+    # ---- weight average (egovlp_amd.ema.ModelEMA): `args.model_ema_decay` (absent, None or 0: off -- nothing below is ever called),
+    # `args.model_ema_warmup` (default True), `args.model_ema_eval` (default True: validate, and select model_best, under the average)
+    ema = None
+
+    def _model_ema(self):
+        """The run's ModelEMA, built at first use from the weights the model then holds; None when the option is off."""
+        decay = getattr(self.args, 'model_ema_decay', None)
+        if not decay:
+            return None
+        if self.ema is None:
+            from ..ema import ModelEMA
+            self.ema = ModelEMA(self.model, decay=float(decay), warmup=bool(getattr(self.args, 'model_ema_warmup', True)))
+        return self.ema
+
+    def _validate(self, epoch):
+        """`_valid_epoch`, under the averaged weights when the average is on and `args.model_ema_eval` says so."""
+        ema = self._model_ema()
+        if ema is None or not getattr(self.args, 'model_ema_eval', True):
+            return self._valid_epoch(epoch)
+        with ema.swapped():
+            return self._valid_epoch(epoch)
+
     @abstractmethod
     def _train_epoch(self, epoch):
         raise NotImplementedError
@@ -152,7 +174,7 @@ class Multi_BaseTrainer_dist:
         is_writer = self.args.rank == 0
         stale_epochs = 0
         if self.init_val:
-            self._valid_epoch(-1)
+            self._validate(-1)
         for epoch in range(self.start_epoch, self.epochs + 1):
             result = self._train_epoch(epoch)
             best = False
@@ -182,6 +204,13 @@ class Multi_BaseTrainer_dist:
         loss_sd = self.loss.state_dict() if hasattr(self.loss, 'state_dict') else {}
         if len(loss_sd) > 0:
             state['loss_state_dict'] = loss_sd
+        # the weight average (an extra key the reference's loader ignores); taken while NOT swapped: 'state_dict' above is the training
+        # weights, 'ema_state_dict'['shadow'] the averaged ones
+        ema = self._model_ema()
+        if ema is not None:
+            if ema.is_swapped():
+                raise RuntimeError("checkpoint while the model holds the averaged weights (inside ModelEMA.swapped())")
+            state['ema_state_dict'] = ema.state_dict()
         return state
 
     def _save_checkpoint(self, epoch, save_best=False):
@@ -252,4 +281,11 @@ class Multi_BaseTrainer_dist:
         ec = getattr(getattr(self.model, 'module', self.model), 'exec_ctx', None)
         if ec is not None and isinstance(ckpt.get('loss_scaler'), dict):
             ec.loss_scaler().load_state_dict(ckpt['loss_scaler'])
+        ema = self._model_ema()                 # built here from the weights just loaded
+        if ema is not None:
+            if isinstance(ckpt.get('ema_state_dict'), dict):
+                ema.load_state_dict(ckpt['ema_state_dict'])
+            else:
+                ema.reset()
+                self.logger.info("Checkpoint without 'ema_state_dict': the weight average starts from the loaded weights")
         self.logger.info("Checkpoint loaded. Resume training from epoch {}".format(self.start_epoch))

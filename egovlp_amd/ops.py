@@ -1323,6 +1323,63 @@ def grad_accumulate_multi(dst_list, src_list):
     check(_lib.lib().egv_grad_accumulate_multi(n, D, S, N, _stream(dst_list[0])), "egv_grad_accumulate_multi")
 
 
+class PairTables:
+    """The argument tables (addresses, sizes) of a FIXED list of tensor pairs for ema_update_multi / swap_multi, built once and reused
+    from call to call: `for_lists` hands back the same object as long as every data_ptr() and size is what it was built from."""
+    __slots__ = ("n", "A", "B", "N", "key")
+
+    def __init__(self, a_list, b_list, what):
+        if len(a_list) != len(b_list):
+            raise ValueError(what + ": two lists of equal length")
+        for a, b in zip(a_list, b_list):
+            if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
+                raise ValueError(what + ": pairs of dense contiguous fp32 tensors of equal size")
+        _need_cuda(*a_list, *b_list)
+        self.n, self.A, self.B, self.N = len(a_list), _addrs(a_list), _addrs(b_list), _numels(a_list)
+        self.key = self._key(a_list, b_list)
+
+    @staticmethod
+    def _key(a_list, b_list):
+        return [(a.data_ptr(), b.data_ptr(), a.numel(), b.numel()) for a, b in zip(a_list, b_list)]
+
+    @classmethod
+    def for_lists(cls, tables, a_list, b_list, what):
+        if tables is not None and tables.n == len(a_list) == len(b_list) and tables.key == cls._key(a_list, b_list):
+            return tables
+        return cls(a_list, b_list, what)
+
+
+def ema_decide(state, skip_flag, decay, warmup):
+    """The per-update decision of a weight average, one thread on the device (egv_ema_decide): `state` int32[8] {t, w, skipped, decay in
+    effect, ...}; `skip_flag`: None or a one-element fp32 device tensor whose non-zero value means "the optimizer step was not applied"
+    (then w = 0 and the skipped count advances); otherwise w = 1 - (warmup ? min(decay, (1 + t) / (10 + t)) : decay) and t advances."""
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError("ema_decide: 0 <= decay < 1")
+    _need_cuda(state, skip_flag)
+    check(_lib.lib().egv_ema_decide(_p(state), _p(skip_flag), float(decay), int(bool(warmup)), _stream(state)), "egv_ema_decide")
+
+
+def ema_update_multi(ema_list, p_list, state, tables=None):
+    """ema[i] += w * (p[i] - ema[i]) for every pair of the two lists in ONE egv_ema_update_multi call, w = state[1] read on the device
+    (0: the pass does nothing).  Dense contiguous fp32 tensors of equal sizes.  -> the PairTables of the lists: hand it back as `tables`
+    at the next call and the address / size tables are reused (rebuilt when a data_ptr() or a size differs)."""
+    tables = PairTables.for_lists(tables, ema_list, p_list, "ema_update_multi")
+    if tables.n == 0:
+        return tables
+    _need_cuda(state)
+    check(_lib.lib().egv_ema_update_multi(tables.n, tables.A, tables.B, tables.N, _p(state), _stream(ema_list[0])), "egv_ema_update_multi")
+    return tables
+
+
+def swap_multi(a_list, b_list, tables=None):
+    """a[i] <-> b[i], bit for bit, for every pair of the two lists in ONE egv_swap_multi call.  -> the PairTables, as ema_update_multi."""
+    tables = PairTables.for_lists(tables, a_list, b_list, "swap_multi")
+    if tables.n == 0:
+        return tables
+    check(_lib.lib().egv_swap_multi(tables.n, tables.A, tables.B, tables.N, _stream(a_list[0])), "egv_swap_multi")
+    return tables
+
+
 def loss_scale_update(state, hyper_out, lr, beta1, beta2, step, correct_bias, growth, backoff, interval, max_scale, advance):
     check(_lib.lib().egv_loss_scale_update(_p(state), _p(hyper_out), float(lr), float(beta1), float(beta2), int(step), int(correct_bias),
                                            float(growth), float(backoff), int(interval), float(max_scale), int(advance), _stream(state)),

@@ -106,12 +106,14 @@ class AdamW(torch.optim.Optimizer):
         self._clip_parts = 0
         self._norm_block = None         # int32[8] on the device: {norm, coef, nonfinite, clipped steps, non-finite steps, -, -, -}
         self._clip_hyper = None         # fp32[64, 4]: the hyper blocks of a step without a scaler
+        self._skip_hyper = None         # the first hyper block the last step() used (None: it had neither a scaler nor clipping)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, scaler=None):
         """`scaler` (LossScaler): the gradients carry its scale S -- scan them for inf / NaN, let the device decide whether the step is
         applied (and with which S next), un-scale inside the update.  No host synchronisation either way."""
         loss = closure() if closure is not None else None
+        self._skip_hyper = None
         groups = [(g, [p for p in g["params"] if p.grad is not None]) for g in self.param_groups]
         if self.max_grad_norm is not None:
             self._step_clipped(groups, grad_scale, scaler)
@@ -178,12 +180,22 @@ class AdamW(torch.optim.Optimizer):
                 lrs.append(group["lr"])
                 sizes.append(_step_size_f32(group["lr"], b1, b2, step, group["correct_bias"]))
             hypers.append(hyper)
+        self._skip_hyper = hypers[0] if hypers else None
         ops.grad_clip_update(self._clip_partials, self._clip_parts, self._norm_block, self.max_grad_norm, hypers,
                              state=scaler.state if scaler is not None else None, grad_scale=grad_scale, lrs=lrs, step_sizes=sizes)
         for hyper, (group, gi, ps, gs, ms, vs, step, tables) in zip(hypers, launches):
             b1, b2 = group["betas"]
             ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
                             group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)
+
+    def skip_flag(self):
+        """Was the last step() applied?  -> a one-element fp32 DEVICE view whose non-zero value means "not applied" (an overflow of the
+        fp16 backward, a non-finite gradient norm): the [3] element of the first hyper block that step used -- the scaler's block, or
+        the optimizer's own first block when clipping ran without a scaler; all blocks of one step carry the same value.  None when the
+        step had neither a scaler nor clipping: such a step is always applied.  An accessor only (no launch, no synchronisation); the
+        view is read on the stream, e.g. by `egovlp_amd.ema.ModelEMA.update`."""
+        h = self._skip_hyper
+        return None if h is None else h[3:4]
 
     # ---- host readbacks of the clip decision (synchronise: logs, tests, checkpoints); None while clipping is off / before a step ----
     def _norm_host(self):
@@ -280,6 +292,8 @@ class AdamW(torch.optim.Optimizer):
             hyper = sc.hyper_block(getattr(self, "_group_index", 0))
             ops.loss_scale_update(sc.state, hyper, group["lr"], b1, b2, step, group["correct_bias"], sc.growth_factor, sc.backoff_factor,
                                   sc.growth_interval, sc.max_scale, advance=self._scaler_first)
+            if self._scaler_first:
+                self._skip_hyper = hyper
             self._scaler_first = False
         ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
                         group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)

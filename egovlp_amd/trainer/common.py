@@ -212,6 +212,9 @@ class TrainerBase(Multi_BaseTrainer_dist):
         # step (:115-121).  Here the NEXT batch is prepared (negatives concatenated, captions tokenised), staged in pinned host
         # memory and copied on a private copy stream while the current step runs; the step only waits for the copy's event.
         feed = _prefetched(self._host_batches(), self.device)
+        # `args.model_ema_decay`: the weight average (egovlp_amd.ema.ModelEMA), built here from the weights on the device before the
+        # first step; None when the option is off, and then no line below does anything
+        ema = self._model_ema()
         for batch_idx, dl_idx, data in feed:
             if batch_idx is None:
                 break
@@ -222,6 +225,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 self._guard = PrecisionGuard(self.model, interval=int(getattr(self.args, 'precision_guard_interval', 1000)))
             self._guard.maybe_check(self._guard_batch(data))
             loss = self._step(data)
+            if ema is not None:
+                ema.update(self.optimizer)  # one decision + one multi-tensor pass per OPTIMIZER step (a cached step's chunks share it)
             total_loss[dl_idx] += loss      # stays on the device: no per-step .item() sync (reference :148,150)
             if self.writer is not None and self.args.rank == 0 and batch_idx % self.log_step == 0:
                 total = int(self.data_loader[dl_idx].n_samples / self.n_gpu) if hasattr(self.data_loader[dl_idx], 'n_samples') else 0
@@ -233,6 +238,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                     self.writer.add_scalar(f'Loss_training/queue_filled_{dl_idx}', self.loss.queue_filled(), (epoch - 1) * total + current)
                 if hasattr(getattr(self, 'loss', None), 'current_bias'):                    # the sigmoid losses: their second parameter
                     self.writer.add_scalar(f'Loss_training/bias_{dl_idx}', self.loss.current_bias(), (epoch - 1) * total + current)
+                if ema is not None:                                                         # the decay the average has just run with
+                    self.writer.add_scalar(f'Loss_training/ema_decay_{dl_idx}', ema.current_decay(), (epoch - 1) * total + current)
                 # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has
                 # just synchronised anyway (off: nothing is computed, nothing is read)
                 if getattr(self.optimizer, 'max_grad_norm', None) is not None:
@@ -243,7 +250,7 @@ class TrainerBase(Multi_BaseTrainer_dist):
             for dl_idx in range(len(self.data_loader)):
                 self.writer.add_scalar(f'Loss_training/loss_total_{dl_idx}', log[f'loss_{dl_idx}'], epoch - 1)
         if self.do_validation:                                              # :172-175
-            val_log = self._valid_epoch(epoch)
+            val_log = self._validate(epoch)             # `_valid_epoch`, under the averaged weights with args.model_ema_eval
             if self.args.rank == 0:
                 log.update(val_log)
         self._adjust_learning_rate(self.optimizer, epoch, self.args)        # :178

@@ -814,6 +814,26 @@ int egv_adamw_multi(int32_t count, float* const* p, const float* const* g, float
  * operand survives the sum, so egv_grad_nonfinite_multi on the accumulators sees the overflow of any chunk.                       */
 int egv_grad_accumulate_multi(int32_t count, float* const* dst, const float* const* src, const int64_t* numel, void* stream);
 
+/* ---- exponential moving average of the weights (no counterpart in the reference) ------------------------------------------
+ * A shadow copy e of every parameter p follows e += w * (p - e), w = 1 - decay, after each optimizer step that was APPLIED; for
+ * evaluation the two sets are exchanged in place.  Everything is decided on the device, nothing synchronises the host.
+ *   state (8 x 32 bits, DEVICE): [0] int32 t, updates applied so far; [1] float w, the weight of this update (0: the pass below does
+ *                                nothing); [2] int32 updates skipped so far; [3] float the decay in effect (logs); [4..7] zero, reserved.
+ * egv_ema_decide (one thread): skip_flag (DEVICE, may be NULL; the [3] element of the hyper_dev block of the optimizer step) non-zero:
+ * w = 0, state[2] += 1, t stays.  Otherwise, in double: d = warmup ? min(decay, (1 + t) / (10 + t)) : decay; w = (float)(1 - d);
+ * state[3] = (float)d; t += 1.  0 <= decay < 1; anything else, or a NULL state, is an invalid argument (nothing enqueued).
+ * egv_ema_update_multi: ema[i][j] = fmaf(w, p[i][j] - ema[i][j], ema[i][j]) with w = state[1] read on the device (w == 0: every block
+ * returns at once), for `count` tensors given as HOST arrays of device pointers / sizes.  One call for the whole model (the table is
+ * copied into kernel arguments 120 tensors at a time); 16-byte accesses where both bases of a pair are 16-byte aligned, scalar otherwise
+ * and for the last numel % 4 elements; every element has one writer.  12 B of HBM traffic per element.
+ * egv_swap_multi: a[i] <-> b[i], bit for bit (NaN payloads included), same list format; swapping twice is the identity.
+ * Both validate as egv_grad_accumulate_multi: count == 0 enqueues nothing, a size of 0 is skipped; a negative count or size, a NULL
+ * pointer of a non-empty tensor or a pair whose ranges overlap is an invalid argument, and then nothing is enqueued.               */
+int egv_ema_decide(int32_t* state, const float* skip_flag, float decay, int32_t warmup, void* stream);
+int egv_ema_update_multi(int32_t count, float* const* ema, const float* const* p, const int64_t* numel, const int32_t* state,
+                         void* stream);
+int egv_swap_multi(int32_t count, float* const* a, float* const* b, const int64_t* numel, void* stream);
+
 /* ---- dynamic loss scale (the fp16 backward) ---------------------------------------------------------------
  * The reference back-propagates in fp32 (trainer/trainer_egoclip.py:139-141); here the backward GEMMs of the video blocks can run on
  * fp16 operands, whose range needs the gradients scaled: the loss is multiplied by S before backward() and AdamW divides by it.
