@@ -160,6 +160,10 @@ PROTOTYPES = {
     "egv_ema_decide": (i32, [c_p, c_p, f32, i32, c_p]),
     "egv_ema_update_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_swap_multi": (i32, [i32, c_p, c_p, c_p, c_p]),
+    "egv_lamb_parts": (i32, [i32, c_p]),
+    "egv_lamb_stage1_multi": (i32, [i32, c_p, c_p, c_p, c_p, c_p, f32, f32, f32, f32, f32, i32, i32, f32, c_p, c_p, i32, c_p]),
+    "egv_lamb_ratio": (i32, [i32, c_p, c_p, i32, i32, i32, c_p, c_p, c_p]),
+    "egv_lamb_stage2_multi": (i32, [i32, c_p, c_p, c_p, c_p, f32, f32, f32, f32, f32, i32, i32, c_p, c_p, c_p]),
     "egv_grad_pack_bf16": (i32, [i32, c_p, c_p, c_p, c_p, f32, c_p]),
     "egv_grad_unpack_bf16": (i32, [i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_slice_sum_bf16": (i32, [c_p, i32, i64, c_p, c_p]),

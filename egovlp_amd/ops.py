@@ -1447,6 +1447,83 @@ def adamw_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step
                                      float(grad_scale), _p(hyper_dev), _stream(params[0])), "egv_adamw_multi")
 
 
+# ------------------------------------------------------------------------------------------------------------ LAMB (csrc/lamb.hip)
+LAMB_CHUNK = 16384      # elements per block of the two element-wise stages = per pair of partials
+
+
+def lamb_parts(tensors):
+    """How many partial PAIRS lamb_stage1_multi writes for this list: one per 16 384-element piece of a tensor.  Counted here from the
+    sizes; egv_lamb_parts is asked as a check."""
+    parts = sum((t.numel() + LAMB_CHUNK - 1) // LAMB_CHUNK for t in tensors)
+    c = int(_lib.lib().egv_lamb_parts(len(tensors), _numels(tensors)))
+    if c < 0 or parts > 2 ** 31 - 1:
+        raise ValueError("lamb_parts: the list is beyond 2^31 - 1 pieces")
+    if c != 0 and c != parts:
+        raise _lib.EgovlpHipError("egv_lamb_parts answers %d pieces, the sizes say %d" % (c, parts))
+    return parts
+
+
+def lamb_tables(params, ms, vs):
+    """The argument tables of the three LAMB calls that do not change from step to step: (P, M, V, N, pieces)."""
+    return _addrs(params), _addrs(ms), _addrs(vs), _numels(params), lamb_parts(params)
+
+
+def _lamb_check(params, partials, ratios, parts):
+    if partials.dtype != torch.float32 or ratios.dtype != torch.float32 or not (partials.is_contiguous() and ratios.is_contiguous()):
+        raise ValueError("LAMB: `partials` and `ratios` are contiguous fp32 tensors")
+    if partials.numel() < 2 * parts or ratios.numel() < len(params):
+        raise ValueError("LAMB: `partials` holds a pair per piece (lamb_parts) and `ratios` one float per tensor")
+    _need_cuda(*params, partials, ratios)
+
+
+def lamb_stage1_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale, partials,
+                      hyper_dev=None, tables=None):
+    """Stage 1 of a LAMB update (egv_lamb_stage1_multi): the moments advance, sum(p^2) and sum(u^2) of every 16 384-element piece go
+    into `partials` (fp32, a pair per piece).  Parameters and gradients are only read.  -> the tables (lamb_tables)."""
+    tables = tables if tables is not None else lamb_tables(params, ms, vs)
+    P, M_, V, N, parts = tables
+    if len(params) == 0:
+        return tables
+    G = _addrs(grads)
+    check(_lib.lib().egv_lamb_stage1_multi(len(params), P, G, M_, V, N, float(lr), float(beta1), float(beta2), float(eps),
+                                           float(weight_decay), int(step), int(correct_bias), float(grad_scale), _p(hyper_dev),
+                                           _p(partials), partials.numel() // 2, _stream(params[0])), "egv_lamb_stage1_multi")
+    return tables
+
+
+def lamb_ratio(params, partials, ratios, adapt, trust_clip, hyper_dev=None, tables=None):
+    """The trust ratio of every tensor from stage 1's partials (egv_lamb_ratio): ratios[i] = ||p_i|| / ||u_i||, or 1 (not `adapt`, a
+    zero norm, an empty tensor), capped at 1 with `trust_clip`."""
+    if len(params) == 0:
+        return
+    N, parts = (tables[3], tables[4]) if tables is not None else (_numels(params), lamb_parts(params))
+    check(_lib.lib().egv_lamb_ratio(len(params), N, _p(partials), parts, int(bool(adapt)), int(bool(trust_clip)), _p(hyper_dev),
+                                    _p(ratios), _stream(params[0])), "egv_lamb_ratio")
+
+
+def lamb_stage2_multi(params, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias, ratios, hyper_dev=None, tables=None):
+    """Stage 2 (egv_lamb_stage2_multi): p -= lr * ratios[i] * u, u recomputed from p and the new moments."""
+    if len(params) == 0:
+        return
+    P, M_, V, N, _ = tables if tables is not None else lamb_tables(params, ms, vs)
+    check(_lib.lib().egv_lamb_stage2_multi(len(params), P, M_, V, N, float(lr), float(beta1), float(beta2), float(eps),
+                                           float(weight_decay), int(step), int(correct_bias), _p(hyper_dev), _p(ratios),
+                                           _stream(params[0])), "egv_lamb_stage2_multi")
+
+
+def lamb_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale, partials, ratios,
+               adapt, trust_clip, hyper_dev=None, tables=None):
+    """One LAMB update of a list of tensors: stage 1, ratio, stage 2 on the current stream.  -> the tables, reusable while the
+    parameters and moments stay where they are."""
+    tables = tables if tables is not None else lamb_tables(params, ms, vs)
+    _lamb_check(params, partials, ratios, tables[4])
+    lamb_stage1_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias, grad_scale, partials,
+                      hyper_dev=hyper_dev, tables=tables)
+    lamb_ratio(params, partials, ratios, adapt, trust_clip, hyper_dev=hyper_dev, tables=tables)
+    lamb_stage2_multi(params, ms, vs, lr, beta1, beta2, eps, weight_decay, step, correct_bias, ratios, hyper_dev=hyper_dev, tables=tables)
+    return tables
+
+
 # ------------------------------------------------------------------------------------------ the CLS tail's pieces (csrc/cls_tail.hip)
 # egv_block_fwd / _bwd launch these from C for the tower's last block (egv_block_geom.train bit 1); the wrappers serve tests and tools.
 def cls_linear_fwd(x, W, bias=None, *, rows=None, ldx=None, gelu=False, want_z=False, residual=None, ldr=None):

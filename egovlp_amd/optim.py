@@ -3,7 +3,8 @@
 The reference builds its optimizer with `config.initialize('optimizer', transformers, params)`
 (run/train_egoclip.py:72-73) -> `transformers.AdamW(lr=3e-5)` with that version's defaults
 betas (0.9, 0.999), eps 1e-6, weight_decay 0.0, correct_bias True.  transformers 5.x no longer
-ships AdamW, so this module is what `optimizer.type == "AdamW"` resolves to.
+ships AdamW, so this module is what `optimizer.type == "AdamW"` resolves to.  `LAMB` (no counterpart in the reference) is AdamW's
+step with another update: layer-wise adaptive rates for large effective batches, on the three kernels of csrc/lamb.hip.
 
 (An `overlap_backward()` mode -- updates enqueued from grad-ready hooks under the rest of backward -- was built in round 2,
 measured 1.8 % SLOWER (the persistent GEMM workgroups own every CU, a 5-GB HBM stream squeezed into their tails only delays
@@ -184,9 +185,7 @@ class AdamW(torch.optim.Optimizer):
         ops.grad_clip_update(self._clip_partials, self._clip_parts, self._norm_block, self.max_grad_norm, hypers,
                              state=scaler.state if scaler is not None else None, grad_scale=grad_scale, lrs=lrs, step_sizes=sizes)
         for hyper, (group, gi, ps, gs, ms, vs, step, tables) in zip(hypers, launches):
-            b1, b2 = group["betas"]
-            ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
-                            group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)
+            self._apply(group, ps, gs, ms, vs, step, grad_scale, hyper, tables)
 
     def skip_flag(self):
         """Was the last step() applied?  -> a one-element fp32 DEVICE view whose non-zero value means "not applied" (an overflow of the
@@ -275,7 +274,7 @@ class AdamW(torch.optim.Optimizer):
             ps.append(p); gs.append(p.grad); ms.append(st["exp_avg"]); vs.append(st["exp_avg_sq"]); sts.append(st)
         self._launch(group, ps, gs, ms, vs, step, grad_scale)
         if uniform and ps:
-            self._plans[id(group)] = (list(ps), sts, list(ms), list(vs), ops.adamw_tables(ps, ms, vs), [p.data_ptr() for p in ps])
+            self._plans[id(group)] = (list(ps), sts, list(ms), list(vs), self._tables(ps, ms, vs), [p.data_ptr() for p in ps])
 
     def _launch(self, group, ps, gs, ms, vs, step, grad_scale, tables=None):
         if not ps:
@@ -295,8 +294,88 @@ class AdamW(torch.optim.Optimizer):
             if self._scaler_first:
                 self._skip_hyper = hyper
             self._scaler_first = False
+        self._apply(group, ps, gs, ms, vs, step, grad_scale, hyper, tables)
+
+    # ---- the update of one launch group: the one thing a subclass with another rule (LAMB) replaces ----
+    def _apply(self, group, ps, gs, ms, vs, step, grad_scale, hyper, tables):
+        b1, b2 = group["betas"]
         ops.adamw_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
                         group["correct_bias"], grad_scale, hyper_dev=hyper, tables=tables)
+
+    def _tables(self, ps, ms, vs):
+        return ops.adamw_tables(ps, ms, vs)
+
+
+class LAMB(AdamW):
+    """Layer-wise adaptive moments (You et al. 2020, "Large Batch Optimization for Deep Learning") on three kernels of csrc/lamb.hip.
+    Per tensor, with the step's g' = g * (1 / S) * coef (loss scale and global-norm clip, both from the hyper block, as in AdamW):
+
+        m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  c = sqrt(1 - b2^t) / (1 - b1^t)   (t: steps APPLIED; 1 without correct_bias)
+        u = c * m / (sqrt(v) + eps) + wd * p
+        r = ||p|| / ||u||  if adapt and ||p|| > 0 and ||u|| > 0 else 1;   r = min(r, 1) if trust_clip;   p = p - lr * r * u
+
+    `adapt` is `weight_decay != 0 or always_adapt`, the rule of timm's Lamb and apex's FusedLAMB (use_nvlamb): biases, LayerNorm
+    weights and loss parameters in weight_decay = 0 groups take plain Adam steps.  An all-zero tensor (the zero-initialised time
+    attention, temporal_embed under 'zeros') has r = 1 and moves at lr.  lr == 0: the moments advance, p stays bit-identical.
+    ONE DEVIATION from timm and apex, which bias-correct m and v separately (eps INSIDE the correction): eps stays OUTSIDE, so u is,
+    per unit lr, the direction this module's AdamW applies, and c = step_size / lr comes from the hyper block {lr, step_size,
+    (1 / S) * coef, skip} that egv_loss_scale_update / egv_grad_clip_update already write.
+    Everything before the update is AdamW's, inherited: the non-finite scan, the clip decision, the scaler's hyper blocks, launch
+    groups by step count, the steady-state plans, `skip_flag()`, `grad_norm()` and the other readbacks.  A step that is not applied
+    leaves parameters, moments and ratios bit-identical.  Defaults are timm's; `trust_clip` and `always_adapt` are group defaults and
+    travel in `state_dict()` with the groups.  `trust_ratios()` reads the last step's ratios back (it synchronises)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, correct_bias=True, max_grad_norm=1.0,
+                 trust_clip=False, always_adapt=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias,
+                         max_grad_norm=max_grad_norm)
+        self.defaults.update(trust_clip=bool(trust_clip), always_adapt=bool(always_adapt))
+        for group in self.param_groups:
+            group.setdefault("trust_clip", bool(trust_clip))
+            group.setdefault("always_adapt", bool(always_adapt))
+        self._lamb_numels = None        # sizes of the gradient list the two buffers below were sized for
+        self._lamb_partials = None      # fp32[2 * pieces]: {sum p^2, sum u^2} of every 16 384-element piece, in list order
+        self._lamb_ratios = None        # fp32[tensors]: the trust ratio of every parameter that had a gradient, in list order
+        self._lamb_cursor = (0, 0)      # (tensors, pieces) the launch groups of the step in progress have taken
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0, scaler=None):
+        loss = None
+        if closure is not None:         # the buffers are sized from the gradients: the closure runs first
+            with torch.enable_grad():
+                loss = closure()
+        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+        numels = [g.numel() for g in grads]
+        if grads and (numels != self._lamb_numels or self._lamb_ratios.device != grads[0].device):
+            # as _clip_partials: sized once, re-sized when the parameter list changes.  The ratios start at 1
+            parts = sum((n + ops.LAMB_CHUNK - 1) // ops.LAMB_CHUNK for n in numels)
+            self._lamb_partials = torch.zeros(2 * max(parts, 1), dtype=torch.float32, device=grads[0].device)
+            self._lamb_ratios = torch.ones(len(numels), dtype=torch.float32, device=grads[0].device)
+            self._lamb_numels = numels
+        self._lamb_cursor = (0, 0)
+        super().step(grad_scale=grad_scale, scaler=scaler)
+        return loss
+
+    def _apply(self, group, ps, gs, ms, vs, step, grad_scale, hyper, tables):
+        b1, b2 = group["betas"]
+        tables = tables if tables is not None else ops.lamb_tables(ps, ms, vs)
+        t0, p0 = self._lamb_cursor
+        parts = tables[4]
+        self._lamb_cursor = (t0 + len(ps), p0 + parts)
+        if t0 + len(ps) > self._lamb_ratios.numel() or 2 * (p0 + parts) > self._lamb_partials.numel():
+            raise RuntimeError("LAMB (HIP): the launch groups of a step exceed the gradient list it was sized for")
+        ops.lamb_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"], group["weight_decay"], step, group["correct_bias"],
+                       grad_scale, self._lamb_partials[2 * p0:2 * (p0 + max(parts, 1))], self._lamb_ratios[t0:t0 + len(ps)],
+                       adapt=(group["weight_decay"] != 0 or group["always_adapt"]), trust_clip=group["trust_clip"],
+                       hyper_dev=hyper, tables=tables)
+
+    def _tables(self, ps, ms, vs):
+        return ops.lamb_tables(ps, ms, vs)
+
+    def trust_ratios(self):
+        """The trust ratios of the last applied step, one per parameter that had a gradient, in the order of the parameter groups:
+        a CPU fp32 tensor (synchronises: logs, tests); None before the first step."""
+        return None if self._lamb_ratios is None else self._lamb_ratios.cpu()
 
 
 def _check_max_grad_norm(v):

@@ -245,6 +245,11 @@ class TrainerBase(Multi_BaseTrainer_dist):
                 if getattr(self.optimizer, 'max_grad_norm', None) is not None:
                     self.writer.add_scalar(f'Grad_training/grad_norm_{dl_idx}', self.optimizer.grad_norm(), (epoch - 1) * total + current)
                     self.writer.add_scalar(f'Grad_training/clip_coef_{dl_idx}', self.optimizer.clip_coef(), (epoch - 1) * total + current)
+                # LAMB: the smallest and the largest trust ratio of the step, next to the norm (the same free read-back)
+                ratios = self.optimizer.trust_ratios() if hasattr(self.optimizer, 'trust_ratios') else None
+                if ratios is not None and ratios.numel():
+                    self.writer.add_scalar(f'Grad_training/trust_ratio_min_{dl_idx}', float(ratios.min()), (epoch - 1) * total + current)
+                    self.writer.add_scalar(f'Grad_training/trust_ratio_max_{dl_idx}', float(ratios.max()), (epoch - 1) * total + current)
         log = {f'loss_{dl_idx}': float(total_loss[dl_idx]) / self.len_epoch for dl_idx in range(len(self.data_loader))}   # :162-164
         if self.writer is not None and self.args.rank == 0:
             for dl_idx in range(len(self.data_loader)):

@@ -881,6 +881,38 @@ int egv_grad_clip_update(const float* partials, int32_t parts, const int32_t* st
                          int32_t n_hyper, float* const* hyper, const float* lr, const float* step_size, int32_t* norm_block,
                          void* stream);
 
+/* ---- LAMB: layer-wise adaptive rates (You et al. 2020; no counterpart in the reference) ----------------------------------
+ * Per tensor, with ge = g * grad_scale:  m = b1 m + (1 - b1) ge;  v = b2 v + (1 - b2) ge^2;  u = c * m / (sqrt(v) + eps) + wd * p;
+ * r = ||p|| / ||u|| if (adapt and ||p|| > 0 and ||u|| > 0) else 1;  r = min(r, 1) if trust_clip;  p = p - lr * r * u.
+ * c = sqrt(1 - b2^t) / (1 - b1^t) (1 when correct_bias == 0): eps stays OUTSIDE the correction, so u is, per unit lr, the direction
+ * egv_adamw_multi applies -- timm's Lamb and apex's FusedLAMB correct m and v separately.  Three calls on one stream, all taking
+ * `count` tensors as HOST arrays of device pointers / sizes (fp32, any 4-byte-aligned base; 16-byte accesses where every base of a
+ * tensor is 16-byte aligned) and the SAME list in the SAME order:
+ * egv_lamb_parts: the number of partial PAIRS stage 1 writes: one per 16 384-element piece of a tensor, empty tensors take none;
+ * -1 for a negative count / size or a list beyond 2^31 - 1 pieces.
+ * egv_lamb_stage1_multi: writes m and v, reduces p^2 and u^2 of every piece in a fixed order (no floating-point atomics) into
+ * partials[2 * piece], partials[2 * piece + 1]; pieces are numbered through the list in order.  p and g are only read.
+ * parts_capacity: pairs behind `partials`, at least egv_lamb_parts.
+ * egv_lamb_ratio: one workgroup per tensor sums its run of pairs in double, in a fixed order, and stores r into ratios[i] (fp32,
+ * `count` floats, i = the tensor's index in the list; an empty tensor gets 1 and shifts nothing).  parts must equal egv_lamb_parts.
+ * egv_lamb_stage2_multi: recomputes u from p and the new m, v with stage 1's expression; p = fmaf(-(lr * ratios[i]), u, p).
+ * lr == 0: p is not written (the moments of stage 1 advanced).
+ * hyper_dev (DEVICE, may be NULL): {lr, step_size, grad_scale, skip} as for egv_adamw_multi; the kernels then take lr and grad_scale
+ * from it and c = step_size / lr (the host's c when lr == 0), and with skip != 0 all three return before any store: parameters,
+ * moments and ratios stay bit-identical.  Everything is validated before the first launch: a negative count / size, step < 1, a NULL
+ * pointer of a non-empty tensor or too small a capacity is an invalid argument and enqueues nothing.
+ * HBM traffic: 16 B + 8 B (stage 1) + 12 B + 4 B (stage 2) = 40 B per parameter; egv_adamw_multi moves 28 B.                     */
+int egv_lamb_parts(int32_t count, const int64_t* numel);
+int egv_lamb_stage1_multi(int32_t count, const float* const* p, const float* const* g, float* const* m, float* const* v,
+                          const int64_t* numel, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                          int32_t correct_bias, float grad_scale, const float* hyper_dev, float* partials, int32_t parts_capacity,
+                          void* stream);
+int egv_lamb_ratio(int32_t count, const int64_t* numel, const float* partials, int32_t parts, int32_t adapt, int32_t trust_clip,
+                   const float* hyper_dev, float* ratios, void* stream);
+int egv_lamb_stage2_multi(int32_t count, float* const* p, const float* const* m, const float* const* v, const int64_t* numel,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, int32_t correct_bias,
+                          const float* hyper_dev, const float* ratios, void* stream);
+
 /* ---- misc -----------------------------------------------------------------------------------------------
  * gather rows: out[r,:] = x[idx_stride * r * ld ...] helper for CLS-row extraction is done with strides in
  * egv_layernorm_fwd (ldx = S*D, rows = B).  relu on fp32 -> split planes: */
