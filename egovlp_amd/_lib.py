@@ -107,6 +107,8 @@ PROTOTYPES = {
     "egv_patch_gather_u8_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
     "egv_patch_gather_u8_aug_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
     "egv_patch_gather_u8_aug_color_sel": (i32, [c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
+    "egv_patch_gather_mix": (i32, [c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
+    "egv_patch_gather_u8_aug_mix": (i32, [c_p, i32, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, c_p, i64, c_p]),
     "egv_assemble_tokens_sel": (i32, [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, c_p, c_p]),
     "egv_assemble_tokens_bwd_sel": (i32, [c_p, c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
     "egv_divided_attn_fwd": (i32, [c_p, c_p, i32, i32, i32, i32, i32, i32, c_p, c_p, c_p, c_p, c_p]),
@@ -146,6 +148,9 @@ PROTOTYPES = {
     "egv_maxmargin_head_work_floats": (i64, [i32, i32]),
     "egv_cls_head_fwd": (i32, [c_p, i64, c_p, c_p, i32, i32, i32, c_p, i64, c_p]),
     "egv_cls_head_loss_bwd": (i32, [c_p, i64, i32, i32, i32, i32, i32, i32, c_p, i64, c_p, i32, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p]),
+    "egv_cls_head_loss_bwd_soft": (i32, [c_p, i64, i32, i32, i32, i32, i32, i32, f32, i32, i32, c_p, i64, c_p, i32, c_p, c_p, c_p, c_p, i64, c_p,
+                                         c_p, c_p]),
+    "egv_cross_entropy_soft_fwd_bwd": (i32, [c_p, i64, c_p, c_p, c_p, f32, i32, i32, i64, c_p, c_p, i64, c_p]),
     "egv_cls_eval_update": (i32, [c_p, i64, i32, i32, i32, i32, i32, i32, i32, i32, c_p, c_p]),
     "egv_dual_softmax": (i32, [c_p, i32, i32, f32, c_p, c_p, c_p]),
     "egv_rank_scores": (i32, [c_p, i64, i32, c_p, i32, i64, i32, i32, i32, c_p, c_p, c_p, c_p]),

@@ -14,8 +14,11 @@
 //                                     cls_grad_kernel (B + C workgroups): workgroup r < B writes dfeats[r] = g_r W, workgroup B + c
 //                                     writes dW[c] = sum_r g_rc feats_r and db[c], with g = s (softmax - onehot) / n recomputed
 //                                     from the stored logsumexp for the local rows only
+//   egv_cls_head_loss_bwd_soft        the same two launches on soft targets (label smoothing, the partner's class and lam of a
+//                                     Mixup / CutMix step in two more columns of the block): cls_loss_soft_kernel, cls_grad_soft_kernel
 //   egv_cls_eval_update    1 launch   hits / keyframe errors of a gathered validation block added to four doubles on the device
-//   egv_cross_entropy_fwd_bwd         the API-compatible loss on given scores and int64 labels, fp32: at the end of the file
+//   egv_cross_entropy_fwd_bwd         the API-compatible loss on given scores and int64 labels, fp32: at the end of the file,
+//   egv_cross_entropy_soft_fwd_bwd    with its soft-target form behind it
 // Values are fp32 in memory; the sums (over K, over the classes, over the rows) are carried in fp64 registers -- at most a few
 // thousand terms per output, so the cost is nothing and every output is the correctly rounded fp32 of an essentially exact sum.
 // Deterministic: no atomics, every sum has a fixed order (a thread's terms by index, lane-xor trees, waves 0..3, rows ascending).
@@ -108,19 +111,40 @@ __device__ __forceinline__ double cls_g(const float* __restrict__ packed, long l
   return sc * (exp((double)x[c] - work[row]) - ((float)c == x[col_t] ? 1.0 : 0.0));
 }
 
+// The soft-target form of the head (label smoothing, Mixup / CutMix): the target distribution of row r is
+//   q_r = (1 - eps) (lam_r e(t_r) + (1 - lam_r) e(t2_r)) + eps / C
+// with t2 = column col_t2 (-1: t2 = t) and lam = column col_lam (-1: lam = 1) of the block.
+struct ClsSoft { int col_t2, col_lam; float eps; };
+
+__device__ __forceinline__ bool cls_target_ok(float tf, int C) { return tf >= 0.f && tf < (float)C && tf == floorf(tf); }
+
+// g_rc = (s / n) (softmax(x_r)_c - q_rc) for a local row r, from the stored logsumexp
+__device__ __forceinline__ double cls_g_soft(const float* __restrict__ packed, long ld, int col_t, const ClsSoft& sf, int C,
+                                             const double* __restrict__ work, double sc, int row, int c) {
+  const float* __restrict__ x = packed + (long)row * ld;
+  const float t = x[col_t], t2 = sf.col_t2 >= 0 ? x[sf.col_t2] : t;
+  const double lam = sf.col_lam >= 0 ? (double)x[sf.col_lam] : 1.0;
+  const double q = (1.0 - (double)sf.eps) * (lam * ((float)c == t ? 1.0 : 0.0) + (1.0 - lam) * ((float)c == t2 ? 1.0 : 0.0)) +
+                   (double)sf.eps / (double)C;
+  return sc * (exp((double)x[c] - work[row]) - q);
+}
+
 // workgroups [0, B): dfeats rows;  workgroups [B, B + C): one class each, dW row and db entry
-__global__ __launch_bounds__(256) void cls_grad_kernel(const float* __restrict__ packed, long ld, int n, int C, int col_t, int row0,
-                                                       int B, const float* __restrict__ feats, long ldf,
-                                                       const float* __restrict__ W, int K, const double* __restrict__ work,
-                                                       float* __restrict__ dW, float* __restrict__ db, float* __restrict__ dfeats,
-                                                       long ldd) {
+template <bool SOFT>
+__device__ __forceinline__ void cls_grad_body(const float* __restrict__ packed, long ld, int n, int C, int col_t, const ClsSoft& sf,
+                                              int row0, int B, const float* __restrict__ feats, long ldf, const float* __restrict__ W,
+                                              int K, const double* __restrict__ work, float* __restrict__ dW, float* __restrict__ db,
+                                              float* __restrict__ dfeats, long ldd) {
   __shared__ double g[CLS_MAX_B];
   const double sc = work[n];
   const int tid = threadIdx.x;
+  auto g_of = [&](int row, int c) {
+    return SOFT ? cls_g_soft(packed, ld, col_t, sf, C, work, sc, row, c) : cls_g(packed, ld, col_t, work, sc, row, c);
+  };
   if ((int)blockIdx.x < B) {
     if (!dfeats) return;
     const int r = blockIdx.x;
-    if (tid < C) g[tid] = cls_g(packed, ld, col_t, work, sc, row0 + r, tid);
+    if (tid < C) g[tid] = g_of(row0 + r, tid);
     __syncthreads();
     for (int k = tid; k < K; k += 256) {
       double a = 0.0;
@@ -129,7 +153,7 @@ __global__ __launch_bounds__(256) void cls_grad_kernel(const float* __restrict__
     }
   } else {
     const int c = blockIdx.x - B;
-    if (tid < B) g[tid] = cls_g(packed, ld, col_t, work, sc, row0 + tid, c);
+    if (tid < B) g[tid] = g_of(row0 + tid, c);
     __syncthreads();
     if (dW) {
       for (int k = tid; k < K; k += 256) {
@@ -143,6 +167,67 @@ __global__ __launch_bounds__(256) void cls_grad_kernel(const float* __restrict__
       for (int r = 0; r < B; ++r) a += g[r];
       db[c] = (float)a;
     }
+  }
+}
+
+__global__ __launch_bounds__(256) void cls_grad_kernel(const float* __restrict__ packed, long ld, int n, int C, int col_t, int row0,
+                                                       int B, const float* __restrict__ feats, long ldf,
+                                                       const float* __restrict__ W, int K, const double* __restrict__ work,
+                                                       float* __restrict__ dW, float* __restrict__ db, float* __restrict__ dfeats,
+                                                       long ldd) {
+  cls_grad_body<false>(packed, ld, n, C, col_t, ClsSoft{-1, -1, 0.f}, row0, B, feats, ldf, W, K, work, dW, db, dfeats, ldd);
+}
+
+__global__ __launch_bounds__(256) void cls_grad_soft_kernel(const float* __restrict__ packed, long ld, int n, int C, int col_t,
+                                                            const ClsSoft sf, int row0, int B, const float* __restrict__ feats, long ldf,
+                                                            const float* __restrict__ W, int K, const double* __restrict__ work,
+                                                            float* __restrict__ dW, float* __restrict__ db,
+                                                            float* __restrict__ dfeats, long ldd) {
+  cls_grad_body<true>(packed, ld, n, C, col_t, sf, row0, B, feats, ldf, W, K, work, dW, db, dfeats, ldd);
+}
+
+// cls_loss_kernel on soft targets: the row term is logsumexp(x_r) - sum_c q_rc x_rc
+//   = logsumexp(x_r) - (1 - eps) (lam x_r[t] + (1 - lam) x_r[t2]) - (eps / C) sum_c x_rc;  a bad t OR t2 voids the loss
+__global__ __launch_bounds__(256) void cls_loss_soft_kernel(const float* __restrict__ packed, long ld, int n, int C, int col_t, int col_s,
+                                                            const ClsSoft sf, float* __restrict__ loss, int* __restrict__ pred,
+                                                            double* __restrict__ work) {
+  __shared__ double sh[2][4];
+  double ls = 0.0, ss = 0.0;
+  int bad = 0;
+  for (int r = threadIdx.x; r < n; r += 256) {
+    const float* __restrict__ x = packed + (long)r * ld;
+    float m;
+    const int am = row_argmax(x, C, m);
+    double e = 0.0, sx = 0.0;
+    for (int c = 0; c < C; ++c) {
+      e += exp((double)x[c] - (double)m);
+      sx += (double)x[c];
+    }
+    const double lse = (double)m + log(e);
+    const float tf = x[col_t], t2f = sf.col_t2 >= 0 ? x[sf.col_t2] : tf;
+    const double lam = sf.col_lam >= 0 ? (double)x[sf.col_lam] : 1.0;
+    if (cls_target_ok(tf, C) && cls_target_ok(t2f, C))
+      ls += lse - ((1.0 - (double)sf.eps) * (lam * (double)x[(int)tf] + (1.0 - lam) * (double)x[(int)t2f]) +
+                   (double)sf.eps / (double)C * sx);
+    else bad = 1;
+    ss += col_s >= 0 ? (double)x[col_s] : 1.0;
+    work[r] = lse;
+    if (pred) pred[r] = am;
+  }
+  bad = __syncthreads_or(bad);
+  ls = wave_sum_d(ls);
+  ss = wave_sum_d(ss);
+  if ((threadIdx.x & 63) == 0) {
+    sh[0][threadIdx.x >> 6] = ls;
+    sh[1][threadIdx.x >> 6] = ss;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double lsum = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+    const double s = (((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3]) / (double)n;
+    loss[0] = bad ? __int_as_float(0x7fc00000) : (float)(s * (lsum / (double)n));
+    work[n] = bad ? nan : s / (double)n;
   }
 }
 
@@ -237,6 +322,31 @@ extern "C" int egv_cls_head_loss_bwd(const float* packed, int64_t ld, int32_t n,
   return EGV_OK;
 }
 
+extern "C" int egv_cls_head_loss_bwd_soft(const float* packed, int64_t ld, int32_t n, int32_t C, int32_t col_target, int32_t col_state,
+                                          int32_t col_target2, int32_t col_lam, float label_smoothing, int32_t row0, int32_t B,
+                                          const float* feats, int64_t ldf, const float* W, int32_t K, float* loss, float* dW, float* db,
+                                          float* dfeats, int64_t ldd, int32_t* pred, double* work, void* stream) {
+  if (!packed || !loss || !work || n <= 0 || n > CLS_MAX_N || C <= 0 || C > CLS_MAX_C) return EGV_ERR_ARG;
+  if (!col_ok(col_target, C, ld) || (col_state >= 0 && (!col_ok(col_state, C, ld) || col_state == col_target))) return EGV_ERR_ARG;
+  if (col_target2 >= 0 && (!col_ok(col_target2, C, ld) || col_target2 == col_target || col_target2 == col_state)) return EGV_ERR_ARG;
+  if (col_lam >= 0 && (!col_ok(col_lam, C, ld) || col_lam == col_target || col_lam == col_state || col_lam == col_target2))
+    return EGV_ERR_ARG;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return EGV_ERR_ARG;
+  if (B <= 0 || B > CLS_MAX_B || row0 < 0 || (int64_t)row0 + B > n || K <= 0 || K > CLS_MAX_K || K % 4 != 0) return EGV_ERR_ARG;
+  const bool grads = dW || db || dfeats;
+  if (grads && ((dW && (!feats || ldf < K)) || (dfeats && (!W || ldd < K)))) return EGV_ERR_ARG;
+  const ClsSoft sf{col_target2 >= 0 ? col_target2 : -1, col_lam >= 0 ? col_lam : -1, label_smoothing};
+  hipStream_t s = (hipStream_t)stream;
+  EGV_LAUNCH(cls_loss_soft_kernel, dim3(1), dim3(256), 0, s, packed, (long)ld, n, C, col_target, col_state, sf, loss, pred, work);
+  EGV_CHECK_LAUNCH();
+  if (grads) {
+    EGV_LAUNCH(cls_grad_soft_kernel, dim3(B + C), dim3(256), 0, s, packed, (long)ld, n, C, col_target, sf, row0, B, feats, (long)ldf, W,
+               K, (const double*)work, dW, db, dfeats, (long)ldd);
+    EGV_CHECK_LAUNCH();
+  }
+  return EGV_OK;
+}
+
 extern "C" int egv_cls_eval_update(const float* packed, int64_t ld, int32_t n, int32_t C, int32_t col_target, int32_t col_state,
                                    int32_t col_fps, int32_t col_start, int32_t col_end, int32_t col_pnr, double* accum,
                                    void* stream) {
@@ -312,6 +422,77 @@ extern "C" int egv_cross_entropy_fwd_bwd(const float* logits, int64_t ld, const 
   if (dlogits && ldd < cols) return EGV_ERR_ARG;
   EGV_LAUNCH(cross_entropy_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, (const long long*)target, rows, cols,
              (long long)ignore_index, loss, dlogits, (long)ldd);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+// ---- the same loss on soft targets (label smoothing, Mixup / CutMix; torch's label_smoothing rule = timm's mixup_target):
+//   q_r = (1 - eps) (lam_r e(t_r) + (1 - lam_r) e(t2_r)) + eps / cols,  target2 NULL: t2 = t,  lam NULL: lam = 1
+//   loss = mean over the rows with t != ignore_index of (logsumexp(x_r) - sum_c q_rc x_rc),  d_logits = (softmax - q) / #valid
+// One workgroup, a wave per row as above; the sums over the classes and over the rows are carried in fp64 (the head's rule).
+namespace {
+__global__ __launch_bounds__(256) void cross_entropy_soft_kernel(const float* __restrict__ logits, long ld, const long long* __restrict__ target,
+                                                                 const long long* __restrict__ target2, const float* __restrict__ lam,
+                                                                 float eps, int rows, int cols, long long ignore_index,
+                                                                 float* __restrict__ loss, float* __restrict__ dlogits, long ldd) {
+  __shared__ double part[4];
+  __shared__ int cnt[4], bad[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // a valid row's t AND t2 lie in [0, cols): anything else voids the loss and every gradient (the rule of cross_entropy_kernel)
+  int nvalid = 0, nbad = 0;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const long long t = target[r], t2 = target2 ? target2[r] : t;
+    nvalid += (t != ignore_index);
+    nbad += (t != ignore_index && (t < 0 || t >= cols || t2 < 0 || t2 >= cols));
+  }
+  nvalid = (int)wave_sum((float)nvalid);
+  nbad = (int)wave_sum((float)nbad);
+  if (lane == 0) { cnt[wave] = nvalid; bad[wave] = nbad; }
+  __syncthreads();
+  const int valid = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  const bool any_bad = (bad[0] + bad[1] + bad[2] + bad[3]) > 0;
+  const double inv = valid > 0 ? 1.0 / (double)valid : 0.0;
+  const double qs = (double)eps / (double)cols, keep1 = 1.0 - (double)eps;
+  double acc = 0.0;
+  for (int r = wave; r < rows; r += 4) {
+    const float* x = logits + (long)r * ld;
+    const long long t = target[r], t2 = target2 ? target2[r] : t;
+    const bool on = t != ignore_index && t >= 0 && t < cols && t2 >= 0 && t2 < cols;
+    const double l = lam ? (double)lam[r] : 1.0;
+    float m = -3.0e38f;
+    for (int c = lane; c < cols; c += 64) m = fmaxf(m, x[c]);
+    m = wave_max(m);
+    double se = 0.0, sx = 0.0;
+    for (int c = lane; c < cols; c += 64) {
+      se += exp((double)x[c] - (double)m);
+      sx += (double)x[c];
+    }
+    se = wave_sum_d(se);
+    sx = wave_sum_d(sx);
+    const double lse = (double)m + log(se);
+    if (on) acc += lse - (keep1 * (l * (double)x[t] + (1.0 - l) * (double)x[t2]) + qs * sx);
+    if (dlogits) {
+      float* d = dlogits + (long)r * ldd;
+      for (int c = lane; c < cols; c += 64) {
+        const double q = keep1 * (l * (c == (int)t ? 1.0 : 0.0) + (1.0 - l) * (c == (int)t2 ? 1.0 : 0.0)) + qs;
+        d[c] = any_bad ? __builtin_nanf("") : (on ? (float)((exp((double)x[c] - lse) - q) * inv) : 0.f);
+      }
+    }
+  }
+  if (lane == 0) part[wave] = acc;      // every lane of a wave holds the same acc
+  __syncthreads();
+  if (threadIdx.x == 0)
+    loss[0] = (valid > 0 && !any_bad) ? (float)((((part[0] + part[1]) + part[2]) + part[3]) * inv) : __builtin_nanf("");
+}
+}  // namespace
+
+extern "C" int egv_cross_entropy_soft_fwd_bwd(const float* logits, int64_t ld, const int64_t* target, const int64_t* target2,
+                                              const float* lam, float label_smoothing, int32_t rows, int32_t cols, int64_t ignore_index,
+                                              float* loss, float* dlogits, int64_t ldd, void* stream) {
+  if (!logits || !target || !loss || rows <= 0 || cols <= 0 || rows > (1 << 20) || cols > 65536 || ld < cols) return EGV_ERR_ARG;
+  if ((dlogits && ldd < cols) || !(label_smoothing >= 0.f && label_smoothing <= 1.f)) return EGV_ERR_ARG;
+  EGV_LAUNCH(cross_entropy_soft_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, (const long long*)target,
+             (const long long*)target2, lam, label_smoothing, rows, cols, (long long)ignore_index, loss, dlogits, (long)ldd);
   EGV_CHECK_LAUNCH();
   return EGV_OK;
 }

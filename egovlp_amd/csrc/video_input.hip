@@ -225,12 +225,18 @@ __device__ __forceinline__ void store_patch4_sel(const float (&v)[4], long orow,
 }
 // One output row of the resized crop of frame bt, channel c: the clamped box, the two source rows behind output row y and the
 // Normalize constants.  sample(ox) is output pixel ox of that row in [0, 1], pixel(ox) the same normalised.
+// The arithmetic is PINNED: contraction off and every fused multiply-add written out.  Left to the compiler, which product of a
+// sum became an FMA depended on how it packed the pixels of a group, and that on everything around the group -- two kernels gave
+// the same bits only while their bodies happened to be alike (measured: 1 % of the lo-plane elements of a kernel that computed two
+// groups differed in the last place).  Written out, every kernel that samples a pixel computes the same bits whatever else it does,
+// which is what the kept-patch and the Mixup / CutMix kernels below promise.
 struct AugRow {
   const unsigned char *r0, *r1;
   float ly, sx, mu, sd;
   int bw, flip, R;
   __device__ __forceinline__ AugRow(const unsigned char* __restrict__ video, const int* __restrict__ boxes, int bt, int T, int C, int c,
                                     int Hs, int Ws, int R_, int y, const PatchNorm& nrm) {
+#pragma clang fp contract(off)
     const int* bx = boxes + (long)(bt / T) * 5;
     // a box that leaves the frame is CLAMPED into it (the host validates boxes it can see, model/video_transformer.py
     // set_input_augmentation; a device-resident box cannot be checked without a sync): no read below can leave the clip
@@ -242,7 +248,7 @@ struct AugRow {
     const unsigned char* src = video + ((long)bt * C + c) * Hs * Ws;
     const float sy = (float)bh / (float)R;
     sx = (float)bw / (float)R;
-    float fy = ((float)y + 0.5f) * sy - 0.5f;
+    float fy = fmaf((float)y + 0.5f, sy, -0.5f);
     fy = fy < 0.f ? 0.f : fy;
     const int y0 = (int)fy;
     const int y1 = y0 + (y0 < bh - 1 ? 1 : 0);
@@ -253,15 +259,17 @@ struct AugRow {
     sd = nrm.std[c];
   }
   __device__ __forceinline__ float sample(int ox) const {
+#pragma clang fp contract(off)
     const int sxi = flip ? R - 1 - ox : ox;               // RandomHorizontalFlip acts on the resized crop
-    float fx = ((float)sxi + 0.5f) * sx - 0.5f;
+    float fx = fmaf((float)sxi + 0.5f, sx, -0.5f);
     fx = fx < 0.f ? 0.f : fx;
     const int x0 = (int)fx;
     const int x1 = x0 + (x0 < bw - 1 ? 1 : 0);
     const float lx = fx - (float)x0;
     const float p00 = (float)r0[x0] / 255.0f, p01 = (float)r0[x1] / 255.0f;
     const float p10 = (float)r1[x0] / 255.0f, p11 = (float)r1[x1] / 255.0f;
-    return (1.0f - ly) * ((1.0f - lx) * p00 + lx * p01) + ly * ((1.0f - lx) * p10 + lx * p11);
+    const float top = fmaf(lx, p01, (1.0f - lx) * p00), bot = fmaf(lx, p11, (1.0f - lx) * p10);
+    return fmaf(ly, bot, (1.0f - ly) * top);
   }
   __device__ __forceinline__ float pixel(int ox) const { return (sample(ox) - mu) / sd; }
 };
@@ -288,9 +296,9 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const unsigned ch
 }
 
 // The train-transform gather over the kept patches.  The bilinear arithmetic is contraction-sensitive (which product of a sum the compiler
-// fuses into an FMA depends on how it packs the four pixels of a group), so a thread computes the SAME aligned 4-pixel group x4 .. x4 + 3
-// of output row y with the SAME code as patch_gather_aug_kernel and stores the pixels of it that lie in its patch: NG = P / 4 groups
-// per patch row when P % 4 == 0, (P + 2) / 4 when a patch can start in the middle of a group (P = 14).
+// fuses into an FMA depends on how it packs the four pixels of a group; AugRow pins it), so a thread computes the SAME aligned 4-pixel
+// group x4 .. x4 + 3 of output row y with the SAME code as patch_gather_aug_kernel and stores the pixels of it that lie in its patch:
+// NG = P / 4 groups per patch row when P % 4 == 0, (P + 2) / 4 when a patch can start in the middle of a group (P = 14).
 __global__ __launch_bounds__(256) void patch_gather_aug_sel_kernel(const unsigned char* __restrict__ video, int BT, int T, int C,
                                                                    int Hs, int Ws, int R, int P, int NG, const int* __restrict__ boxes,
                                                                    const int* __restrict__ keep, int K, bf16_t* __restrict__ ahi,
@@ -450,6 +458,190 @@ __global__ __launch_bounds__(256) void patch_gather_aug_color_sel_kernel(const u
   aug_color_group(video, boxes, color, bt, T, Hs, Ws, R, py * P + iy, xq * 4, nrm, v);
 #pragma unroll
   for (int c = 0; c < 3; ++c) store_patch4_sel(v[c], orow, c, iy, xq * 4 - px * P, P, ahi, alo, lda);
+}
+
+// ---- Mixup / CutMix inside the gather (extension; timm's Mixup restated, the reference has neither) -----------------------------------
+// The host draws, per clip b, mix_idx[b] = (partner, op, y0, y1, x0, x1) and mix_lam[b] (data_loader/transforms.py mix_params).  With
+// A_x the fully transformed clip x (its own crop box, flip, colour row and Normalize) and p = partner, the output of clip b is
+//   op 1 (mixup):   lam * A_b + (1 - lam) * A_p     two products and one sum, (1 - lam) formed in fp32, nothing contracted
+//   op 2 (cutmix):  A_p in rows [y0, y1) x columns [x0, x1) of the output frame (every frame of the clip: a tube), A_b elsewhere
+//   op 0 and 3:     A_b
+// The partner enters unmixed: no chains.  A thread computes the partner's G-pixel group with the code of the unmixed kernels (the
+// contraction rule above patch_gather_aug_sel_kernel) and selects per pixel, so a cutmix output is the unmixed gathers' bits; a
+// group wholly outside the box never reads the partner, one wholly inside never reads its own clip.  Both tables are read
+// defensively: partner clamped into [0, B), the box into the frame, op & 3 -- no table value addresses anything unclamped.  One
+// body per source kind; `keep` (NULL: all patches) only picks the thread map, and under it clip b's kept positions select the
+// output rows and the partner is read at those positions.
+struct MixRow { int bp, op, y0, y1, x0, x1; float lam; };
+__device__ __forceinline__ MixRow mix_row(const int* __restrict__ mix_idx, const float* __restrict__ mix_lam, int b, int B, int H, int W) {
+  const int* m = mix_idx + (long)b * 6;
+  MixRow r;
+  r.bp = min(max(m[0], 0), B - 1);
+  r.op = m[1] & 3;
+  r.y0 = min(max(m[2], 0), H);
+  r.y1 = min(max(m[3], 0), H);
+  r.x0 = min(max(m[4], 0), W);
+  r.x1 = min(max(m[5], 0), W);
+  r.lam = mix_lam[b];
+  return r;
+}
+__device__ __forceinline__ bool mix_in_box(const MixRow& r, int y, int x) {
+  return r.op == 2 && y >= r.y0 && y < r.y1 && x >= r.x0 && x < r.x1;
+}
+// which of the two clips the N pixels x .. x + N - 1 of output row y need
+template <int N>
+__device__ __forceinline__ void mix_needs(const MixRow& r, int y, int x, bool& own, bool& partner) {
+  int inside = 0;
+#pragma unroll
+  for (int e = 0; e < N; ++e) inside += mix_in_box(r, y, x + e) ? 1 : 0;
+  own = inside < N;
+  partner = r.op == 1 || inside > 0;
+}
+template <int N>
+__device__ __forceinline__ void mix_select(const MixRow& r, int y, int x, const float (&a)[N], const float (&p)[N], float (&v)[N]) {
+#pragma clang fp contract(off)
+  const float om = 1.0f - r.lam;
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = r.op == 1 ? r.lam * a[e] + om * p[e] : (mix_in_box(r, y, x + e) ? p[e] : a[e]);
+}
+
+// the same in two steps, for a kernel that walks the clip (w = 0) and then its partner (w = 1): out = lam * a, then out + (1 - lam) * p
+template <int N>
+__device__ __forceinline__ void mix_take(const MixRow& r, int y, int x, int w, const float (&v)[N], float (&out)[N]) {
+#pragma clang fp contract(off)
+  const float f = w ? 1.0f - r.lam : r.lam;
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    if (r.op == 1) out[e] = w ? out[e] + f * v[e] : f * v[e];
+    else if (mix_in_box(r, y, x + e) == (w != 0)) out[e] = v[e];
+  }
+}
+
+// fp32 and plain uint8 clips (no resampling): the thread maps, loads and stores of patch_gather_kernel / patch_gather_sel_kernel
+template <int G, bool U8>
+__global__ __launch_bounds__(256) void patch_gather_mix_kernel(const void* __restrict__ video_, int BT, int T, int C, int H, int W, int P,
+                                                               const int* __restrict__ mix_idx, const float* __restrict__ mix_lam,
+                                                               const int* __restrict__ keep, int K, bf16_t* __restrict__ ahi,
+                                                               bf16_t* __restrict__ alo, long lda, const PatchNorm nrm) {
+  const int gw = W / P, gh = H / P;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  int bt, c, y, x;
+  long row;
+  if (keep) {
+    const int PG = P / G;
+    if (i >= (long)BT * K * C * P * PG) return;
+    const int xg = (int)(i % PG);
+    long t = i / PG;
+    const int iy = (int)(t % P);
+    t /= P;
+    c = (int)(t % C);
+    row = t / C;                                // bt * K + j
+    bt = (int)(row / K);
+    const int pos = keep_at(keep, (long)(bt / T) * K + (row - (long)bt * K), gw * gh);
+    const int py = pos / gw, px = pos - py * gw;
+    y = py * P + iy;
+    x = px * P + xg * G;
+  } else {
+    const int WG = W / G;
+    if (i >= (long)BT * C * H * WG) return;
+    x = (int)(i % WG) * G;
+    long t = i / WG;
+    y = (int)(t % H);
+    t /= H;
+    c = (int)(t % C);
+    bt = (int)(t / C);
+    row = ((long)bt * gh + y / P) * gw + x / P;
+  }
+  const MixRow m = mix_row(mix_idx, mix_lam, bt / T, BT / T, H, W);
+  const int btp = m.bp * T + bt % T;
+  bool own, partner;
+  mix_needs<G>(m, y, x, own, partner);
+  float a[G] = {}, p[G] = {}, v[G];
+  if (own) load_pixels<G, U8>(video_, (((long)bt * C + c) * H + y) * W + x, c, nrm, a);
+  if (partner) load_pixels<G, U8>(video_, (((long)btp * C + c) * H + y) * W + x, c, nrm, p);
+  mix_select<G>(m, y, x, a, p, v);
+  store_group<G>(v, row, (c * P + y % P) * P + x % P, ahi, alo, lda);
+}
+
+// The aligned 4-pixel group x4 .. x4 + 3 of output row y of frame bt as the unmixed train-transform kernels compute it: channel c
+// into v[0] (plain), or the three jittered channels (COLOR)
+template <bool COLOR>
+__device__ __forceinline__ void aug_group(const unsigned char* __restrict__ video, const int* __restrict__ boxes,
+                                          const float* __restrict__ color, int bt, int T, int C, int c, int Hs, int Ws, int R, int y,
+                                          int x4, const PatchNorm& nrm, float (&v)[3][4]) {
+  if (COLOR) {
+    aug_color_group(video, boxes, color, bt, T, Hs, Ws, R, y, x4, nrm, v);
+  } else {
+    const AugRow row(video, boxes, bt, T, C, c, Hs, Ws, R, y, nrm);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[0][e] = row.pixel(x4 + e);
+  }
+}
+
+// the fused train transform: the thread maps and stores of the four patch_gather_aug*_kernel
+template <bool COLOR>
+__global__ __launch_bounds__(256) void patch_gather_aug_mix_kernel(const unsigned char* __restrict__ video, int BT, int T, int C, int Hs,
+                                                                   int Ws, int R, int P, int NG, const int* __restrict__ boxes,
+                                                                   const float* __restrict__ color, const int* __restrict__ mix_idx,
+                                                                   const float* __restrict__ mix_lam, const int* __restrict__ keep,
+                                                                   int K, bf16_t* __restrict__ ahi, bf16_t* __restrict__ alo, long lda,
+                                                                   const PatchNorm nrm) {
+  const int CT = COLOR ? 1 : C;                 // channels walked by the thread map
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  int bt, c = 0, y, x4, iy = 0, ix = 0;
+  long orow = 0;
+  if (keep) {
+    if (i >= (long)BT * K * CT * P * NG) return;
+    const int g = (int)(i % NG);
+    long t = i / NG;
+    iy = (int)(t % P);
+    t /= P;
+    if (!COLOR) {
+      c = (int)(t % C);
+      t /= C;
+    }
+    orow = t;                                   // bt * K + j
+    bt = (int)(orow / K);
+    const int gw = R / P;
+    const int pos = keep_at(keep, (long)(bt / T) * K + (orow - (long)bt * K), gw * gw);
+    const int py = pos / gw, px = pos - py * gw;
+    const int xq = (px * P) / 4 + g;            // the 4-pixel group of the whole output row
+    if (xq * 4 >= (px + 1) * P) return;
+    y = py * P + iy;
+    x4 = xq * 4;
+    ix = x4 - px * P;
+  } else {
+    const int WG = R / 4;
+    if (i >= (long)BT * CT * R * WG) return;
+    x4 = (int)(i % WG) * 4;
+    long t = i / WG;
+    y = (int)(t % R);
+    t /= R;
+    if (!COLOR) {
+      c = (int)(t % C);
+      t /= C;
+    }
+    bt = (int)t;
+  }
+  const MixRow m = mix_row(mix_idx, mix_lam, bt / T, BT / T, R, R);
+  const int btp = m.bp * T + bt % T;
+  bool need[2];
+  mix_needs<4>(m, y, x4, need[0], need[1]);
+  // ONE copy of the group's code, walked for the clip and then for its partner: the loop body is the body of the unmixed kernels
+  float out[3][4] = {};
+#pragma unroll 1
+  for (int w = 0; w < 2; ++w) {
+    if (!need[w]) continue;
+    float v[3][4];
+    aug_group<COLOR>(video, boxes, color, w ? btp : bt, T, C, c, Hs, Ws, R, y, x4, nrm, v);
+#pragma unroll
+    for (int k = 0; k < (COLOR ? 3 : 1); ++k) mix_take<4>(m, y, x4, w, v[k], out[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < (COLOR ? 3 : 1); ++k) {
+    if (keep) store_patch4_sel(out[k], orow, COLOR ? k : c, iy, ix, P, ahi, alo, lda);
+    else store_patch4(out[k], bt, COLOR ? k : c, y, x4, R, P, ahi, alo, lda);
+  }
 }
 
 // ---- val / test transform fused into the patch gather (data_loader/transforms.py:49-60: Resize(S) -> CenterCrop(S) -> Resize(R) ->
@@ -755,6 +947,39 @@ int patch_gather_aug_launch(const uint8_t* video, int BT, int T, int C, int Hs, 
   return EGV_OK;
 }
 
+// the mixed gathers: the refusals and grids of the two launchers above, plus the two mix tables
+template <bool U8>
+int patch_gather_mix_launch(const void* video, int BT, int T, int C, int H, int W, int P, const int32_t* mix_idx, const float* mix_lam,
+                            const int32_t* keep, int K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, const PatchNorm& nrm, void* stream) {
+  if (!mix_idx || !mix_lam || !gather_geom_ok(video, a_hi, BT, T, C, H, W, P, lda, keep ? 4 : 2, keep, K)) return EGV_ERR_ARG;
+  const int G = P % 4 == 0 ? 4 : 2;
+  dim3 grid;
+  if (!grid_of(keep ? (long)BT * K * C * P * (P / G) : (long)BT * C * H * (W / G), grid)) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (G == 4) EGV_LAUNCH((patch_gather_mix_kernel<4, U8>), grid, dim3(256), 0, s, video, BT, T, C, H, W, P, mix_idx, mix_lam, keep, K, a_hi, a_lo, (long)lda, nrm);
+  else EGV_LAUNCH((patch_gather_mix_kernel<2, U8>), grid, dim3(256), 0, s, video, BT, T, C, H, W, P, mix_idx, mix_lam, keep, K, a_hi, a_lo, (long)lda, nrm);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
+int patch_gather_aug_mix_launch(const uint8_t* video, int BT, int T, int C, int Hs, int Ws, int R, int P, const int32_t* boxes,
+                                const float* color, const float* mean, const float* std, const int32_t* mix_idx, const float* mix_lam,
+                                const int32_t* keep, int K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  PatchNorm nrm{};
+  if (!boxes || !mix_idx || !mix_lam || Hs <= 0 || Ws <= 0 || R % 4 != 0 || (color && C != 3) || !fill_norm(nrm, mean, std, C))
+    return EGV_ERR_ARG;
+  if (!gather_geom_ok(video, a_hi, BT, T, C, R, R, P, lda, keep ? 4 : 2, keep, K)) return EGV_ERR_ARG;
+  const int NG = P % 4 == 0 ? P / 4 : (P + 2) / 4;
+  const int CT = color ? 1 : C;
+  dim3 grid;
+  if (!grid_of(keep ? (long)BT * K * CT * P * NG : (long)BT * CT * R * (R / 4), grid)) return EGV_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (color) EGV_LAUNCH(patch_gather_aug_mix_kernel<true>, grid, dim3(256), 0, s, video, BT, T, C, Hs, Ws, R, P, NG, boxes, color, mix_idx, mix_lam, keep, K, a_hi, a_lo, (long)lda, nrm);
+  else EGV_LAUNCH(patch_gather_aug_mix_kernel<false>, grid, dim3(256), 0, s, video, BT, T, C, Hs, Ws, R, P, NG, boxes, color, mix_idx, mix_lam, keep, K, a_hi, a_lo, (long)lda, nrm);
+  EGV_CHECK_LAUNCH();
+  return EGV_OK;
+}
+
 // token assembly over K tokens per frame; keep == NULL: all patches, K == n
 int assemble_launch(const float* pe, const float* cls, const float* pos, const float* temporal, const int32_t* keep, int B, int T, int n,
                     int K, int D, float* x, void* stream) {
@@ -860,6 +1085,23 @@ extern "C" int egv_patch_gather_u8_aug_color_sel(const uint8_t* video, int32_t B
                                                  int64_t lda, void* stream) {
   if (!color || C != 3 || !keep) return EGV_ERR_ARG;
   return patch_gather_aug_launch(video, BT, T, C, Hs, Ws, R, P, boxes, color, mean, std, keep, K, a_hi, a_lo, lda, stream);
+}
+
+extern "C" int egv_patch_gather_mix(const void* video, int32_t u8, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                                    const float* mean, const float* std, const int32_t* mix_idx, const float* mix_lam,
+                                    const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  PatchNorm nrm{};
+  if (!u8) return patch_gather_mix_launch<false>(video, BT, T, C, H, W, P, mix_idx, mix_lam, keep, K, a_hi, a_lo, lda, nrm, stream);
+  if (!fill_norm(nrm, mean, std, C)) return EGV_ERR_ARG;
+  return patch_gather_mix_launch<true>(video, BT, T, C, H, W, P, mix_idx, mix_lam, keep, K, a_hi, a_lo, lda, nrm, stream);
+}
+
+extern "C" int egv_patch_gather_u8_aug_mix(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
+                                           int32_t P, const int32_t* boxes, const float* color, const float* mean, const float* std,
+                                           const int32_t* mix_idx, const float* mix_lam, const int32_t* keep, int32_t K,
+                                           egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream) {
+  return patch_gather_aug_mix_launch(video, BT, T, C, Hs, Ws, R, P, boxes, color, mean, std, mix_idx, mix_lam, keep, K, a_hi, a_lo, lda,
+                                     stream);
 }
 
 extern "C" int egv_patch_gather_u8_eval(const uint8_t* frames, int32_t F, const int32_t* index, int32_t BT, int32_t C, int32_t Hs,

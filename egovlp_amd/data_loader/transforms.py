@@ -18,6 +18,10 @@ brightness and saturation and [-h, h], 0 <= h <= 0.5, for hue; a (min, max) pair
 the identity value disables the op (skipped, not run with factor 1: the hue round trip is not the identity in fp32).  Contrast
 cannot be set through the reference's `init_transform_dict` and is skipped wherever it lands in the permutation.
 
+Mixup / CutMix (an extension, timm's `Mixup` restated; the reference mixes nothing) keeps the same division of labour: `mix_params`
+draws, per clip, the partner, the op, the cutmix box and lam, and the patch gather blends or selects the pixels of the two transformed
+clips (`SpaceTimeTransformer.set_input_mix`, `egv_patch_gather_mix` / `egv_patch_gather_u8_aug_mix`).
+
 The 'val' / 'test' transform (data_loader/transforms.py:49-60) is deterministic:
 
     Resize(center_crop) -> CenterCrop(center_crop) -> Resize(input_res) -> Normalize(mean, std)
@@ -132,3 +136,60 @@ def eval_transform_geometry(height, width, center_crop=256):
     else:
         H1, W1 = int(S * height / width), S
     return H1, W1, int(round((H1 - S) / 2.0)), int(round((W1 - S) / 2.0))
+
+
+def _beta(alpha, generator):
+    """One draw of Beta(alpha, alpha) from `generator`: X / (X + Y) with X, Y ~ Gamma(alpha, 1)."""
+    g = torch._standard_gamma(torch.full((2,), float(alpha), dtype=torch.float64), generator=generator)
+    total = float(g[0] + g[1])
+    return float(g[0]) / total if total > 0.0 else 0.5
+
+
+def _mix_draw(height, width, mixup_alpha, cutmix_alpha, prob, switch_prob, generator):
+    """One decision of timm's Mixup -> (op, lam, y0, y1, x0, x1)."""
+    if not float(torch.rand(1, generator=generator)) < prob:
+        return 0, 1.0, 0, 0, 0, 0
+    if mixup_alpha > 0.0 and cutmix_alpha > 0.0:
+        cut = float(torch.rand(1, generator=generator)) < switch_prob
+    else:
+        cut = cutmix_alpha > 0.0
+    lam = _beta(cutmix_alpha if cut else mixup_alpha, generator)
+    if not cut:
+        return 1, lam, 0, 0, 0, 0
+    ratio = math.sqrt(1.0 - lam)
+    cut_h, cut_w = int(height * ratio), int(width * ratio)
+    cy = int(torch.randint(0, height, (1,), generator=generator))
+    cx = int(torch.randint(0, width, (1,), generator=generator))
+    y0, y1 = min(max(cy - cut_h // 2, 0), height), min(max(cy + cut_h // 2, 0), height)
+    x0, x1 = min(max(cx - cut_w // 2, 0), width), min(max(cx + cut_w // 2, 0), width)
+    return 2, 1.0 - (y1 - y0) * (x1 - x0) / float(height * width), y0, y1, x0, x1
+
+
+def mix_params(batch, height, width, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode='batch', generator=None):
+    """The host half of Mixup / CutMix inside the patch gather (an extension: timm's `Mixup` restated, the recipe of the VideoMAE /
+    MViT fine-tunes; the reference mixes nothing) -> (mix_idx int32 [batch, 6], mix_lam float32 [batch]), or (None, None) when it
+    is off (both alphas 0, or prob 0): every caller then makes the calls it made before.
+    mix_idx[b] = (partner, op, y0, y1, x0, x1): op 0 nothing, 1 mixup, 2 cutmix; the box covers rows [y0, y1) and columns [x0, x1)
+    of the OUTPUT frame of `height` x `width` pixels (input_res x input_res under the fused train transform), the same in every
+    frame of the clip.  With probability `prob` the batch (mode 'batch': one op, one lam, one box for all clips) or the clip (mode
+    'elem': its own draw) is mixed; cutmix is chosen with probability `switch_prob` when both alphas are > 0; lam ~ Beta(alpha,
+    alpha); the cutmix box has extents int(height * cut), int(width * cut), cut = sqrt(1 - lam), a centre uniform over the frame,
+    is clipped to the frame, and lam is then REPLACED by 1 - area / (height * width) of the clipped box.  The partner is the flipped
+    batch, batch - 1 - b (the middle clip of an odd batch pairs with itself); rows that are not mixed are (b, 0, 0, 0, 0, 0), lam 1.
+    The target of clip b is lam * target[b] + (1 - lam) * target[partner] (`classification_step(mix=...)`)."""
+    if mode not in ('batch', 'elem'):
+        raise ValueError("mix_params: mode is 'batch' or 'elem'")
+    if batch < 1 or height < 1 or width < 1:
+        raise ValueError("mix_params: batch, height and width are positive")
+    if mixup_alpha < 0.0 or cutmix_alpha < 0.0 or not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+        raise ValueError("mix_params: alphas are non-negative, prob and switch_prob lie in [0, 1]")
+    if (mixup_alpha == 0.0 and cutmix_alpha == 0.0) or prob == 0.0:
+        return None, None
+    draws = [_mix_draw(height, width, mixup_alpha, cutmix_alpha, prob, switch_prob, generator)
+             for _ in range(batch if mode == 'elem' else 1)]
+    rows, lams = [], []
+    for b in range(batch):
+        op, lam, y0, y1, x0, x1 = draws[b if mode == 'elem' else 0]
+        rows.append([batch - 1 - b if op else b, op, y0, y1, x0, x1])
+        lams.append(lam)
+    return torch.tensor(rows, dtype=torch.int32), torch.tensor(lams, dtype=torch.float32)

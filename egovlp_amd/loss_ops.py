@@ -312,9 +312,15 @@ def dual_softmax(x, temp=500.0):
     return out
 
 
-def cross_entropy(logits, target, ignore_index=-100, want_grad=True):
-    """nn.CrossEntropyLoss (mean over targets != ignore_index) on [rows, classes] fp32 scores and int64 labels -> (loss[1], dlogits)."""
-    ops._need_cuda(logits, target)
+def cross_entropy(logits, target, ignore_index=-100, want_grad=True, target2=None, lam=None, label_smoothing=0.0):
+    """nn.CrossEntropyLoss (mean over targets != ignore_index) on [rows, classes] fp32 scores and int64 labels -> (loss[1], dlogits).
+    target2 [rows] / lam [rows] / label_smoothing (Mixup / CutMix and label smoothing): the soft targets
+    (1 - eps) (lam e(t) + (1 - lam) e(t2)) + eps / classes of egv_cross_entropy_soft_fwd_bwd; without any of them the call made before."""
+    if lam is not None and target2 is None:
+        raise ValueError("cross_entropy: lam mixes target with target2")
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError("cross_entropy: label_smoothing lies in [0, 1]")
+    ops._need_cuda(logits, target, target2, lam)
     if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
         raise ValueError("cross_entropy: logits [rows, classes], target [rows]")
     x = logits.float()
@@ -323,6 +329,16 @@ def cross_entropy(logits, target, ignore_index=-100, want_grad=True):
     t = target.to(torch.int64).contiguous()
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     dx = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device) if want_grad else None
+    if target2 is not None or float(label_smoothing) != 0.0:
+        rows = x.shape[0]
+        if (target2 is not None and tuple(target2.shape) != (rows,)) or (lam is not None and tuple(lam.shape) != (rows,)):
+            raise ValueError("cross_entropy: target2 [rows], lam [rows]")
+        t2 = None if target2 is None else target2.to(torch.int64).contiguous()
+        lm = None if lam is None else lam.to(torch.float32).contiguous()
+        check(_lib.lib().egv_cross_entropy_soft_fwd_bwd(_p(x), x.stride(0), _p(t), _p(t2), _p(lm), float(label_smoothing), rows, x.shape[1],
+                                                        int(ignore_index), _p(loss), _p(dx), x.shape[1], ops._stream(x)),
+              "egv_cross_entropy_soft_fwd_bwd")
+        return loss, dx
     check(_lib.lib().egv_cross_entropy_fwd_bwd(_p(x), x.stride(0), _p(t), x.shape[0], x.shape[1], int(ignore_index), _p(loss),
                                                _p(dx), x.shape[1], ops._stream(x)), "egv_cross_entropy_fwd_bwd")
     return loss, dx
@@ -340,9 +356,10 @@ def cls_head_ok(n, B, K, C):
 class ClsLayout:
     """Columns of the fp32 row block that crosses the ranks in the classification fine-tunes: [0, C) the scores, then the class
     index, then (PNR) the state, then (PNR validation) fps as two floats (hi + lo of the fp64 value), parent_start_frame,
-    parent_end_frame, parent_pnr_frame.  Integer columns are exact below 2^24."""
+    parent_end_frame, parent_pnr_frame.  Integer columns are exact below 2^24.  `soft` (Mixup / CutMix) appends, AFTER all of these,
+    the partner's class index and the mixing weight: a layout without it is the layout it always was."""
 
-    def __init__(self, C, task='oscc', evaluate=False):
+    def __init__(self, C, task='oscc', evaluate=False, soft=False):
         if task not in ('oscc', 'pnr'):
             raise ValueError("task is 'oscc' or 'pnr'")
         self.C, self.task = C, task
@@ -353,10 +370,17 @@ class ClsLayout:
         if task == 'pnr' and evaluate:
             self.fps, self.start, self.end, self.pnr = C + 2, C + 4, C + 5, C + 6
             self.ld = C + 7
+        self.target2 = self.lam = -1
+        if soft:
+            self.target2, self.lam = self.ld, self.ld + 1
+            self.ld += 2
 
-    def fill(self, packed, target, state=None, fps=None, start=None, end=None, pnr=None):
+    def fill(self, packed, target, state=None, fps=None, start=None, end=None, pnr=None, target2=None, lam=None):
         """Write everything but the scores into packed [B, ld]."""
         packed[:, self.target] = target
+        if self.target2 >= 0:
+            packed[:, self.target2] = target2
+            packed[:, self.lam] = lam
         if self.state >= 0:
             packed[:, self.state] = state
         if self.fps >= 0:
@@ -400,10 +424,14 @@ def cls_head_fwd(feats, weight, bias, out=None):
     return out
 
 
-def cls_head_loss_bwd(packed, C, col_target, col_state=-1, row0=0, B=None, feats=None, weight=None, want_grad=True, want_pred=False):
+def cls_head_loss_bwd(packed, C, col_target, col_state=-1, row0=0, B=None, feats=None, weight=None, want_grad=True, want_pred=False,
+                      col_target2=-1, col_lam=-1, label_smoothing=0.0):
     """Loss (and backward) of the classification head on the gathered block packed [n, ld] (egv_cls_head_loss_bwd)
     -> (loss[1], dW [C, K], db [C], dfeats [B, K], pred int32 [n]); entries not asked for are None.  feats [B, K]: the LOCAL rows
-    row0 .. row0 + B of the batch."""
+    row0 .. row0 + B of the batch.  col_target2 / col_lam (columns of the partner's class and of the mixing weight; -1: none) or
+    label_smoothing > 0: the soft-target head, egv_cls_head_loss_bwd_soft; without any of them the call made before."""
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError("cls_head_loss_bwd: label_smoothing lies in [0, 1]")
     ops._need_cuda(packed)
     if packed.dim() != 2 or packed.dtype != torch.float32 or packed.stride(1) != 1:
         raise ValueError("cls_head_loss_bwd: packed must be fp32 [n, ld] with unit column stride")
@@ -426,6 +454,12 @@ def cls_head_loss_bwd(packed, C, col_target, col_state=-1, row0=0, B=None, feats
         dW = torch.empty((C, K), dtype=torch.float32, device=dev)
         db = torch.empty(C, dtype=torch.float32, device=dev)
         dx = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if int(col_target2) >= 0 or int(col_lam) >= 0 or float(label_smoothing) != 0.0:
+        check(_lib.lib().egv_cls_head_loss_bwd_soft(_p(packed), packed.stride(0), n, C, int(col_target), int(col_state), int(col_target2),
+                                                    int(col_lam), float(label_smoothing), int(row0), B, _p(x),
+                                                    0 if x is None else x.stride(0), _p(w), K, _p(loss), _p(dW), _p(db), _p(dx), K,
+                                                    _p(pred), _p(work), ops._stream(packed)), "egv_cls_head_loss_bwd_soft")
+        return loss, dW, db, dx, pred
     check(_lib.lib().egv_cls_head_loss_bwd(_p(packed), packed.stride(0), n, C, int(col_target), int(col_state), int(row0), B,
                                            _p(x), 0 if x is None else x.stride(0), _p(w), K, _p(loss), _p(dW), _p(db), _p(dx), K,
                                            _p(pred), _p(work), ops._stream(packed)), "egv_cls_head_loss_bwd")

@@ -343,35 +343,61 @@ class AdaptiveMaxMarginRankingLoss(nn.Module):
 
 class CrossEntropy(nn.Module):
     """model/loss.py:135-141: `nn.CrossEntropyLoss()(output, target)` (mean reduction, ignore_index -100), the loss of
-    configs/ft/oscc.json and pnr.json."""
+    configs/ft/oscc.json and pnr.json.  `label_smoothing` (an extension, torch's own argument: `"args": {"label_smoothing": 0.1}`)
+    and the `target2` / `lam` of a Mixup / CutMix step make the target of a row (1 - eps) (lam e(t) + (1 - lam) e(t2)) + eps / C;
+    with label_smoothing 0 and no target2 every method makes the calls it made before."""
 
-    def __init__(self):
+    def __init__(self, label_smoothing=0.0):
         super().__init__()
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError("CrossEntropy: label_smoothing lies in [0, 1]")
+        self.label_smoothing = float(label_smoothing)
 
-    def forward(self, output, target):
+    def _soft(self, target2, lam):
+        if lam is not None and target2 is None:
+            raise ValueError("CrossEntropy: lam mixes target with target2")
+        return {} if target2 is None and self.label_smoothing == 0.0 else \
+            {"target2": target2, "lam": lam, "label_smoothing": self.label_smoothing}
+
+    def forward(self, output, target, target2=None, lam=None):
+        soft = self._soft(target2, lam)
+        return _KernelLossFn.apply(lambda output: loss_ops.cross_entropy(output, target, want_grad=True, **soft), output)
+
+    def hard(self, output, target):
+        "The loss on the hard targets whatever `label_smoothing` says: what validation reports (comparable across recipes)."
         return _KernelLossFn.apply(lambda output: loss_ops.cross_entropy(output, target, want_grad=True), output)
 
-    def fused(self, feats, weight, bias, target, state=None, world_size=1, rank=0, ec=None):
+    def fused(self, feats, weight, bias, target, state=None, world_size=1, rank=0, ec=None, target2=None, lam=None):
         """The classification head of the OSCC / PNR step in one node, from the video tower's features [B, K]:
         scores = feats weight^T + bias, gathered over the ranks with target (and state) in one collective, then
           state None:  CrossEntropy(scores, target)                       trainer/trainer_oscc.py:335-338
           state [B]:   mean(state.T * CrossEntropy(scores, target))       trainer/trainer_pnr.py:345-350
         and the local gradients w.r.t. feats, weight and bias (what AllGather_multi.backward leaves to this rank).
-        `ec`: the model's execution context (its backward poll runs first in backward, as in the projection node this replaces)."""
-        return _ClsHeadFn.apply(feats, weight, bias, target, state, world_size, rank, ec)[0]
+        `ec`: the model's execution context (its backward poll runs first in backward, as in the projection node this replaces).
+        target2 [B] / lam [B]: the partner's class and the mixing weight of a Mixup / CutMix step; they ride in the same collective."""
+        self._soft(target2, lam)
+        return _ClsHeadFn.apply(feats, weight, bias, target, state, world_size, rank, ec, target2, lam, self.label_smoothing)[0]
 
 
 class _ClsHeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, weight, bias, target, state, world, rank, ec=None):
+    def forward(ctx, feats, weight, bias, target, state, world, rank, ec=None, target2=None, lam=None, label_smoothing=0.0):
         B, C = feats.shape[0], weight.shape[0]
-        lay = loss_ops.ClsLayout(C, 'oscc' if state is None else 'pnr')
+        # hard targets: the layout, the columns and the loss call of always; the two soft columns ride only with a target2
+        cols, soft = {}, {}
+        if target2 is None:
+            lay = loss_ops.ClsLayout(C, 'oscc' if state is None else 'pnr')
+        else:
+            lay = loss_ops.ClsLayout(C, 'oscc' if state is None else 'pnr', soft=True)
+            cols = {"target2": target2, "lam": 1.0 if lam is None else lam}
         packed = torch.empty((B, lay.ld), dtype=torch.float32, device=feats.device)
         loss_ops.cls_head_fwd(feats, weight, bias, out=packed)
-        lay.fill(packed, target, state)
+        lay.fill(packed, target, state, **cols)
         allp = gather._gather_rows(packed, world)             # the ONE collective of the step; nothing is sent at world size 1
+        if target2 is not None or label_smoothing != 0.0:
+            soft = {"col_target2": lay.target2, "col_lam": lay.lam, "label_smoothing": label_smoothing}
         loss, dW, db, dx, _ = loss_ops.cls_head_loss_bwd(allp, C, lay.target, lay.state, row0=rank * B, B=B, feats=feats,
-                                                         weight=weight)
+                                                         weight=weight, **soft)
         ctx.ec, ctx.has_bias = ec, bias is not None
         ctx.save_for_backward(dx, dW, db)
         ctx.mark_non_differentiable(allp)
@@ -382,4 +408,4 @@ class _ClsHeadFn(torch.autograd.Function):
         dx, dW, db = ctx.saved_tensors
         if ctx.ec is not None and not ctx.ec.on_text_stream():
             ctx.ec.poll_backward()      # the first node of the video tower's backward on the main stream (as _ProjFn.backward)
-        return dx * g, dW * g, (db * g if ctx.has_bias else None), None, None, None, None, None
+        return (dx * g, dW * g, (db * g if ctx.has_bias else None)) + (None,) * 8

@@ -40,8 +40,9 @@ class BlockCall(NamedTuple):      # the `geom` argument of the two block nodes; 
 
 # The `geom` argument of _PatchTokensFn.  P: patch size; mean_std: the loader's Normalize; aug = (boxes, out_res[, colour-jitter table]): the
 # train transform inside the gather; eval = (center_crop, out_res, frame table): the val / test transform inside the gather; keep: patch
-# dropout, int32 [B, K] kept positions on the device
-PatchCall = namedtuple("PatchCall", "B T n P D T_model mean_std aug eval keep", defaults=((ops.IMAGENET_MEAN, ops.IMAGENET_STD), None, None, None))
+# dropout, int32 [B, K] kept positions on the device; mix = (mix_idx, mix_lam): Mixup / CutMix inside the gather, tables on the device
+PatchCall = namedtuple("PatchCall", "B T n P D T_model mean_std aug eval keep mix",
+                       defaults=((ops.IMAGENET_MEAN, ops.IMAGENET_STD), None, None, None, None))
 
 
 def f16x2_block_ok(M, D, Hd, train):
@@ -371,7 +372,8 @@ class _PatchTokensFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, video, geom, ec, proj_w, proj_b, cls_token, pos_embed, temporal_embed):
         geom = PatchCall(*geom)
-        B, T, n, P_, D, T_model, (mean, std), aug, ev, keep = geom
+        B, T, n, P_, D, T_model, (mean, std), aug, ev, keep, mix = geom
+        mixed = {} if mix is None else {"mix": mix}             # no mix: the calls made without the argument
         Pp = ec.fwd_passes_split
         wc = ec.wc
         if ev is not None:
@@ -380,9 +382,9 @@ class _PatchTokensFn(torch.autograd.Function):
         else:
             # uint8 frames: /255 + Normalize (and, with `aug`, the train transform's crop / resize / flip) inside the gather
             if aug is not None and len(aug) > 2:       # (boxes, out_res, colour-jitter table)
-                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug[:2], keep=keep, color=aug[2])
+                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug[:2], keep=keep, color=aug[2], **mixed)
             else:
-                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug, keep=keep)
+                a = ops.patch_gather(video.contiguous(), P_, Pp, mean, std, aug=aug, keep=keep, **mixed)
         K = proj_w[0].numel()
         if a.cols == K:
             w_pl = wc.get(proj_w, need_t=False)[0]
@@ -391,7 +393,7 @@ class _PatchTokensFn(torch.autograd.Function):
         pe = torch.empty((a.rows, D), dtype=torch.float32, device=video.device)
         ops.gemm_nt(a, w_pl, passes=Pp, bias=proj_b, out_f32=pe, ec=ec)
         x = ops.assemble_tokens(pe, cls_token, pos_embed, temporal_embed, B, T, n, D, keep=keep)
-        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom._replace(keep=None), a, Pp, ec
+        ctx.geom, ctx.a, ctx.Pp, ctx.ec = geom._replace(keep=None, mix=None), a, Pp, ec
         ctx.save_for_backward(*(() if keep is None else (keep,)))
         ctx.wshape, ctx.proj_w = proj_w.shape, proj_w
         return x
@@ -671,6 +673,31 @@ class SpaceTimeTransformer(nn.Module):
             aug = aug + (color.to(device=self.cls_token.device, dtype=torch.float32).contiguous(),)
         self._input_aug = aug
 
+    def set_input_mix(self, mix_idx, mix_lam):
+        """Mixup / CutMix inside the patch gather of the NEXT forward (egovlp_amd.data_loader.transforms.mix_params draws the tables):
+        `mix_idx` int [B, 6] rows (partner, op, y0, y1, x0, x1) -- op 0 nothing, 1 mixup, 2 cutmix, the box in rows / columns of the
+        frame the tower patches -- and `mix_lam` float [B].  Clip b becomes lam * A_b + (1 - lam) * A_partner (mixup) or takes the
+        partner's pixels inside the box (cutmix), with A_x the transformed clip x; it combines with fp32 and uint8 input,
+        set_input_augmentation and patch dropout, and not with set_input_eval_transform.  Host-resident tables are validated here
+        (partner in [0, B), lam finite in [0, 1]); device tables are taken as they are (no sync; the kernels clamp what they read).
+        One-shot: consumed by the next forward_features call."""
+        if getattr(self, "_input_eval", None) is not None:
+            raise ValueError("set_input_mix: an eval transform is pending for the next forward (set_input_eval_transform)")
+        if not torch.is_tensor(mix_idx) or mix_idx.is_floating_point() or mix_idx.dtype == torch.bool or mix_idx.dim() != 2 \
+                or mix_idx.shape[1] != 6 or mix_idx.shape[0] < 1:
+            raise ValueError("set_input_mix: mix_idx is an int [B, 6] table (partner, op, y0, y1, x0, x1)")
+        B = mix_idx.shape[0]
+        if not torch.is_tensor(mix_lam) or not mix_lam.is_floating_point() or tuple(mix_lam.shape) != (B,):
+            raise ValueError(f"set_input_mix: mix_lam is a float [{B}] table, one weight per row of mix_idx")
+        if not mix_idx.is_cuda and (bool((mix_idx[:, 0] < 0).any()) or bool((mix_idx[:, 0] >= B).any())):
+            raise ValueError(f"set_input_mix: a partner lies outside the batch of {B} clips")
+        if not mix_lam.is_cuda:
+            lam = mix_lam.detach().double()
+            if not bool(torch.isfinite(lam).all()) or bool((lam < 0).any()) or bool((lam > 1).any()):
+                raise ValueError("set_input_mix: mix_lam values are finite and lie in [0, 1]")
+        dev = self.cls_token.device
+        self._input_mix = (mix_idx.to(device=dev, dtype=torch.int32).contiguous(), mix_lam.to(device=dev, dtype=torch.float32).contiguous())
+
     def set_input_eval_transform(self, center_crop=256, out_res=None, frame_index=None):
         """Fuse the loader's val / test transform (Resize(center_crop) -> CenterCrop(center_crop) -> Resize(out_res) -> Normalize,
         data_loader/transforms.py:49-60) into the NEXT forward: it takes decoded uint8 frames [b, T, C, Hs, Ws] and resizes, crops
@@ -681,6 +708,8 @@ class SpaceTimeTransformer(nn.Module):
         set_input_augmentation."""
         if getattr(self, "_input_aug", None) is not None:
             raise ValueError("set_input_eval_transform: a train augmentation is pending for the next forward (set_input_augmentation)")
+        if getattr(self, "_input_mix", None) is not None:
+            raise ValueError("set_input_eval_transform: a Mixup / CutMix table is pending for the next forward (set_input_mix)")
         S, R = int(center_crop), int(out_res or self.patch_embed.img_size[0])
         if S < 1 or R < 1:
             raise ValueError("set_input_eval_transform: center_crop and out_res are positive sizes")
@@ -695,9 +724,13 @@ class SpaceTimeTransformer(nn.Module):
         self._input_eval = None
         aug = getattr(self, "_input_aug", None)
         self._input_aug = None
+        mix = getattr(self, "_input_mix", None)
+        self._input_mix = None
         if ev is not None:
             if aug is not None:
                 raise ValueError("set_input_eval_transform and set_input_augmentation are mutually exclusive")
+            if mix is not None:
+                raise ValueError("set_input_eval_transform and set_input_mix are mutually exclusive")
             if x.dtype != torch.uint8:
                 raise ValueError("set_input_eval_transform expects decoded uint8 frames")
             if ev[2] is not None:
@@ -722,13 +755,15 @@ class SpaceTimeTransformer(nn.Module):
                 raise ValueError(f"set_input_augmentation: a crop box leaves the {Hh} x {Ww} frame (or the batch size changed)")
             aug = aug[:2] + aug[3:]                                            # (boxes, out_res[, colour-jitter table])
             Hh = Ww = aug[1]                                                   # the resized crop is what gets patched
+        if mix is not None and mix[0].shape[0] != b:
+            raise ValueError(f"set_input_mix: the tables have {mix[0].shape[0]} rows, the batch {b} clips")
         n = (Hh // P_) * (Ww // P_)
         if n != self.patches_per_frame:
             raise NotImplementedError("input resolution must match the positional embedding")
         # `input_norm` = (mean, std) of the loader's Normalize (data_loader/transforms.py:34-39); only used when the frames
         # arrive as decoded uint8 (then x / 255 and the normalisation are fused into the patch gather on the device)
         geom = PatchCall(b, curr_frames, n, P_, self.embed_dim, self.num_frames,
-                         getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev)
+                         getattr(self, "input_norm", (ops.IMAGENET_MEAN, ops.IMAGENET_STD)), aug, ev, None, mix)
         ec = self.exec_ctx
         drops = self.training and any(blk.drop_path > 0. for blk in self.blocks)
         patch_drop = self.training and self.patch_drop_rate > 0.

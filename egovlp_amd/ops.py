@@ -1004,7 +1004,21 @@ def patch_keep_draw(B, n, K, seed, seed_dev=None, device="cuda"):
     return keep
 
 
-def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None, keep=None, color=None) -> Planes:
+def _check_mix(mix, B, what):
+    """The Mixup / CutMix tables of a call: contiguous int32 [B, 6] (partner, op, y0, y1, x0, x1) and float32 [B] in HBM."""
+    if not isinstance(mix, (tuple, list)) or len(mix) != 2 or not all(torch.is_tensor(t) for t in mix):
+        raise ValueError(f"{what}: mix is (mix_idx int32 [B, 6], mix_lam float32 [B])")
+    idx, lam = mix
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (B, 6) or not idx.is_contiguous():
+        raise ValueError(f"{what}: mix_idx is a contiguous int32 [{B}, 6] table (partner, op, y0, y1, x0, x1), got "
+                         f"{idx.dtype} {tuple(idx.shape)}")
+    if lam.dtype != torch.float32 or tuple(lam.shape) != (B,) or not lam.is_contiguous():
+        raise ValueError(f"{what}: mix_lam is a contiguous float32 [{B}] table, got {lam.dtype} {tuple(lam.shape)}")
+    _need_cuda(idx, lam)
+    return idx, lam
+
+
+def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_STD, aug=None, keep=None, color=None, mix=None) -> Planes:
     """im2col planes [B*T*patches, K = C*P*P]; K is padded with zero columns to a multiple of 64 (the GEMM k-tile;
     588 -> 640 for ViT-L/14), `cols` of the returned planes is the PADDED width.  A uint8 `video5d` (decoded frames) is
     scaled and normalised in the kernel (x / 255, then (x - mean) / std per channel) -- the loader's host transform.
@@ -1014,8 +1028,13 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
     shift, op code) as `data_loader.transforms.train_transform_params_color` draws them -- the transform's ColorJitter, applied
     between the flip and Normalize (the egv_patch_gather_u8_aug_color kernels).  None: the calls made without it.
     keep (patch dropout): int32 [B, Kp] on the device -- only those patch positions of every frame of clip b are gathered, row
-    bt * Kp + j = patch keep[bt // T][j] of frame bt, the bits of that row of the full gather (the egv_patch_gather*_sel kernels)."""
+    bt * Kp + j = patch keep[bt // T][j] of frame bt, the bits of that row of the full gather (the egv_patch_gather*_sel kernels).
+    mix = (mix_idx int32 [B, 6], mix_lam float32 [B]) on the device (`data_loader.transforms.mix_params`): Mixup / CutMix of every clip
+    with its partner inside the gather, on any of the input paths above (egv_patch_gather_mix / egv_patch_gather_u8_aug_mix).  None:
+    the calls made without it."""
     B, T, Cc, H, W = video5d.shape
+    if mix is not None:
+        mix = _check_mix(mix, B, "patch_gather")
     if aug is not None:
         boxes, R = aug
         if video5d.dtype != torch.uint8:
@@ -1048,6 +1067,16 @@ def patch_gather(video5d, P, passes, norm_mean=IMAGENET_MEAN, norm_std=IMAGENET_
     if color is not None:
         geom = geom + (_p(color),)
     norm = ((C.c_float * Cc)(*norm_mean), (C.c_float * Cc)(*norm_std)) if u8 else ()
+    if mix is not None:
+        # the two mixed entries take every table as a nullable argument: one call per source kind
+        tail = (_p(mix[0]), _p(mix[1]), _p(keep), per_frame if keep is not None else 0, _p(pl.hi), _p(pl.lo), pl.ld, _stream(video5d))
+        if aug is not None:
+            check(_lib.lib().egv_patch_gather_u8_aug_mix(_p(video5d), B * T, T, Cc, video5d.shape[3], video5d.shape[4], H, P, _p(aug[0]),
+                                                         _p(color), *norm, *tail), "egv_patch_gather_u8_aug_mix")
+        else:
+            check(_lib.lib().egv_patch_gather_mix(_p(video5d), int(u8), B * T, T, Cc, H, W, P, *(norm or (None, None)), *tail),
+                  "egv_patch_gather_mix")
+        return pl
     sel = () if keep is None else (_p(keep), per_frame)
     check(getattr(_lib.lib(), name)(_p(video5d), B * T, *clip, Cc, *geom, *norm, *sel, _p(pl.hi), _p(pl.lo), pl.ld,
                                     _stream(video5d)), name)

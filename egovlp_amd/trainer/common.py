@@ -238,6 +238,8 @@ class TrainerBase(Multi_BaseTrainer_dist):
                     self.writer.add_scalar(f'Loss_training/queue_filled_{dl_idx}', self.loss.queue_filled(), (epoch - 1) * total + current)
                 if hasattr(getattr(self, 'loss', None), 'current_bias'):                    # the sigmoid losses: their second parameter
                     self.writer.add_scalar(f'Loss_training/bias_{dl_idx}', self.loss.current_bias(), (epoch - 1) * total + current)
+                if getattr(self, 'last_mix_lambda', None) is not None:                      # Mixup / CutMix on: the mean lam of this step's draw
+                    self.writer.add_scalar(f'Loss_training/mix_lambda_{dl_idx}', self.last_mix_lambda, (epoch - 1) * total + current)
                 if ema is not None:                                                         # the decay the average has just run with
                     self.writer.add_scalar(f'Loss_training/ema_decay_{dl_idx}', ema.current_decay(), (epoch - 1) * total + current)
                 # gradient clipping on: the step's un-scaled pre-clip norm and its coefficient, read back where float(loss) has

@@ -18,6 +18,7 @@ import torch
 
 from .. import loss_ops
 from ..gather import AllGatherRows, _gather_rows, _world
+from ..data_loader.transforms import mix_params
 from ..loss_ops import ClsLayout, cls_head_ok
 from .classification_eval import ClassificationEvaluator
 from .common import step_epilogue, step_prologue
@@ -41,20 +42,39 @@ def _head(core):
 
 
 def classification_step(model, loss_fn, optimizer, data, world_size=1, rank=0, task='oscc', fused_head=True, grad_sync=None,
-                        scaler=None):
+                        scaler=None, mix=None):
     """One fine-tuning step on a batch {'video', 'state'[, 'labels']} already on the device.  Returns the (device) loss tensor; no
-    host sync.  `grad_sync` / `scaler`: as egoclip_step."""
+    host sync.  `grad_sync` / `scaler`: as egoclip_step.
+    mix = (mix_idx, mix_lam) (an extension; data_loader.transforms.mix_params): Mixup / CutMix of every clip with its partner inside
+    the patch gather (`set_input_mix`), the target lam * target + (1 - lam) * target[partner] -- partners are rank-local, so the
+    partner's class is formed here, before the gather, and rides with lam in the step's one collective.  OSCC only: a blended clip
+    has no keyframe.  None: the calls made without it."""
+    if mix is not None and task == 'pnr':
+        raise ValueError("classification_step: Mixup / CutMix does not combine with task='pnr' (a blended clip has no keyframe); "
+                         "PNR takes label smoothing only")
     core, ec, scaler = step_prologue(model, optimizer, scaler)                  # trainer_oscc.py:333
     video = data['video']
     target, state = _targets(data, task, video.device)
     lin, B = _head(core), video.shape[0]
+    soft = ()
+    if mix is not None:
+        mix_idx, mix_lam = mix
+        core.video_model.set_input_mix(mix_idx, mix_lam)                        # consumed by the forward below, on either route
+        partner = mix_idx[:, 0].to(device=video.device, dtype=torch.long).clamp(0, B - 1)   # the clamp of the kernels
+        soft = (target[partner], mix_lam.to(device=video.device, dtype=torch.float32))
     if fused_head and hasattr(loss_fn, 'fused') and lin is not None and cls_head_ok(world_size * B, B, lin.in_features, lin.out_features):
         ec.begin_step()
         feats = core.video_model(video)                                         # model/model.py:114, without the projection
-        loss = loss_fn.fused(feats, lin.weight, lin.bias, target, state, world_size, rank, ec)   # :335-338 / pnr :341-350
+        if soft:
+            loss = loss_fn.fused(feats, lin.weight, lin.bias, target, state, world_size, rank, ec, target2=soft[0], lam=soft[1])
+        else:
+            loss = loss_fn.fused(feats, lin.weight, lin.bias, target, state, world_size, rank, ec)   # :335-338 / pnr :341-350
     else:
         scores = model(data, video_only=True)                                   # :335
-        if state is None:
+        if soft:
+            scores, target, target2, lam = AllGatherRows.apply(world_size, rank, scores, target, *soft)
+            loss = loss_fn(scores, target, target2, lam)
+        elif state is None:
             scores, target = AllGatherRows.apply(world_size, rank, scores, target)             # :336-337
             loss = loss_fn(scores, target)                                      # :338
         else:
@@ -73,9 +93,23 @@ class ClassificationTrainerBase(RetrievalTrainerBase):
     def _host_batch(self, data):
         return data
 
+    MIX_ARGS = ('mixup_alpha', 'cutmix_alpha')      # `args` attributes that switch Mixup / CutMix on (absent or 0: off)
+    last_mix_lambda = None                           # mean lam of the step's draw, for the log; None: nothing was drawn
+
+    def _mix_on(self):
+        return any(float(getattr(self.args, k, 0) or 0) > 0 for k in self.MIX_ARGS)
+
+    def _draw_mix(self, data):
+        """The step's Mixup / CutMix tables from args.mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, mix_mode; None when off."""
+        return None
+
     def _step(self, data):
+        mix = self._draw_mix(data)
+        if mix is None:
+            return classification_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank, task=self.task,
+                                       fused_head=self.fused_head, grad_sync=self.grad_sync)
         return classification_step(self.model, self.loss, self.optimizer, data, self.n_gpu, self.args.rank, task=self.task,
-                                   fused_head=self.fused_head, grad_sync=self.grad_sync)
+                                   fused_head=self.fused_head, grad_sync=self.grad_sync, mix=mix)
 
     def _val_columns(self, data):
         """Everything of a validation batch that rides in the row block besides the scores (ClsLayout.fill's arguments)."""
@@ -110,7 +144,7 @@ class ClassificationTrainerBase(RetrievalTrainerBase):
                         block = torch.empty((B, lay.ld), dtype=torch.float32, device=self.device)
                         block[:, :C] = scores
                         lay.fill(block, **cols)
-                        loss = self.loss(scores, cols['target'])
+                        loss = getattr(self.loss, 'hard', self.loss)(scores, cols['target'])     # no smoothing in validation
                         if cols['state'] is not None:
                             loss = torch.mean(cols['state'] * loss)
                     evaluator.add_loss(loss, dl_idx)
@@ -139,3 +173,19 @@ class Multi_Trainer_dist_OSCC(ClassificationTrainerBase):
 
     task = 'oscc'
     _verbose = staticmethod(verbose)
+    _mix_generator = None
+
+    def _draw_mix(self, data):
+        a = self.args
+        if not self._mix_on():
+            return None
+        if self._mix_generator is None:             # a stream of its own per rank: the draws disturb no other random state
+            self._mix_generator = torch.Generator().manual_seed(int(getattr(a, 'seed', 0) or 0) * 1000003 + int(getattr(a, 'rank', 0)))
+        video = data['video']
+        prob = getattr(a, 'mix_prob', None)
+        switch = getattr(a, 'mix_switch_prob', None)
+        mix = mix_params(video.shape[0], video.shape[-2], video.shape[-1], float(getattr(a, 'mixup_alpha', 0) or 0),
+                         float(getattr(a, 'cutmix_alpha', 0) or 0), 1.0 if prob is None else float(prob),
+                         0.5 if switch is None else float(switch), getattr(a, 'mix_mode', None) or 'batch', self._mix_generator)
+        self.last_mix_lambda = None if mix[0] is None else float(mix[1].mean())         # host tables: no sync
+        return None if mix[0] is None else mix

@@ -25,6 +25,13 @@ class Multi_Trainer_dist_PNR(ClassificationTrainerBase):
     task = 'pnr'
     _verbose = staticmethod(verbose)
 
+    def __init__(self, args, *rest, **kw):
+        self.args = args
+        if self._mix_on():          # a blended clip has no keyframe: refused here, before anything is built
+            raise ValueError("Multi_Trainer_dist_PNR: Mixup / CutMix (args.mixup_alpha / args.cutmix_alpha) does not apply to keyframe "
+                             "localisation; PNR takes label smoothing only (CrossEntropy(label_smoothing=...))")
+        super().__init__(args, *rest, **kw)
+
     def _val_columns(self, data):
         cols = super()._val_columns(data)
         for key, name in (('fps', 'fps'), ('start', 'parent_start_frame'), ('end', 'parent_end_frame'), ('pnr', 'parent_pnr_frame')):

@@ -406,6 +406,31 @@ int egv_patch_gather_u8_aug_sel(const uint8_t* video, int32_t BT, int32_t T, int
 int egv_patch_gather_u8_aug_color_sel(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R,
                                       int32_t P, const int32_t* boxes, const float* color, const float* mean, const float* std,
                                       const int32_t* keep, int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
+/* ---- Mixup / CutMix inside the gather (extension; timm's Mixup, the VideoMAE / MViT fine-tuning recipe -- the reference has neither)
+ * The host draws two tables per batch of B = BT / T clips (data_loader/transforms.py mix_params), both on the DEVICE:
+ *   mix_idx int32 [B, 6]: (partner, op, y0, y1, x0, x1);  mix_lam fp32 [B].
+ * With A_x the fully transformed clip x (for the train transform: its own crop box, flip, colour row and Normalize) and p = partner,
+ * the output rows of clip b hold
+ *   op 1 (mixup):   lam * A_b + (1 - lam) * A_p -- on the normalised values, in exactly this order: the two products, then their sum,
+ *                   (1 - lam) formed in fp32, nothing contracted; lam = 1 gives A_b's bits and lam = 0 A_p's;
+ *   op 2 (cutmix):  A_p in rows [y0, y1) x columns [x0, x1) of the OUTPUT frame (H x W; R x R under the train transform), the same
+ *                   box in all T frames (a tube), A_b elsewhere -- a selection: every element is a bit copy of the unmixed gather;
+ *   op 0 (and 3):   A_b, the bits of the entry without a mix.
+ * The partner enters unmixed (no chains).  The kernels clamp partner into [0, B) and the box into the frame and read op & 3: no table
+ * value addresses anything unclamped.  keep (NULL: all patches, then K is not read): the patch-dropout table of the *_sel entries;
+ * clip b's kept positions select the output rows and the partner is read at those positions.  No backward: the gather has no
+ * gradient to the pixels.
+ * egv_patch_gather_mix: clips that need no resampling -- u8 == 0: fp32 [B*T,C,H,W] (mean / std not read), else decoded uint8 with
+ * HOST mean / std -- and otherwise the arguments and refusals of egv_patch_gather[_u8][_sel].
+ * egv_patch_gather_u8_aug_mix: the fused train transform; color NULL: no jitter, else C == 3; otherwise the arguments and refusals
+ * of egv_patch_gather_u8_aug[_color][_sel].  A NULL mix table is EGV_ERR_ARG, nothing launched.                                   */
+int egv_patch_gather_mix(const void* video, int32_t u8, int32_t BT, int32_t T, int32_t C, int32_t H, int32_t W, int32_t P,
+                         const float* mean, const float* std, const int32_t* mix_idx, const float* mix_lam, const int32_t* keep,
+                         int32_t K, egv_bf16* a_hi, egv_bf16* a_lo, int64_t lda, void* stream);
+int egv_patch_gather_u8_aug_mix(const uint8_t* video, int32_t BT, int32_t T, int32_t C, int32_t Hs, int32_t Ws, int32_t R, int32_t P,
+                                const int32_t* boxes, const float* color, const float* mean, const float* std,
+                                const int32_t* mix_idx, const float* mix_lam, const int32_t* keep, int32_t K, egv_bf16* a_hi,
+                                egv_bf16* a_lo, int64_t lda, void* stream);
 /* x[b,0,:] = cls + pos[0]; x[b,1+f*K+j,:] = (pe[(b*T+f)*K+j,:] + pos[1+keep[b][j]]) + temporal[f] (:305-320 on the kept tokens):
  * the sum order of egv_assemble_tokens, so the rows are bit-identical to the matching rows of the full assembly.                  */
 int egv_assemble_tokens_sel(const float* pe, const float* cls, const float* pos, const float* temporal, const int32_t* keep,
@@ -702,6 +727,23 @@ int egv_cls_head_loss_bwd(const float* packed, int64_t ld, int32_t n, int32_t C,
                           int32_t row0, int32_t B, const float* feats, int64_t ldf, const float* W, int32_t K,
                           float* loss, float* dW, float* db, float* dfeats, int64_t ldd, int32_t* pred, double* work,
                           void* stream);
+/* egv_cls_head_loss_bwd on SOFT targets (extension: label smoothing and Mixup / CutMix; torch's label_smoothing rule, which is timm's
+ * mixup_target).  Two more columns of the block -- col_target2 the partner's class t2 (-1: t2 = t), col_lam the mixing weight lam
+ * (-1: lam = 1) -- and eps = label_smoothing in [0, 1] give the target distribution of row r
+ *   q_r  = (1 - eps) (lam_r e(t_r) + (1 - lam_r) e(t2_r)) + eps / C
+ *   loss = s (1/n) sum_r (logsumexp(x_r) - sum_c q_rc x_rc),   g_r = s (softmax(x_r) - q_r) / n.
+ * dW, db, dfeats, pred (the argmax of the SCORES), s, the limits, the fp64 sums, the fixed summation order and the work buffer are
+ * those of egv_cls_head_loss_bwd; a t OR t2 outside [0, C) makes the loss and every gradient NaN.  The columns are distinct. */
+int egv_cls_head_loss_bwd_soft(const float* packed, int64_t ld, int32_t n, int32_t C, int32_t col_target, int32_t col_state,
+                               int32_t col_target2, int32_t col_lam, float label_smoothing, int32_t row0, int32_t B,
+                               const float* feats, int64_t ldf, const float* W, int32_t K, float* loss, float* dW, float* db,
+                               float* dfeats, int64_t ldd, int32_t* pred, double* work, void* stream);
+/* egv_cross_entropy_fwd_bwd on the same soft targets, for given scores: target2 (int64 [rows]) and lam (fp32 [rows]) may each be NULL
+ * (t2 = t, lam = 1).  Rows with target == ignore_index drop out of the numerator and of the count, as in torch; a valid row whose t
+ * or t2 lies outside [0, cols) makes loss and dlogits NaN.  Sums over classes and rows in fp64, fixed order.                   */
+int egv_cross_entropy_soft_fwd_bwd(const float* logits, int64_t ld, const int64_t* target, const int64_t* target2, const float* lam,
+                                   float label_smoothing, int32_t rows, int32_t cols, int64_t ignore_index, float* loss,
+                                   float* dlogits, int64_t ldd, void* stream);
 /* Validation accumulator: accum = double[4] on the device {sum of hits, rows seen, sum of err_sec, positives seen}, updated in
  * place with the rows of a gathered block in ascending order.
  *   col_state < 0 (OSCC, model/metric.py:342-353): hit = argmax(x_r) == t_r; accum[0] += hits, accum[1] += n.
