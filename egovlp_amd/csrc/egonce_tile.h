@@ -1,7 +1,24 @@
-// Tile pieces shared by the contrastive heads that walk the n x n similarity in 64 x 64 tiles without storing it
-// (egonce_long.hip, sigmoid_head.hip): the prep kernel and its outputs, the LDS tile, the bit-packed noun / verb mask tile, the
-// X^T fragment product on the fp32-input MFMA, the column-range split and the finish kernel (sum of the partials + the backward
-// of the row normalisation).  The k order of the two products is described at the top of egonce_long.hip.
+// Tile pieces shared by the contrastive heads that walk the similarity in 64 x 64 tiles without storing it (egonce_long.hip: the long
+// and the queue head; sigmoid_head.hip): the prep kernel and its outputs, the column-range split, and the steps of a walk -- the
+// prologue (lane coordinates, A operand), the LDS tile, the bit-packed noun / verb mask tile, the X^T fragment product on the
+// fp32-input MFMA, the second product dA += G . B with its store -- and the finish kernel (sum of the partials + the backward of the
+// row normalisation).
+//
+// The walk.  Workgroup = (64 rows of A, a range of 64-row column tiles); a wave owns 16 rows and keeps their operand in registers
+// (EGL_WALK_LDS, EGL_WALK_BEGIN).  Per tile: barrier, the tile's rows and the mask tile go to LDS (egl_stage_tile, egl_mask_tile; a
+// head may stage more), barrier, X^T fragments (egl_xt) and the lane's mask words, row 16 wave + li of the mask tile (bit 4 g + r of
+// word jf belongs to x[jf][r]); the head's own arithmetic on the 16 pairs of the lane; then, in a gradient walk, G -- formed in the
+// registers of the X^T fragment, which IS the operand layout of the next product (lane = row i, lane group = k) -- goes through
+// EGL_SECOND_PRODUCT on the same MFMA with B_J read from the LDS tile, and EGL_STORE_GPART writes the raw partials of the column
+// range at the end.
+//
+// The prologue, the second product and the store are macros over the names of the kernel's scope, not functions: the same
+// statements behind a call boundary come out of the compiler as other machine code for the walk instances ("One walk").
+//
+// k order.  The 16x16x4 MFMA takes k = lane >> 4 from each lane.  A lane reads FOUR consecutive floats (one 16-byte LDS read)
+// and feeds element t to MFMA t, so MFMA t of chunk c sums k = 16 c + 4 (lane >> 4) + t; both operands use the same map, which
+// only permutes the order of the fma chain.  The second product uses the same trick on the OUTPUT column: MFMA t of a 64-wide
+// chunk produces d = 64 c + 4 (lane & 15) + t, so a lane ends with four consecutive d and stores 16 bytes.
 #pragma once
 #include "head_common.h"
 
@@ -10,11 +27,12 @@ namespace {
 constexpr int EGL_TILE = 64;          // rows per tile (A rows per workgroup, B rows per LDS tile)
 constexpr int EGL_GRAD_WGS = 256;     // the gradient walks aim at this many workgroups: their partials cost memory and a pass
 
-inline void egl_split(int ntiles, int target, int& tps, int& ns) {
-  int want = (target + ntiles - 1) / ntiles;
-  if (want > ntiles) want = ntiles;
-  tps = (ntiles + want - 1) / want;
-  ns = (ntiles + tps - 1) / tps;       // no empty range
+// `rtiles` row tiles against `ctiles` column tiles, about `target` workgroups -> tiles per column range and ranges
+inline void egl_split(int rtiles, int ctiles, int target, int& tps, int& ns) {
+  int want = (target + rtiles - 1) / rtiles;
+  if (want > ctiles) want = ctiles;
+  tps = (ctiles + want - 1) / want;
+  ns = (ctiles + tps - 1) / tps;       // no empty range
 }
 
 // ------------------------------------------------------------------------------------------------ prep
@@ -126,20 +144,24 @@ inline int egl_launch_prep(const EglPrepLayout& L, const float* text, const floa
 }
 
 // ------------------------------------------------------------------------------------------------ tile pieces
-// B rows j0 .. j0 + 63 -> LDS image [64][DP + 4] (the 4 floats of padding spread the rows over the banks)
-template <int DP>
-__device__ __forceinline__ void egl_stage_tile(float* bt, const float* __restrict__ B, int j0) {
+// B rows j0 .. j0 + 63 -> LDS image [64][DP + 4] (the 4 floats of padding spread the rows over the banks).  ZERO_TAIL: the rows
+// from `valid` on are written as zeros and not read (an unused queue slot may hold anything).
+template <int DP, bool ZERO_TAIL = false>
+__device__ __forceinline__ void egl_stage_tile(float* bt, const float* __restrict__ B, int j0, int valid = EGL_TILE) {
   constexpr int LD = DP + 4, C4 = DP / 4;
   for (int idx = threadIdx.x; idx < EGL_TILE * C4; idx += 256) {
     const int r = idx / C4, c4 = idx % C4;
-    *(f32x4_t*)(bt + r * LD + 4 * c4) = *(const f32x4_t*)(B + (long)(j0 + r) * DP + 4 * c4);
+    f32x4_t v = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    if (!ZERO_TAIL || r < valid) v = *(const f32x4_t*)(B + (long)(j0 + r) * DP + 4 * c4);
+    *(f32x4_t*)(bt + r * LD + 4 * c4) = v;
   }
 }
 
-// The 64 x 64 mask tile, 16 bits per thread: thread (row i0 + (tid & 63), wave q) covers columns j0 + 16 q .. + 15; the words of
-// a column row are wave-uniform.  mode 0: diagonal only; 1: noun AND verb; 2: noun; 3: verb.  mb: [64][4] words.
-__device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words, int W, int wn, int mode, int i0, int j0,
-                                              uint32_t* mb) {
+// The 64 x 64 mask tile between the words of the A rows (wa, rows i0 ..) and those of the tile's rows (wb, rows j0 ..; the same
+// array, or a queue's), 16 bits per thread: thread (row i0 + (tid & 63), wave q) covers columns j0 + 16 q .. + 15; the words of a
+// column row are wave-uniform.  mode 0: nothing; 1: noun AND verb; 2: noun; 3: verb.  diag: add i == j.  mb: [64][4] words.
+__device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ wa, const uint32_t* __restrict__ wb, int W, int wn,
+                                              int mode, int i0, int j0, int diag, uint32_t* mb) {
   const int il = threadIdx.x & 63;
   const int jq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int gi = i0 + il, jb = j0 + jq * 16;
@@ -148,14 +170,14 @@ __device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words
     uint32_t hn[16], hv[16];
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) hn[jj] = hv[jj] = 0u;
-    const u32x4_t* wi = (const u32x4_t*)(words + (long)gi * W);
+    const u32x4_t* wi = (const u32x4_t*)(wa + (long)gi * W);
     const int qn = wn >> 2, qa = W >> 2;
     if (mode != 3)
       for (int q = 0; q < qn; ++q) {
         const u32x4_t a = wi[q];
 #pragma unroll
         for (int jj = 0; jj < 16; ++jj) {
-          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];      // wave-uniform: scalar loads
+          const u32x4_t b = ((const u32x4_t*)(wb + (long)(jb + jj) * W))[q];         // wave-uniform: scalar loads
           hn[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
         }
       }
@@ -164,7 +186,7 @@ __device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words
         const u32x4_t a = wi[q];
 #pragma unroll
         for (int jj = 0; jj < 16; ++jj) {
-          const u32x4_t b = ((const u32x4_t*)(words + (long)(jb + jj) * W))[q];
+          const u32x4_t b = ((const u32x4_t*)(wb + (long)(jb + jj) * W))[q];
           hv[jj] |= (a[0] & b[0]) | (a[1] & b[1]) | (a[2] & b[2]) | (a[3] & b[3]);
         }
       }
@@ -175,7 +197,7 @@ __device__ __forceinline__ void egl_mask_tile(const uint32_t* __restrict__ words
     }
   }
   const int dj = gi - jb;
-  if (dj >= 0 && dj < 16) bits |= 1u << dj;
+  if (diag && dj >= 0 && dj < 16) bits |= 1u << dj;
   mb[il * 4 + jq] = bits;
 }
 
@@ -196,6 +218,55 @@ __device__ __forceinline__ void egl_xt(const float* bt, const f32x4_t (&a)[DP / 
       for (int jf = 0; jf < 4; ++jf) x[jf] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[jf][t], a[c][t], x[jf], 0, 0, 0);
   }
 }
+
+// What a walk kernel starts with, declared in the kernel's own scope: the two LDS images at the front of its dynamic LDS `smem`
+// (bt [64][DP + 4]: the column tile; mb [64][4]: the mask tile; a head's own staging follows from mb + 4 * EGL_TILE on), the lane's
+// coordinates (wave: uniform; li = lane & 15, g = lane >> 4; i0: first row of the workgroup, gi: this lane's row), ntiles = np / 64,
+// the column tiles t0 .. t1 - 1 of the workgroup out of `tiles` (an expression, which may use ntiles), and row gi of A as the
+// operand of egl_xt (the floats 16 c + 4 g .. + 3 of every chunk c).
+#define EGL_WALK_LDS(DP)                                      \
+  float* bt = (float*)smem;                                   \
+  uint32_t* mb = (uint32_t*)(bt + EGL_TILE * ((DP) + 4))
+#define EGL_WALK_BEGIN(DP, A, np, tiles, tps)                                                    \
+  const int lane = threadIdx.x & 63;                                                             \
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                             \
+  const int li = lane & 15, g = lane >> 4;                                                       \
+  const int i0 = blockIdx.x * EGL_TILE;                                                          \
+  const int ntiles = (np) / EGL_TILE;                                                            \
+  const int t0 = blockIdx.y * (tps), t1 = min((tiles), t0 + (tps));                              \
+  const int gi = i0 + wave * 16 + li;                                                            \
+  f32x4_t a[(DP) / 16];                                                                          \
+  _Pragma("unroll") for (int c = 0; c < (DP) / 16; ++c) a[c] = *(const f32x4_t*)((A) + (long)gi * (DP) + 16 * c + 4 * g)
+
+// the accumulators of the second product
+template <int DP>
+__device__ __forceinline__ void egl_acc_zero(f32x4_t (&acc)[DP / 64][4]) {
+#pragma unroll
+  for (int c = 0; c < DP / 64; ++c)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[c][t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+}
+
+// dA[i][d] += sum_j G[i][j] B[j][d] on the prologue's names: x[jf][r] holds G and is the A operand of k-step (jf, r) as it stands
+// (k = j = 16 jf + 4 g + r), B_J is read from the LDS tile bt, acc[DP / 64][4] are the accumulators.
+#define EGL_SECOND_PRODUCT(DP)                                                                           \
+  _Pragma("unroll") for (int jf = 0; jf < 4; ++jf)                                                       \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                          \
+  _Pragma("unroll") for (int c = 0; c < (DP) / 64; ++c) {                                                \
+    const f32x4_t bv = *(const f32x4_t*)(bt + (jf * 16 + 4 * g + r) * ((DP) + 4) + 64 * c + 4 * li);     \
+    _Pragma("unroll") for (int tt = 0; tt < 4; ++tt)                                                     \
+      acc[c][tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[jf][r], bv[tt], acc[c][tt], 0, 0, 0);          \
+  }
+
+// acc[c][tt][rr]: row i0 + 16 wave + 4 g + rr, column 64 c + 4 li + tt -> gpart [ranges][np][DP]; a walk with no tile stores zeros
+#define EGL_STORE_GPART(DP, gpart, np)                                                                   \
+  {                                                                                                      \
+    float* out = (gpart) + ((long)blockIdx.y * (np) + i0 + wave * 16 + 4 * g) * (DP) + 4 * li;           \
+    _Pragma("unroll") for (int c = 0; c < (DP) / 64; ++c)                                                \
+    _Pragma("unroll") for (int rr = 0; rr < 4; ++rr)                                                     \
+      *(f32x4_t*)(out + (long)rr * (DP) + 64 * c) =                                                      \
+          (f32x4_t){acc[c][0][rr], acc[c][1][rr], acc[c][2][rr], acc[c][3][rr]};                         \
+  }
 
 // sum of the column-range partials in a fixed order + the backward of the row normalisation (egv_norm_bwd)
 __global__ __launch_bounds__(256) void egl_finish_kernel(const float* __restrict__ gpart, int ns, const float* __restrict__ an,

@@ -1,4 +1,4 @@
-// Pieces shared by the contrastive and ranking heads (egonce.hip, egonce_long.hip, egonce_queue.hip, sigmoid_head.hip through egonce_tile.h,
+// Pieces shared by the contrastive and ranking heads (egonce.hip, egonce_long.hip, sigmoid_head.hip through egonce_tile.h,
 // maxmargin_head.hip): the 256-thread block reductions, the backward of the row normalisation and the scale-gradient kernel.
 #pragma once
 #include "common.h"
@@ -29,7 +29,7 @@ __device__ __forceinline__ T egv_norm_bwd(T g, T a, float proj, float nrm, float
 }
 
 // dL/d(logit scale) = sum of `count` fp32 partials; one workgroup, double, fixed order.  A kernel in a header is emitted into every
-// file that includes it, launched or not: only the files that launch it (egonce.hip, egonce_long.hip, egonce_queue.hip) define EGV_SCALE_GRAD_KERNEL.
+// file that includes it, launched or not: only the files that launch it (egonce.hip, egonce_long.hip) define EGV_SCALE_GRAD_KERNEL.
 #ifdef EGV_SCALE_GRAD_KERNEL
 __global__ __launch_bounds__(256) void egv_scale_grad_kernel(const float* __restrict__ part, int count,
                                                              float* __restrict__ d_logit_scale) {

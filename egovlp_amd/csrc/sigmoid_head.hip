@@ -10,8 +10,8 @@
 // memory; all arithmetic fp32 on the fp32-input MFMA (egonce_tile.h); every reduction runs in a fixed order (no float atomics).
 //
 //   prep    the long head's (egonce_tile.h): tn / vn zero-padded to Dp, the packed noun / verb words, norms, the bad-entry flags.
-//   walk    workgroup = (64 rows of A, a range of 64-row tiles of B).  Per tile: the X^T fragment, the mask tile, u, p and G in the
-//           fragment's registers, then dA_I += G_IJ . B_J on the same MFMA; raw partials per column range.  Launched with roles
+//   walk    the walk of egonce_tile.h (prologue, tile pieces, second product and store are its pieces); this head's own part is the
+//           arithmetic on a tile's pairs: u, p and G in the fragment's registers.  Launched with roles
 //           (tn, vn) and (vn, tn): the mask is symmetric.  In the (tn, vn) walk each lane also sums its loss terms, G x and z p (per
 //           tile first, then into the running sums); the workgroup stores ONE partial of each per (row tile, column range).
 //           Rows and columns >= n of the last tile are masked out of all of them: a padded pair has u = b, a FINITE loss term.
@@ -37,7 +37,7 @@ struct SigLayout : EglPrepLayout {
 
 inline SigLayout sig_layout(int n, int D, int dn, int dv) {
   SigLayout L{egl_prep_layout(n, D, dn, dv)};
-  egl_split(L.ntiles, SIG_WALK_WGS, L.tps, L.ns);
+  egl_split(L.ntiles, L.ntiles, SIG_WALK_WGS, L.tps, L.ns);
   const long np = L.np;
   long o = L.total;
   L.gpart = o;  o += (long)L.ns * np * L.Dp;
@@ -66,37 +66,22 @@ __global__ __launch_bounds__(256, 2) void sig_walk_kernel(const float* __restric
                                                           float* __restrict__ lpart /* [3][ranges][tiles]; SUMS only */) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float sh[4];
-  constexpr int LD = DP + 4;
-  float* bt = (float*)smem;
-  uint32_t* mb = (uint32_t*)(bt + EGL_TILE * LD);
+  EGL_WALK_LDS(DP);
   const float t = expf(logit_scale[0]), b = logit_bias[0];
   const float sc = -t / (float)n;
   float ls = 0.f, gx = 0.f, zs = 0.f;                 // this lane's share of sum softplus, sum G X, sum z p
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, g = lane >> 4;
-  const int i0 = blockIdx.x * EGL_TILE;
-  const int ntiles = np / EGL_TILE;
-  const int t0 = blockIdx.y * tps, t1 = min(ntiles, t0 + tps);
-  const int gi = i0 + wave * 16 + li;
-
-  f32x4_t a[DP / 16];
-#pragma unroll
-  for (int c = 0; c < DP / 16; ++c) a[c] = *(const f32x4_t*)(A + (long)gi * DP + 16 * c + 4 * g);
+  EGL_WALK_BEGIN(DP, A, np, ntiles, tps);
   const bool live = gi < n;
 
   f32x4_t acc[DP / 64][4];
-#pragma unroll
-  for (int c = 0; c < DP / 64; ++c)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) acc[c][tt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  egl_acc_zero<DP>(acc);
 
 #pragma unroll 1
   for (int tl = t0; tl < t1; ++tl) {
     const int j0 = tl * EGL_TILE;
     __syncthreads();                                  // every wave is done with the previous tile
     egl_stage_tile<DP>(bt, B, j0);
-    egl_mask_tile(words, W, wn, mode, i0, j0, mb);
+    egl_mask_tile(words, words, W, wn, mode, i0, j0, 1, mb);
     __syncthreads();
     f32x4_t x[4];
     egl_xt<DP>(bt, a, li, g, x);
@@ -120,28 +105,10 @@ __global__ __launch_bounds__(256, 2) void sig_walk_kernel(const float* __restric
     gx += tgx;
     zs += tzs;
     if constexpr (GRAD) {
-      // dA[i][d] += sum_j G[i][j] B[j][d]: x[jf][r] is the A operand of k-step (jf, r) as it stands (k = j = 16 jf + 4 g + r)
-#pragma unroll
-      for (int jf = 0; jf < 4; ++jf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int c = 0; c < DP / 64; ++c) {
-            const f32x4_t bv = *(const f32x4_t*)(bt + (jf * 16 + 4 * g + r) * LD + 64 * c + 4 * li);
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) acc[c][tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[jf][r], bv[tt], acc[c][tt], 0, 0, 0);
-          }
+      EGL_SECOND_PRODUCT(DP);
     }
   }
-  if constexpr (GRAD) {
-    // acc[c][tt][rr]: row i0 + 16 wave + 4 g + rr, column 64 c + 4 li + tt
-    float* out = gpart + ((long)blockIdx.y * np + i0 + wave * 16 + 4 * g) * DP + 4 * li;
-#pragma unroll
-    for (int c = 0; c < DP / 64; ++c)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        *(f32x4_t*)(out + (long)rr * DP + 64 * c) = (f32x4_t){acc[c][0][rr], acc[c][1][rr], acc[c][2][rr], acc[c][3][rr]};
-  }
+  if constexpr (GRAD) EGL_STORE_GPART(DP, gpart, np);
   if constexpr (SUMS) {
     const long cnt = (long)gridDim.y * ntiles, at = (long)blockIdx.y * ntiles + blockIdx.x;
     ls = egv_block_sum_256(ls, sh);

@@ -9,7 +9,7 @@ Two ways in, same kernels underneath (egovlp_amd/csrc/egonce.hip, through the wr
 Both losses take `learnable_temperature=True` (not in the reference): the temperature becomes CLIP's learnable logit scale, read on the
 device by the *_ls variants of the same entry points, which also return its gradient (_TemperatureMixin below), and `queue_size=Q`
 (not in the reference): the normalised embeddings of the last steps are kept in a ring of Q rows on the device and serve as extra
-constant columns of the softmax in `fused` (egv_egonce_queue_fwd_bwd, csrc/egonce_queue.hip); the ring is no part of state_dict(),
+constant columns of the softmax in `fused` (egv_egonce_queue_fwd_bwd, csrc/egonce_long.hip); the ring is no part of state_dict(),
 so a resumed run refills its queue in Q / n steps.
 SigmoidLoss / EgoSigmoidLoss (not in the reference) are the pairwise sigmoid (SigLIP) counterparts of the two softmax losses, with a
 learnable logit scale AND bias (_SigmoidMixin): `forward` over egv_sigmoid_from_sim, `fused` over egv_sigmoid_head_fwd_bwd
@@ -118,7 +118,7 @@ class _TemperatureMixin(_LogitScaleMixin):
         return _KernelLossFn.apply(call, x, *self._scale())
 
     # ---- the queue of past embeddings (`queue_size=Q`, a multiple of 64 in [64, 65 536]; 0: none, the module is what it always was)
-    # In train() mode `fused` runs the rectangular head of csrc/egonce_queue.hip for EVERY n <= Q: the batch against itself and
+    # In train() mode `fused` runs the rectangular head of csrc/egonce_long.hip for EVERY n <= Q: the batch against itself and
     # against the valid slots of the ring -- extra negatives and, for EgoNCE, extra positives (a queued clip that shares a noun and
     # a verb with an anchor), constants that get no gradient -- and then enqueues the batch, unless the loss is not finite.  Every
     # rank runs the head on the same gathered batch, so every rank enqueues the same rows and nothing is exchanged.  In eval() mode

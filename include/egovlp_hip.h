@@ -626,11 +626,11 @@ int egv_egonce_long_fwd_bwd_ls(const float* text, const float* video, const floa
 int egv_egonce_from_sim_ls(const float* x, const float* sim_v, const float* sim_n, int32_t n, const float* logit_scale,
                            int32_t use_noun, int32_t use_verb, float* loss, float* dx, float* d_logit_scale,
                            float* work /* n*n + 7n floats */, void* stream);
-/* EgoNCE / NormSoftmaxLoss with a QUEUE of past embeddings (csrc/egonce_queue.hip): the normalised rows of earlier steps are extra
+/* EgoNCE / NormSoftmaxLoss with a QUEUE of past embeddings (csrc/egonce_long.hip: the long head's walk with queue tiles): the normalised rows of earlier steps are extra
  * constant columns of both softmaxes -- more negatives and, for EgoNCE, more positives (a queued clip that shares a noun and a verb
  * with an anchor) at no encoder cost.  With K = filled valid slots the head walks the rectangle of n batch rows against n + K columns
  * per direction, 2 n (n + K) pairs, and forms no queue x queue term; K = 0 is egv_egonce_long_fwd_bwd's loss.  Formulas: the top of
- * csrc/egonce_queue.hip.  The queue lives in caller-owned DEVICE buffers in the kernels' own layout, which egv_egonce_queue_layout
+ * csrc/egonce_long.hip.  The queue lives in caller-owned DEVICE buffers in the kernels' own layout, which egv_egonce_queue_layout
  * returns (Dp floats per embedding row, W 32-bit words per noun / verb row; 1 on a bad D / dn / dv):
  *   q_text, q_video [Q, Dp] fp32;  q_words [Q, W] uint32 (may be NULL when W == 0: no noun / verb vectors);
  *   q_state int32 {head, filled}, both 0 for an empty queue.  Slots >= filled are never used, whatever they hold.

@@ -158,6 +158,49 @@ def oracle_head(O, text, video, noun, verb, temperature=0.05, use_noun=True, use
     return loss.detach(), td.grad, vd.grad, mask
 
 
+# ---- the workspace layout, restated from the host code as it stood before the long and the queue head shared one layout function
+# (egl_prep_layout, egl_split, egl_layout, sig_layout, egl_args_ok): sizes in floats; a refused size is 0.
+STAT_WGS, GRAD_WGS, SIG_WALK_WGS = 512, 256, 512
+
+
+def args_ok(n, D, dn, dv):
+    return 1 <= n <= 65536 and 4 <= D <= 256 and D % 4 == 0 and 0 <= dn <= 65536 and 0 <= dv <= 65536
+
+
+def prep_layout(n, D, dn, dv):
+    """-> dict(np, Dp, wn, W, ntiles, total): what prep writes at the front of a tiled head's workspace"""
+    np_ = (n + TILE - 1) // TILE * TILE
+    Dp = 64 if D <= 64 else 256
+    wn = ((dn + 31) // 32 + 3) // 4 * 4
+    W = wn + ((dv + 31) // 32 + 3) // 4 * 4
+    return dict(np=np_, Dp=Dp, wn=wn, W=W, ntiles=np_ // TILE, total=2 * np_ * Dp + np_ * W + 2 * np_ + np_)
+
+
+def split(ntiles, target):
+    """the square split of the long and sigmoid heads -> (tiles per column range, ranges)"""
+    want = min((target + ntiles - 1) // ntiles, ntiles)
+    tps = (ntiles + want - 1) // want
+    return tps, (ntiles + tps - 1) // tps
+
+
+def long_work_floats(n, D, dn, dv):
+    """egv_egonce_long_work_floats"""
+    if not args_ok(n, D, dn, dv):
+        return 0
+    L = prep_layout(n, D, dn, dv)
+    ns_s, ns_g = split(L["ntiles"], STAT_WGS)[1], split(L["ntiles"], GRAD_WGS)[1]
+    return L["total"] + 2 * ns_s * 3 * L["np"] + 6 * L["np"] + ns_g * L["np"] * L["Dp"] + ns_g * L["ntiles"]
+
+
+def sigmoid_work_floats(n, D, dn, dv):
+    """egv_sigmoid_head_work_floats"""
+    if not args_ok(n, D, dn, dv):
+        return 0
+    L = prep_layout(n, D, dn, dv)
+    ns = split(L["ntiles"], SIG_WALK_WGS)[1]
+    return L["total"] + ns * L["np"] * L["Dp"] + 3 * ns * L["ntiles"]
+
+
 def rel(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).norm() / b.norm().clamp_min(1e-300))

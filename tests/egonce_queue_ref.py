@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE of the EgoNCE head with a queue of past embeddings (egovlp_amd/csrc/egonce_queue.hip):
+"""TEST INFRASTRUCTURE of the EgoNCE head with a queue of past embeddings (egovlp_amd/csrc/egonce_long.hip):
 
   * `oracle`: the loss in fp64 with autograd.  The K valid queue rows are constant extra columns of both softmaxes,
         Z_i = sum_j a_ij + sum_q a_iq,  P_i = sum_j m_ij a_ij + sum_q m_iq a_iq   (columns: the same with b_jq = exp(v_j . tq_q / tau)),
@@ -16,6 +16,37 @@ import torch
 import egonce_long_ref as R
 
 TILE = R.TILE
+
+
+# ---- the workspace layout, restated from the host code as it stood when the queue head had a layout function of its own
+# (egq_split, egq_layout, egq_args_ok, egv_egonce_queue_layout)
+def queue_args_ok(n, D, dn, dv, Q):
+    return R.args_ok(n, D, dn, dv) and TILE <= Q <= 65536 and Q % TILE == 0 and n <= Q
+
+
+def rect_split(rtiles, ctiles, target):
+    """`rtiles` row tiles against `ctiles` column tiles -> (tiles per column range, ranges)"""
+    want = min((target + rtiles - 1) // rtiles, ctiles)
+    tps = (ctiles + want - 1) // want
+    return tps, (ctiles + tps - 1) // tps
+
+
+def queue_work_floats(n, D, dn, dv, Q):
+    """egv_egonce_queue_work_floats"""
+    if not queue_args_ok(n, D, dn, dv, Q):
+        return 0
+    L = R.prep_layout(n, D, dn, dv)
+    ctiles = L["ntiles"] + Q // TILE
+    ns_s, ns_g = rect_split(L["ntiles"], ctiles, R.STAT_WGS)[1], rect_split(L["ntiles"], ctiles, R.GRAD_WGS)[1]
+    return L["total"] + 2 * ns_s * 3 * L["np"] + 6 * L["np"] + ns_g * L["np"] * L["Dp"] + 2 * ns_g * L["ntiles"]
+
+
+def queue_layout(D, dn, dv):
+    """egv_egonce_queue_layout -> (Dp, W), or None where it returns an error"""
+    if not R.args_ok(1, D, dn, dv):
+        return None
+    L = R.prep_layout(1, D, dn, dv)
+    return L["Dp"], L["W"]
 
 
 def normalise(x, eps=1e-8):

@@ -1,4 +1,4 @@
-"""The EgoNCE head with a queue of past embeddings (egovlp_amd/csrc/egonce_queue.hip) without a GPU: the test inputs' properties, the
+"""The EgoNCE head with a queue of past embeddings (egovlp_amd/csrc/egonce_long.hip) without a GPU: the test inputs' properties, the
 tiled algorithm restated in torch (tests/egonce_queue_ref.py) against the fp64 oracle, the host model of the ring, the constructor
 argument `queue_size` of EgoNCE / NormSoftmaxLoss, and the new entries of the C ABI.  Values on the device:
 tests/test_gpu_egonce_queue.py."""

@@ -1,4 +1,4 @@
-"""The EgoNCE head with a queue of past embeddings (egv_egonce_queue_fwd_bwd / _push, egovlp_amd/csrc/egonce_queue.hip) on a real MI355X
+"""The EgoNCE head with a queue of past embeddings (egv_egonce_queue_fwd_bwd / _push, egovlp_amd/csrc/egonce_long.hip) on a real MI355X
 (`pytest -m gpu`) against the fp64 oracle with autograd (tests/egonce_queue_ref.py), at the smallest sizes at which each thing can
 break: a single anchor, tile edges, a validity edge inside a queue tile next to a wholly unused tile, more than one column range, a
 batch past the short head's cap; every mask mode, the operand map, the learnable scale, determinism, the ring (wrap, overwritten
